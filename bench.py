@@ -1,10 +1,16 @@
 #!/usr/bin/env python
 """bench.py - train rays/s of the Switch-NeRF hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
-        N > 1 without torchrun's environment: bench.py re-launches itself as N ranks
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+        N > 1 without torchrun's environment: bench.py launches N ranks as a child process
         (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>)
         and fails if fewer than N devices are visible.  Under torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*.
+
+A plain run measures the headline only: set up, W warm-up steps, K timed steps, the line.  --full adds everything else the line can
+carry (the eager re-run of the step and `runner_loop_ms_per_step`, `kernels` / `roofline` with the library yardsticks, `balanced`,
+`cpu_baseline`, and for N > 1 or --loopback the all-reduce report and the expert-parallel reports / probes); without it those fields
+are null or empty.  --dump-outputs DIR writes what the last timed step returned to its caller (loss terms, rendered rgb / depth, and
+the parameters and gradient after the step; float32 .npy, 64 MB at most) so that two builds can be compared output for output.
 
 One step = one full training step of BASELINE.json configs[1]: 8192 synthetic rays x 256 samples (routing segments of 131072
 points), 8 experts top-1, capacity_factor 1.0, batch-prioritised routing, bf16 compute, stratified perturbation + sigma noise
@@ -38,37 +44,6 @@ import json
 import os
 import sys
 import time
-
-
-def _supervise():
-    """Single-GPU invocations run the measurement in a CHILD process and forward its output: if the child dies on a signal before it has
-    printed its line (seen once in ~60 runs of round 6: SIGSEGV, cause not found - profiles/r06_experiments.md 6), it is started once
-    more.  Nothing is measured in this process; multi-rank launches (torchrun / --gpus N) are not wrapped."""
-    if os.environ.get("SWN_BENCH_CHILD") == "1" or "WORLD_SIZE" in os.environ:
-        return
-    argv = sys.argv[1:]
-    if "--gpus" in argv and argv[argv.index("--gpus") + 1:][:1] not in (["1"],):
-        return
-    if any(a_.startswith("--gpus=") and a_ != "--gpus=1" for a_ in argv):
-        return
-    import subprocess
-    env = dict(os.environ, SWN_BENCH_CHILD="1")
-    rc = 1
-    for attempt in (1, 2):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv, env=env, stdout=subprocess.PIPE)
-        out = r.stdout.decode(errors="replace")
-        rc = r.returncode
-        if rc < 0 and not any(l.startswith("{") for l in out.splitlines()) and attempt == 1:
-            print(f"bench.py: the measuring process died on signal {-rc} before its line was out; starting it once more", file=sys.stderr, flush=True)
-            continue
-        sys.stdout.write(out)
-        sys.stdout.flush()
-        break
-    sys.exit(0 if rc < 0 and any(l.startswith("{") for l in out.splitlines()) else rc)
-
-
-if __name__ == "__main__":
-    _supervise()
 
 import torch
 
@@ -120,6 +95,27 @@ def cpu_baseline(seconds_budget=30.0):
     return dict(value=n_rays / t_best, unit="rays/s", cores=_host_cores(), threads=torch.get_num_threads(), kind="port",
                 sample=f"oracle fwd+bwd fp32 on 1 of 16 segments (512 rays x 256 samples = 131072 points), best of {reps}; "
                        f"{t_best:.2f} s/segment => {16 * t_best:.1f} s per 8192-ray step")
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000      # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy, float32 (float64 stays float64).  When the arrays exceed DUMP_LIMIT_BYTES the budget is
+    shared out smallest array first and an array larger than its share is written as a fixed sample of its flattened elements (the
+    same seeded, sorted index set in every run of the same shapes)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy() for k, t in arrays.items()}
+    left, n_left = DUMP_LIMIT_BYTES, len(host)
+    for k in sorted(host, key=lambda k_: (host[k_].nbytes, k_)):
+        v, share = host[k], left // n_left
+        if v.nbytes > share:
+            v = v.reshape(-1)
+            keep = share // v.itemsize
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+        left, n_left = left - v.nbytes, n_left - 1
 
 
 def main():
@@ -178,6 +174,12 @@ def main():
                     help="N > 1, data parallel: skip the expert-parallel measurement that otherwise follows the headline in the same line")
     ap.add_argument("--ep-probe-limit", type=float, default=180.0,
                     help="seconds the expert-parallel probe may take before the line is printed without it (a collective that never returns)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: eager re-run, runner loop, per-kernel timing + roofline + library yardsticks, "
+                         "balanced routing, CPU baseline, all-reduce / expert-parallel reports and probes (off: headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (loss terms, rgb / depth, parameters and gradient "
+                         "after the step) as DIR/<name>.npy, float32, 64 MB at most")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -266,10 +268,10 @@ def main():
                     from switch_nerf_amd.graph import GraphedRender
                     graphed[0] = GraphedRender(model, rays, idx, a.samples, a.chunk)
                 o_ = graphed[0](rays, idx)
-                return dict(ctx=dict(counts=eval_counts[0], cap=eval_counts[1]), loss=o_["rgb"].sum() * 0)
+                return dict(ctx=dict(counts=eval_counts[0], cap=eval_counts[1]), loss=o_["rgb"].sum() * 0, rgb=o_["rgb"], depth=o_["depth"])
             with torch.no_grad():
                 c = model.forward_rays(rays, idx, a.samples, a.chunk, 0.0, None, None, training=False)
-            return dict(ctx=c, loss=c["rgb"].sum() * 0)
+            return dict(ctx=c, loss=c["rgb"].sum() * 0, rgb=c["rgb"], depth=c["depth"])
         pr = torch.rand(n_rays, a.samples, device=dev)              # rendering.py:582 rand_like
         ar = allreduce if multi else None
         if a.mip:      # rendering_mip recipe: a.samples edges -> a.samples - 1 frustums per level, coarse + fine level
@@ -377,12 +379,18 @@ def main():
     reset_state(1234)
     dt, st = timed(a.steps, False)
     ms = dt / a.steps * 1e3
+    if a.dump_outputs and rank == 0:     # what the caller of the last timed step holds, before anything below runs more steps
+        outs = {k: v for k, v in st.items() if torch.is_tensor(v) and v.is_floating_point()}
+        if not a.eval:
+            for m, tag in zip(models, ("", "bg_")):
+                outs[tag + "params"], outs[tag + "grad"] = m.flat, m.grad
+        dump_outputs(a.dump_outputs, outs)
     ev_steps = max(3, min(10, a.steps))
     eager_ms = None
     ktimes, kkept = {}, None
     if use_graph:
         graphed[0] = None
-    if plain and not a.no_events:
+    if a.full and plain and not a.no_events:
         edt, st = timed(ev_steps, False)     # the same steps launched eagerly (reported next to the replayed number)
         eager_ms = edt / ev_steps * 1e3
         ktimes, kkept = kernel_times()       # back-to-back relaunches of the expert kernels on the next step's live buffers
@@ -599,7 +607,7 @@ def main():
     #      router fills some experts to capacity and starves others).  Point i goes to expert i mod E - every (segment, expert) group
     #      is exactly full, nothing is dropped; gate values, ranking, dispatch and every kernel run as usual.
     balanced = None
-    if not other and not a.no_balanced and not a.fine and a.routing == "router":
+    if a.full and not other and not a.no_balanced and not a.fine and a.routing == "router":
         route_override[0] = (torch.arange(P, device=dev, dtype=torch.int32) % E).contiguous()
         reset_state(4321)
         if use_graph:
@@ -621,7 +629,7 @@ def main():
     # ---- the loop a maintainer of the reference would run (runner.py:604-693): rendering.render_rays under autograd, loss.backward(),
     #      torch.optim.Adam on the flat parameter, ExponentialLR - forward / backward replayed from captured graphs (nerf.graph_train)
     runner_ms = None
-    if plain and not other and world == 1 and not a.no_events:        # (the headline recipe only)
+    if a.full and plain and not other and world == 1 and not a.no_events:        # (the headline recipe only)
         from argparse import Namespace
         from switch_nerf_amd import rendering
         reset_state(1234)
@@ -693,12 +701,12 @@ def main():
                           "64-row tail launches (the fused tail rides the expert launch of LOCAL experts only: INTEGRATION.md section 5)"))
 
     ep_info = None
-    if a.parallelism == "ep" and model.ep is not None:
+    if a.full and a.parallelism == "ep" and model.ep is not None:
         ep_info = ep_report()
 
     # ---- data parallel: the gradient all-reduce - its time and how much of it ran under the second backward graph
     ar_info = None
-    if multi and a.parallelism == "dp" and hasattr(allreduce, "report"):
+    if a.full and multi and a.parallelism == "dp" and hasattr(allreduce, "report"):
         if use_graph and graphed[0] is None:
             graphed[0] = GraphedTrainStep(model, rgbs, rays, idx, a.samples, a.chunk, perturb=1.0, noise_std=1.0, split_backward=split_bwd)
         allreduce.profile = True
@@ -745,7 +753,7 @@ def main():
                                      "reference's loop (render_rays under autograd + loss.backward() + torch.optim.Adam + ExponentialLR) with the "
                                      "forward and backward graphs of nerf.graph_train; `kernels`: every expert kernel relaunched 5 x back to back "
                                      "on one step's live buffers between two HIP events on the launch stream (independent of the host's launch rate)")
-                                    if not a.no_events else "no per-kernel timing")},
+                                    if a.full and not a.no_events else "no per-kernel timing")},
         "roofline": roof, "kernels": detail, "balanced": balanced,
     }
     if ep_info is not None:
@@ -758,7 +766,7 @@ def main():
     #      same line (north_star: RCCL all-to-all over xGMI in place of Tutel's; BASELINE configs[2]) - experts sharded E / N per GPU, kept
     #      rows exchanged per routing segment on a side stream, eager launches (the kept-rows mode reads split sizes on the host).
     #      A watchdog prints the line without it if a collective never returns: the headline must not depend on the probe.
-    if multi and a.parallelism == "dp" and plain and not other and not a.no_ep_probe and model.E % world == 0:
+    if a.full and multi and a.parallelism == "dp" and plain and not other and not a.no_ep_probe and model.E % world == 0:
         import threading
 
         probe_done = threading.Event()
@@ -797,7 +805,7 @@ def main():
         probe_done.set()
         dog.cancel()
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline and not other and not a.loopback:
+        if a.full and world == 1 and not a.no_cpu_baseline and not other and not a.loopback:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:      # the baseline must never take the bench line down
@@ -816,8 +824,10 @@ def main():
 
 
 def self_launch(n: int):
-    """`python bench.py --gpus N` without torchrun's environment: become the launcher of N ranks on this node (one per GPU, RCCL)."""
+    """`python bench.py --gpus N` without torchrun's environment: start the launcher of N ranks on this node (one per GPU, RCCL) as a
+    child process and exit with its status."""
     import socket
+    import subprocess
     have = torch.cuda.device_count()
     if have < n and "SWN_FORCE_DEVICE" not in os.environ:
         raise SystemExit(f"bench.py: --gpus {n} but only {have} GPU(s) are visible on this node")
@@ -828,7 +838,7 @@ def self_launch(n: int):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 if __name__ == "__main__":

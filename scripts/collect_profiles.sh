@@ -42,10 +42,10 @@ SWN_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats -d gpurun_out/p_1024 -o step -
 python scripts/prof_summary.py $(find gpurun_out/p_1024 -name "*.db" | head -1) 45 > $O/${R}_kernel_stats_1024rays.md
 rm -rf gpurun_out/p_1024
 # (d) the bench lines
-python bench.py > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench_20_5.json 2>/dev/null
+python bench.py --full > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_20_5.json 2>/dev/null
 SWN_NO_OVERLAP=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-balanced --no-events > $O/${R}_bench_no_overlap.json 2>/dev/null
-python bench.py --rays 1024 --steps 100 --warmup 20 --no-cpu-baseline --no-balanced --graph on > $O/${R}_bench_1024rays_graph.json 2>/dev/null
+python bench.py --full --rays 1024 --steps 100 --warmup 20 --no-cpu-baseline --no-balanced --graph on > $O/${R}_bench_1024rays_graph.json 2>/dev/null
 python bench.py --rays 1024 --steps 100 --warmup 20 --no-cpu-baseline --no-balanced --graph off --no-events > $O/${R}_bench_1024rays_eager.json 2>/dev/null
 python bench.py --eval --steps 50 --warmup 10 --no-cpu-baseline > $O/${R}_bench_eval_graph.json 2>/dev/null
 python bench.py --eval --graph off --steps 50 --warmup 10 --no-cpu-baseline > $O/${R}_bench_eval_eager.json 2>/dev/null

@@ -39,9 +39,9 @@ SWN_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats -d gpurun_out/p_1024 -o step -
 python scripts/prof_summary.py $(find gpurun_out/p_1024 -name "*.db" | head -1) 45 > $O/${R}_kernel_stats_1024rays.md
 rm -rf gpurun_out/p_1024
 # (d) the bench lines (traffic.json of THIS build is in place: roofline.traffic is reported)
-python bench.py > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench_20_5.json 2>/dev/null
-python bench.py --rays 1024 --steps 100 --warmup 20 --no-cpu-baseline --no-balanced --graph on > $O/${R}_bench_1024rays_graph.json 2>/dev/null
+python bench.py --full > $O/${R}_bench_default.json 2> $O/${R}_bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_20_5.json 2>/dev/null
+python bench.py --full --rays 1024 --steps 100 --warmup 20 --no-cpu-baseline --no-balanced --graph on > $O/${R}_bench_1024rays_graph.json 2>/dev/null
 python bench.py --rays 1024 --steps 100 --warmup 20 --no-cpu-baseline --no-balanced --graph off --no-events > $O/${R}_bench_1024rays_eager.json 2>/dev/null
 python bench.py --eval --steps 50 --warmup 10 --no-cpu-baseline > $O/${R}_bench_eval_graph.json 2>/dev/null
 ls -la $O | head -60
@@ -56,11 +56,11 @@ python scripts/prof_summary.py $(find gpurun_out/p_mb -name "*.db" | head -1) 30
 rm -rf gpurun_out/p_mb
 # (f) the recipes' bench lines
 ( for fl in "" "--bg" "--bg --fine 512" "--dense" "--hash --capacity-factor 1.25" "--hash --capacity-factor 1.25 --dtype fp16" "--eval" "--fine 512" "--mip --samples 257" "--mip --samples 257 --rays 3328 --chunk 212992 --model-dim 512 --experts 16" "--dtype fp16"; do
-    echo "### bench.py $fl"; python bench.py $fl --no-cpu-baseline --no-balanced --steps 10 --warmup 3 2>/dev/null | tail -1; done ) > $O/${R}_bench_recipes.txt
+    echo "### bench.py $fl"; python bench.py $fl --full --no-cpu-baseline --no-balanced --steps 10 --warmup 3 2>/dev/null | tail -1; done ) > $O/${R}_bench_recipes.txt
 # (g) the one-GPU rehearsal of the multi-GPU step over RCCL (world-1 loopback)
-python bench.py --gpus 1 --loopback --rays 1024 --steps 50 --warmup 10 --no-cpu-baseline --no-balanced --no-events > $O/${R}_bench_loopback_dp_1024rays.json 2>/dev/null
-python bench.py --gpus 1 --loopback --parallelism ep --steps 10 --warmup 3 --no-cpu-baseline --no-balanced --no-events > $O/${R}_bench_loopback_ep.json 2>/dev/null
-python bench.py --gpus 1 --loopback --parallelism ep --ep-owner-tail --steps 10 --warmup 3 --no-cpu-baseline --no-balanced --no-events > $O/${R}_bench_loopback_ep_owner_tail.json 2>/dev/null
+python bench.py --full --gpus 1 --loopback --rays 1024 --steps 50 --warmup 10 --no-cpu-baseline --no-balanced --no-events > $O/${R}_bench_loopback_dp_1024rays.json 2>/dev/null
+python bench.py --full --gpus 1 --loopback --parallelism ep --steps 10 --warmup 3 --no-cpu-baseline --no-balanced --no-events > $O/${R}_bench_loopback_ep.json 2>/dev/null
+python bench.py --full --gpus 1 --loopback --parallelism ep --ep-owner-tail --steps 10 --warmup 3 --no-cpu-baseline --no-balanced --no-events > $O/${R}_bench_loopback_ep_owner_tail.json 2>/dev/null
 # (h) the 512-feature router against fp64 + timing, both 16-bit builds
 GATE_G=512 GATE_E=16 python scripts/gate_check.py 2>&1 | grep -v amdgpu > $O/${R}_gate_check_512x16.txt
 GATE_G=512 GATE_E=16 GATE_DTYPE=fp16 python scripts/gate_check.py 2>&1 | grep -v amdgpu > $O/${R}_gate_check_512x16_fp16.txt

@@ -66,3 +66,31 @@ def test_kernel_switches_are_resolved_once_from_the_environment():
     src = inspect.getsource(SwitchNeRF)
     body = src[src.index("def forward_rays"):]
     assert "os.environ" not in body, "forward / backward must not read the environment"
+
+
+def test_dump_outputs_are_float32_within_budget_and_sampled_the_same_way_every_run(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one .npy per array (float32; float64 stays float64), all of them within the byte budget, and an array
+    larger than its share written as the same fixed sample of its elements in every run."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    arrays = dict(loss=torch.tensor(0.25, dtype=torch.float64), rgb=torch.rand(10, 3).to(torch.bfloat16),
+                  params=torch.arange(5000, dtype=torch.float32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {d: {k: np.load(tmp_path / d / f"{k}.npy") for k in arrays} for d in ("a", "b")}
+    a = got["a"]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["loss.npy", "params.npy", "rgb.npy"]
+    assert a["loss"].dtype == np.float64 and a["loss"].shape == () and a["loss"] == 0.25
+    assert a["rgb"].dtype == np.float32 and a["rgb"].shape == (10, 3)
+    np.testing.assert_array_equal(a["rgb"], arrays["rgb"].float().numpy())
+    p = a["params"]
+    assert p.dtype == np.float32 and p.ndim == 1 and 0 < p.size < 5000
+    assert np.all(np.diff(p) > 0) and np.all(p == np.round(p)) and p.max() < 5000       # sorted distinct elements of the original
+    assert sum(v.nbytes for v in a.values()) <= 4000
+    for k in arrays:
+        np.testing.assert_array_equal(a[k], got["b"][k])

@@ -40,7 +40,7 @@ def test_rccl_split_backward_graphs_with_overlapped_allreduce_50_steps():
 
 def _bench(port, extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--loopback", "--steps", "3", "--warmup", "1", "--rays", "1024",
-           "--no-events", "--no-balanced", "--no-cpu-baseline"] + list(extra)
+           "--no-events", "--no-balanced", "--no-cpu-baseline", "--full"] + list(extra)
     out = subprocess.run(cmd, env={k: v for k, v in _env(port).items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}, cwd=ROOT,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-2500:])
