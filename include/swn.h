@@ -224,6 +224,14 @@ int swn_route_dropped(const int32_t* idx, const int32_t* loc, const int32_t* cou
 int swn_route_pack(const int32_t* idx, const int32_t* loc, const int32_t* counts, int n_tokens, int seg_tokens, int n_experts,
                    int32_t* begin, int32_t* perm, int32_t* tok2row, void* stream);
 
+/* Top-1 routing WITHOUT dropping, straight into the packed row space (capacity_factor = 0 in training, tutel_fast_dispatch.py:212-213:
+ * a capacity no group exceeds).  loc, counts and l_aux are swn_route_top1's (same ranking, same bits); begin[n_seg * E], perm[n_tokens]
+ * (row -> token) and tok2row[n_tokens] (token -> row, may be NULL) are swn_route_pack's layout, written by the routing itself: row
+ * begin[g] + loc of group g = (segment, expert).  No strided [n_seg, E * capacity] perm.  workspace: swn_route_workspace_bytes().   */
+int swn_route_top1_packed(const int32_t* idx, const float* gmax, const float* gates, int n_tokens, int seg_tokens, int n_experts,
+                          int bpr, int32_t* loc, int32_t* counts, int32_t* begin, int32_t* perm, int32_t* tok2row, float* l_aux,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fast-path combine (the reference's decode + the MoE layer's `act: relu`, models/nerf_moe.py:385-386):
  * y[i] = relu?(gate[i] * expert_out[seg(i)*E*C + idx*C + loc]), zero rows for dropped tokens.                 */
 int swn_combine_fwd(const float* gates, const int32_t* indices, const int32_t* locations, void* y,
@@ -512,6 +520,15 @@ typedef struct swn_chain_desc {
                                    the expert's rank, ep_owner.py: the tokens an owner received from every rank, rowbias = the all-gathered
                                    per-ray terms)                                                                                       */
   swn_chain_layer layers[SWN_MAX_CHAIN_LAYERS];
+  /* Packed ReLU-mask slots (packed_rows > 0; group_begin required; geometry 0 / 1 and 7 - the others refuse it): the row space holds
+     at most packed_rows rows, packed per group through group_begin (the no-drop training layout, swn_route_top1_packed), and tile t
+     of group g keeps its masks in slot floor(group_begin[g] / BM) + g + t (BM = the kernel's tile rows) instead of
+     g * ceil(group_stride / BM) + t - unique over the groups and below ceil(packed_rows / BM) + n_groups, so the mask buffers
+     (swn_chain_mask_words_packed) follow the rows, not n_groups * group_stride.  Geometry 7 walks exactly these slots as its tile
+     queue (a fused backward's comb_dwsig_ws then holds (ceil(packed_rows / 256) + n_groups) * 8 rows:
+     swn_chain_dwsig_workspace_bytes(1, packed_rows + 256 * n_groups)).  Forward and backward chains must both set it.
+     0 = the strided slots.                                                                                                         */
+  int32_t packed_rows;
 } swn_chain_desc;
 
 int swn_mlp_chain(const swn_chain_desc* desc, void* stream);
@@ -524,6 +541,9 @@ int swn_chain_tile_rows(int dtype);
 /* uint32 words of one ReLU mask buffer of a chain over n_groups x group_stride rows whose widest layer has max_width features
  * (layers wider than 256 features run on the 512-feature kernels, whose tiles carry twice the bits per row).           */
 long swn_chain_mask_words(int dtype, int n_groups, int group_stride, int max_width);
+/* ... the same for the packed slots (swn_chain_desc.packed_rows = rows): *words = uint32 words of one mask buffer of a chain over at
+ * most `rows` packed rows in n_groups groups, for every geometry that accepts packed slots.                                  */
+int swn_chain_mask_words_packed(int dtype, int rows, int n_groups, int max_width, int64_t* words);
 
 /* Pack fp32 master weights [n_wsets][in_dim][out_dim] (the reference's ExpertMLP layout, tutel_moe_layer_nobatch.py:853)
  * into the compute copy swn_mlp_chain consumes.  transpose = 1: forward weights (N = out, K = in);

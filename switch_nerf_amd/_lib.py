@@ -59,7 +59,7 @@ class ChainDesc(C.Structure):
                 ("heads_ws", vp), ("heads_bs", vp), ("heads_wc", vp), ("heads_bc", vp), ("heads_noise", vp), ("heads_raw", vp), ("sched", vp), ("x_features", i32),
                 ("head_layers", i32), ("tail_first", i32), ("y_features", i32), ("tail_gate", vp), ("tail_dropped", vp), ("tail_n_dropped", vp),
                 ("tail_dropped_max", i32), ("tail_tokens", i32), ("tail_bias_row", vp),
-                ("layers", ChainLayer * 12)]
+                ("layers", ChainLayer * 12), ("packed_rows", i32)]
 
 
 # name -> argtypes; every symbol declared in include/swn.h must be listed here (tests/test_abi.py checks both ways)
@@ -92,6 +92,8 @@ SIGNATURES = {
     "swn_dispatch_nobatch_bwd_data": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "swn_dispatch_nobatch_bwd_gate": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "swn_route_pack": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "swn_route_top1_packed": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "swn_chain_mask_words_packed": [i32, i32, i32, i32, vp],
     "swn_route_dropped": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],
     "swn_combine_fwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "swn_combine_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],

@@ -644,6 +644,8 @@ __global__ __launch_bounds__(NT, Cfg<T>::OCC) void chain_kernel(const ChainArgs 
   const int rows_in_tile = min(BM, rows_valid - row0);
   const long grow0 = (d.group_begin ? (long)d.group_begin[g] : (long)g * d.group_stride) + row0;
   const int wset = g % d.n_wsets;
+  // the tile's ReLU-mask slot: packed (swn_chain_desc.packed_rows) or strided
+  const long mslot = d.packed_rows > 0 ? (long)(d.group_begin[g] / BM) + g + tile : (long)g * args.tiles_per_group + tile;
 
   // per-lane LDS byte offsets of the activation fragments (the swizzle makes them non-affine in k: 8 (bf16) / 16
   // (fp32) distinct values; everything else is an immediate offset)
@@ -795,7 +797,7 @@ __global__ __launch_bounds__(NT, Cfg<T>::OCC) void chain_kernel(const ChainArgs 
     const bool mpre_on = ly.relu == 2 && ly.mask != nullptr && wave_active;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
-      mpre[mi] = mpre_on ? ly.mask[(size_t)((g * args.tiles_per_group + tile) * (NT / 64) + wn) * MI * 64 * (NI / 2) + lane + mi * 64] : 0u;
+      mpre[mi] = mpre_on ? ly.mask[(size_t)(mslot * (NT / 64) + wn) * MI * 64 * (NI / 2) + lane + mi * 64] : 0u;
 #endif
 #if SWN_TIMING_ON
     long long q0 = TICK();
@@ -851,7 +853,7 @@ __global__ __launch_bounds__(NT, Cfg<T>::OCC) void chain_kernel(const ChainArgs 
       int l31e = l31, lhie = lhi;
       asm volatile("" : "+v"(l31e), "+v"(lhie));
       const float* rbp = ly.rowbias ? ly.rowbias + (grow0 / ly.rows_per_bias) * (size_t)n : nullptr;   // tile-aligned per-ray bias
-      uint32_t* mk = ly.mask ? ly.mask + (size_t)((g * args.tiles_per_group + tile) * (NT / 64) + wn) * MI * 64 * (NI / 2) + lane : nullptr;
+      uint32_t* mk = ly.mask ? ly.mask + (size_t)(mslot * (NT / 64) + wn) * MI * 64 * (NI / 2) + lane : nullptr;
       const int nvalid = n - wn * 32 * NI;   // feature tiles of this wave that exist: nvalid >= 32 NI -> all
 #if SWN_WIDE == 2 && !SWN_CONCAT
       epilogue_body<T, true, 0, false, false, false>(acc, act, bias_lds, rbp, mk, wn, l31e, lhie, nvalid, grow0, ly.rows_per_bias, n,
@@ -1256,6 +1258,25 @@ extern "C" long swn_chain_mask_words(int dtype, int n_groups, int group_stride, 
   return words;
 }
 
+/* ... for the packed slots (swn_chain_desc.packed_rows): ceil(rows / BM) + n_groups tiles of every geometry that accepts them */
+extern "C" int swn_chain_mask_words_packed(int dtype, int rows, int n_groups, int max_width, int64_t* words) {
+  SWN_CHECK(words && rows >= 0 && n_groups >= 1, "swn_chain_mask_words_packed: bad arguments (rows %d, groups %d)", rows, n_groups);
+  const bool wide = max_width > 256;
+  const int bm = wide ? chain_wide_tile_rows(dtype) : swn_chain_tile_rows(dtype);
+  long w = ((long)cdiv(rows, bm) + n_groups) * bm * (wide ? 16 : 8);
+  if (wide && dtype != SWN_F32) {              // the 128-row tiles of the 512-feature chains
+    const int bm2 = chain_wide2_tile_rows();
+    const long w2 = ((long)cdiv(rows, bm2) + n_groups) * bm2 * 16;
+    if (w2 > w) w = w2;
+  }
+  if (!wide && dtype != SWN_F32) {             // geometry 7 (chain_big.hip's 256-row tiles)
+    const long w7 = ((long)cdiv(rows, chain_big_tile_rows(7)) + n_groups) * chain_big_mask_words_per_tile(7);
+    if (w7 > w) w = w7;
+  }
+  *words = w;
+  return 0;
+}
+
 extern "C" int swn_mlp_chain(const swn_chain_desc* desc, void* stream) {
   SWN_CHECK(desc != nullptr, "swn_mlp_chain: null descriptor");
   const swn_chain_desc& d = *desc;
@@ -1303,6 +1324,12 @@ extern "C" int swn_mlp_chain(const swn_chain_desc* desc, void* stream) {
             "swn_mlp_chain: x_features = %d: only 128-feature rows under a zero-padded k = 256 first layer on geometry 6 / 7", d.x_features);
   SWN_CHECK(!(wide && concat), "swn_mlp_chain: concat-skip layers are built for the 256-feature kernels only");
   SWN_CHECK(d.geometry >= 0 && d.geometry <= 7, "swn_mlp_chain: geometry %d not in [0,7]", d.geometry);
+  SWN_CHECK(d.packed_rows >= 0, "swn_mlp_chain: packed_rows %d < 0", d.packed_rows);
+  if (d.packed_rows > 0) {
+    SWN_CHECK(d.group_begin != nullptr, "swn_mlp_chain: packed mask slots (packed_rows > 0) address the groups through group_begin");
+    SWN_CHECK(d.geometry <= 1 || d.geometry == 7, "swn_mlp_chain: packed mask slots (packed_rows > 0) run on geometry 0 / 1 or 7, not %d",
+              d.geometry);
+  }
   if (d.comb_y && d.head_layers == 0) {      // (head_layers > 0: the combine backward sits behind the head layers - chain_persistent_eligible)
     const int nl = d.layers[d.n_layers - 1].n;
     SWN_CHECK(d.comb_gate && d.comb_dgate, "swn_mlp_chain: combine backward needs comb_gate and comb_dgate");

@@ -1594,7 +1594,18 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
           break;
         }
       }
-      if ((n_wsets & 7) == 0 && (n_groups & 7) == 0) {           // chainp_kernel's mapping: XCD x meets every weight set in turn
+      if (d.packed_rows > 0) {                                    // packed slots (swn_chain_desc.packed_rows): vb IS the mask slot
+        // floor(group_begin[g] / BM) + g + tile, strictly increasing in g: the group is the last one whose first slot is <= vb
+        // (an empty group owns one slot with no rows; the slots behind the last rows are empty too)
+        int lo = 0, hi = n_groups - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (d.group_begin[mid] / BM + mid <= vb) lo = mid;
+          else hi = mid - 1;
+        }
+        g = lo;
+        tile = vb - (d.group_begin[g] / BM + g);
+      } else if ((n_wsets & 7) == 0 && (n_groups & 7) == 0) {           // chainp_kernel's mapping: XCD x meets every weight set in turn
         const int x = vb & 7, qq = vb >> 3;
         const int s_ = qq / tpg;
         tile = qq - s_ * tpg;
@@ -1606,7 +1617,7 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
       rows_valid = d.group_stride;
       if (d.group_rows) rows_valid = d.group_rows[g];
       if (rows_valid > d.group_rows_clamp) rows_valid = d.group_rows_clamp;
-      if (tile * BM < rows_valid) break;
+      if (tile >= 0 && tile * BM < rows_valid) break;
     }
     if (fresh_lane() == 0) {
       int* t = (int*)(smem + Q_TINFO) + slot * 8;
@@ -2278,8 +2289,10 @@ static int chain_persistent_launch(const swn_chain_desc& d, void* stream) {
   a.d = d;
   a.tiles_per_group = cdiv(d.group_rows ? (d.group_rows_clamp < d.group_stride ? d.group_rows_clamp : d.group_stride) : d.group_stride, G::BM);
   if (!d.group_rows) a.d.group_rows_clamp = d.group_stride;
-  const long n_vb = (long)a.tiles_per_group * d.n_groups;
+  const bool packed = d.packed_rows > 0;      // the queue walks the packed mask slots (swn_chain_desc.packed_rows)
+  const long n_vb = packed ? (long)cdiv(d.packed_rows, G::BM) + d.n_groups : (long)a.tiles_per_group * d.n_groups;
   SWN_CHECK(n_vb > 0 && n_vb < (1L << 28), "swn_mlp_chain: %ld tiles out of range", n_vb);
+  SWN_CHECK(!packed || d.geometry == 7, "swn_mlp_chain: packed mask slots run on geometry 7 (the persistent chains), not %d", d.geometry);
   a.n_vb = a.n_vb_e = (int)n_vb;
   if (d.tail_first > 0 || d.head_layers > 0) a.n_vb += cdiv(d.tail_dropped_max, G::BM);      // tiles of the dropped tokens behind the experts' (the count is a
                                                                         // device scalar: tiles beyond it end the queue)
@@ -2287,12 +2300,13 @@ static int chain_persistent_launch(const swn_chain_desc& d, void* stream) {
   const char* ov = getenv("SWN_CHAINQ_WGS");            // experiments
   if (ov && atoi(ov) > 0) grid = atoi(ov);
   if (grid > n_vb) grid = (int)n_vb;
-  const bool rotated = (d.n_wsets & 7) == 0 && (d.n_groups & 7) == 0;
+  const bool rotated = !packed && (d.n_wsets & 7) == 0 && (d.n_groups & 7) == 0;
   a.n_queues = (rotated && grid % 8 == 0 && d.sched) ? 8 : 1;
   a.per_queue = 0;
-  if (!rotated && d.n_groups == 1 && grid % 8 == 0 && d.sched && n_vb >= 64) {      // one group (dense chains): XCD x walks its own eighth
+  // one group (dense chains) or packed slots (in group order: an eighth covers about one expert per segment): XCD x walks its own eighth
+  if (!rotated && (d.n_groups == 1 || packed) && grid % 8 == 0 && d.sched && n_vb >= 64) {
     a.n_queues = 8;
-    a.per_queue = (int)cdiv(n_vb, 8);
+    a.per_queue = (int)cdiv(packed ? a.n_vb : n_vb, 8);      // (packed: a fused tail's dropped-token tiles included)
   }
   a.stagger = 0;                                        // (a start offset between the workgroups of an XCD: measured, no effect - r04_experiments.md 2)
   const void* fn;

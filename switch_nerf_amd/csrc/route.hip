@@ -238,6 +238,34 @@ __global__ void route_finalize_kernel(const uint32_t* __restrict__ keys, const i
   }
 }
 
+// Packed no-drop form (swn_route_top1_packed): every token keeps its row, and the rows of group g = (segment, expert) sit contiguously at
+// [begin[g], begin[g] + counts[g]).  With begin = segment * seg_tokens + the exclusive prefix of the segment's counts (what
+// route_pack_begin_kernel computes) the packed row of the token at sorted position pos is begin + loc = segment * seg_tokens + pos: the
+// sorted order IS the packed row space, so the finalize writes perm / tok2row / begin directly (no strided perm, no pack pass).
+// Threads i < n_groups also write begin[i] (grid: max(n_tokens, n_groups) threads).
+__global__ void route_finalize_packed_kernel(const uint32_t* __restrict__ keys, const int32_t* __restrict__ vals,
+                                             const int32_t* __restrict__ counts, int n_tokens, int seg_tokens, int E, int n_groups,
+                                             int32_t* __restrict__ loc, int32_t* __restrict__ begin, int32_t* __restrict__ perm,
+                                             int32_t* __restrict__ tok2row) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_groups) {
+    const int gs = (int)(i / E), ge = (int)(i - (long)gs * E);
+    int start = 0;
+    for (int q = 0; q < ge; ++q) start += counts[gs * E + q];
+    begin[i] = gs * seg_tokens + start;
+  }
+  if (i >= n_tokens) return;
+  const int seg = (int)(i / seg_tokens);
+  const int pos = (int)(i - (long)seg * seg_tokens);
+  const int e = (int)(keys[i] >> 26);
+  int start = 0;
+  for (int q = 0; q < e; ++q) start += counts[seg * E + q];
+  const long tok = (long)seg * seg_tokens + vals[i];
+  loc[tok] = pos - start;
+  perm[i] = (int32_t)tok;
+  if (tok2row) tok2row[tok] = (int32_t)i;
+}
+
 // No-batch (evaluation) layout, tutel_fast_dispatch_nobatch.py:24-36: the rows of group g = (segment, expert) sit contiguously at
 // [begin[g], begin[g] + counts[g]), begin = exclusive prefix sum of the counts (expert_locations_begin), nothing is dropped.
 // One block computes begin (n_groups <= 4096); the tokens then scatter themselves.
@@ -375,7 +403,7 @@ extern "C" int swn_route_top1x(const int32_t* idx, const float* gmax, const floa
 static int route_choice(const int32_t* idx, const float* gmax, const float* gates, int n_tokens, int seg_tokens,
                         int n_experts, int capacity, int bpr, int32_t* loc, int32_t* counts, int32_t* perm,
                         int32_t* tok2row, float* l_aux, void* workspace, size_t workspace_bytes, void* stream,
-                        const int32_t* prev, int n_prev) {
+                        const int32_t* prev, int n_prev, int32_t* begin = nullptr) {
   SWN_CHECK(idx && gmax && loc && counts && workspace, "swn_route_top1: null pointer");
   SWN_CHECK(n_tokens > 0 && seg_tokens > 0 && n_tokens % seg_tokens == 0,
             "swn_route_top1: n_tokens (%d) must be a positive multiple of seg_tokens (%d)", n_tokens, seg_tokens);
@@ -399,7 +427,7 @@ static int route_choice(const int32_t* idx, const float* gmax, const float* gate
   hipError_t e = use_memset ? hipMemsetAsync(counts, 0, (size_t)n_seg * n_experts * 4, s)
                             : fill_u32_async(counts, 0u, (size_t)n_seg * n_experts * 4, s);
   SWN_CHECK(e == hipSuccess, "fill: %s", hipGetErrorString(e));
-  if (perm && n_prev == 0) {
+  if (perm && n_prev == 0 && !begin) {
     e = use_memset ? hipMemsetAsync(perm, 0xFF, (size_t)n_seg * n_experts * capacity * 4, s)
                    : fill_u32_async(perm, 0xFFFFFFFFu, (size_t)n_seg * n_experts * capacity * 4, s);
     SWN_CHECK(e == hipSuccess, "fill: %s", hipGetErrorString(e));
@@ -422,8 +450,14 @@ static int route_choice(const int32_t* idx, const float* gmax, const float* gate
     uint32_t* tk = ki; ki = ko; ko = tk;
     int32_t* tv = vi; vi = vo; vo = tv;
   }
-  hipLaunchKernelGGL(route_finalize_kernel, dim3(cdiv(n_tokens, 256)), dim3(256), 0, s, ki, vi, counts, n_tokens,
-                     seg_tokens, n_experts, capacity, loc, perm, tok2row, prev, n_prev);
+  if (begin) {      // packed no-drop form (top-1 only: n_prev == 0)
+    const int n_groups = n_seg * n_experts;
+    hipLaunchKernelGGL(route_finalize_packed_kernel, dim3(cdiv(max(n_tokens, n_groups), 256)), dim3(256), 0, s, ki, vi, counts, n_tokens,
+                       seg_tokens, n_experts, n_groups, loc, begin, perm, tok2row);
+  } else {
+    hipLaunchKernelGGL(route_finalize_kernel, dim3(cdiv(n_tokens, 256)), dim3(256), 0, s, ki, vi, counts, n_tokens,
+                       seg_tokens, n_experts, capacity, loc, perm, tok2row, prev, n_prev);
+  }
   SWN_LAUNCH_CHECK();
   if (gates && l_aux) {
     hipLaunchKernelGGL(laux_partial_kernel, dim3(nblk, n_seg), dim3(256), 0, s, gates, seg_tokens, n_experts, nblk, partial);
@@ -438,6 +472,15 @@ extern "C" int swn_route_top1(const int32_t* idx, const float* gmax, const float
                               int32_t* tok2row, float* l_aux, void* workspace, size_t workspace_bytes, void* stream) {
   return route_choice(idx, gmax, gates, n_tokens, seg_tokens, n_experts, capacity, bpr, loc, counts, perm, tok2row, l_aux, workspace,
                       workspace_bytes, stream, nullptr, 0);
+}
+
+extern "C" int swn_route_top1_packed(const int32_t* idx, const float* gmax, const float* gates, int n_tokens, int seg_tokens,
+                                     int n_experts, int bpr, int32_t* loc, int32_t* counts, int32_t* begin, int32_t* perm,
+                                     int32_t* tok2row, float* l_aux, void* workspace, size_t workspace_bytes, void* stream) {
+  SWN_CHECK(begin && perm, "swn_route_top1_packed: begin and perm are required");
+  // the ranking, counts and l_aux of swn_route_top1 (same kernels, same bits); capacity = seg_tokens: nothing is dropped
+  return route_choice(idx, gmax, gates, n_tokens, seg_tokens, n_experts, seg_tokens, bpr, loc, counts, perm, tok2row, l_aux, workspace,
+                      workspace_bytes, stream, nullptr, 0, begin);
 }
 
 // ---- top-k (k > 1) ------------------------------------------------------------------------------------------------------------

@@ -45,7 +45,7 @@ class GraphedTrainStep:
                  routing_override=None, warmup: int = 2, split_backward=None):
         N, S = rays.shape[0], int(n_samples)
         if model.ep is not None:
-            seg_payload = model.E * int(model.cf * ((min(int(seg_tokens), N * S) + model.E - 1) // model.E)) * model.M * (4 if model.dtype == torch.float32 else 2)
+            seg_payload = model.E * model.capacity(min(int(seg_tokens), N * S)) * model.M * (4 if model.dtype == torch.float32 else 2)
             if not (model.ep.capturable and model.ep.use_padded(seg_payload)):
                 raise ValueError("GraphedTrainStep: the expert-parallel step with unequal splits reads their sizes on the host and cannot be "
                                  "captured; use SwitchNeRF.train_step, or ExpertParallel(..., padded=True) (equal, capacity-padded splits)")

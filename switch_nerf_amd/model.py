@@ -100,6 +100,10 @@ class LossScaler:
         self._good = int(sd.get("_growth_tracker", 0))
 
 
+DYNCAP_EP_ERROR = ("capacity_factor = 0 (dynamic capacity, nothing dropped) is not supported with expert parallelism: the exchange "
+                   "buffers are sized by a static capacity; use capacity_factor > 0, or < 0 (the dynamic capacity clamped at the static one)")
+
+
 class SwitchNeRF:
     def __init__(self, cfg: dict = BUILDING, dtype=torch.bfloat16, device="cuda", capacity_factor=1.0,
                  batch_prioritized=True, moe_l_aux_wt=5e-4, lr=5e-4, seed=0, gate_noise=-1.0, kernel_switches=None):
@@ -116,6 +120,8 @@ class SwitchNeRF:
         elif dtype == torch.bfloat16:
             _lib.use_half("bf16")
         self.loss_scaler = LossScaler() if dtype == torch.float16 else None
+        # capacity_factor (--moe_capacity_factor, opts.py:118): > 0 a static capacity; 0 the reference's dynamic capacity, nothing dropped
+        # (the packed no-drop row space below); < 0 the dynamic capacity clamped at the static one of |cf| - see capacity()
         self.cf, self.bpr, self.wt, self.lr = capacity_factor, batch_prioritized, moe_l_aux_wt, lr
         # --gate_noise (opts.py:208, default -1 = off): a TRAINING forward adds gate_noise * randn / E to the router's logits
         # (tutel_moe_layer_nobatch.py:119-122).  gate_noise_draw: a [P, E] tensor to use as that draw (tests), else drawn per forward.
@@ -404,6 +410,19 @@ class SwitchNeRF:
         return ("l2h.w" in self.spec and "l1.w" in self.spec and self.M == 256 and self.H2 == 128 and self.dtype != torch.float32
                 and self.sw["fused_heads"] and self.L + 2 <= 12 and self.sw["fused_tail"])
 
+    def capacity(self, seg_tokens: int) -> int:
+        """Rows per (segment, expert) group of a routing segment of seg_tokens points (tutel_fast_dispatch.py:210-216, top-1):
+          cf > 0: int(cf * ceil(P / E)), the tokens past it are dropped;
+          cf < 0: the reference's min(max(loc) + 1, int(-cf * ceil(P / E))).  Every loc is at most max(loc), so a token is kept
+                  (loc < capacity) iff loc < int(-cf * ceil(P / E)): the same outputs as that static capacity (the cross-rank MAX of the
+                  reference only makes max(loc) + 1 larger; only its padded buffer's size differs) - used as is, expert parallelism
+                  included;
+          cf = 0: max(loc) + 1, every token kept: seg_tokens, a capacity no group exceeds (the training step then runs on the packed
+                  row space, one row per token - _net_forward_rows)."""
+        if self.cf == 0:
+            return int(seg_tokens)
+        return int(abs(self.cf) * ((int(seg_tokens) + self.E - 1) // self.E))      # tutel_fast_dispatch.py:211 / :216
+
     def set_expert_parallel(self, ep):
         """Shard the experts over the ranks of `ep` (parallel.ExpertParallel) and exchange the dispatched rows instead of
         computing every expert locally.  Ownership is sharded like the reference's (models/nerf_moe.py:139, 1037-1039: expert
@@ -413,6 +432,8 @@ class SwitchNeRF:
         their full size (3.7 M expert parameters); gather_expert_shards() refreshes every rank's copy from the owners before a
         checkpoint / evaluation without expert parallelism."""
         assert ep is None or ep.E == self.E
+        if ep is not None and self.cf == 0:
+            raise ValueError(DYNCAP_EP_ERROR)
         if ep is None and self.ep is not None:       # leaving expert parallelism: every rank needs every expert's trained weights
             self.gather_expert_shards()
         self.ep = ep
@@ -576,9 +597,14 @@ class SwitchNeRF:
         M, E, L, G, H2 = self.M, self.E, self.L, self.G, self.H2
         assert P % seg_tokens == 0, "points must be a multiple of the segment (model chunk) size"
         n_seg = P // seg_tokens
-        cap = int(self.cf * ((seg_tokens + E - 1) // E))     # tutel_fast_dispatch.py:211
+        cap = self.capacity(seg_tokens)     # tutel_fast_dispatch.py:210-216
         if no_batch:        # eval path (apply_on_expert_fn_nobatch): nothing is dropped == a capacity nothing exceeds
             cap = seg_tokens
+        # capacity_factor = 0 (the reference's dynamic capacity: nothing dropped) outside the no-batch forms: the packed row space, one row
+        # per token (the strided one would hold n_seg * E * seg_tokens rows - E times the saves, masks and perm)
+        dyn = self.cf == 0 and not no_batch
+        if dyn and self.ep is not None:
+            raise ValueError(DYNCAP_EP_ERROR)
         c = dict(N=N, S=S, P=P, n_seg=n_seg, cap=cap, seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
         c["pe"], c["pe_dir"] = pe, pe_dir
         # the per-ray half of layer "2" (gather + a 75 x 128 GEMM per ray: one small launch) only needs the direction encoding: on the side
@@ -627,7 +653,7 @@ class SwitchNeRF:
         if routing_override is not None:     # tests: inject the oracle's expert choice (near-tie robustness)
             c["idx"] = routing_override.to(dev).int().contiguous()
             c["gmax"] = c["gates"].gather(1, c["idx"].long()[:, None])[:, 0].contiguous()
-        packed = bool(no_batch) and not sv and self.ep is None      # (see below: the no-batch row layout of the inference forward)
+        packed = (bool(no_batch) and not sv and self.ep is None) or dyn      # (see below: the packed row layout)
         # expert chains (forward here, backward-data in backward_net - the pair shares its ReLU mask layout): the 256-row geometry
         # with phase-shifted row groups as a persistent launch (chain_big.hip, geometry 7 = geometry 4 walking a tile queue) for 256-feature
         # experts in a 16-bit compute dtype once a group holds at least one full tile.  The chain_geom switch picks another one (1: the
@@ -641,10 +667,20 @@ class SwitchNeRF:
         owner = ep_owner.eligible(self, c, no_batch, row_range)
         # (the fused tail's list of dropped tokens comes out of the routing launch)
         want_drops = (c["tail_fused"] or owner) and not packed
-        routed = o.route_top1(c["idx"], c["gmax"], c["gates"], seg_tokens, E, cap, self.bpr, want_perm=not packed, want_drops=want_drops)
-        c["loc"], c["counts"], c["perm"], c["tok2row"], c["l_aux"] = routed[:5]
-        if want_drops:
-            c["drop_begin"], c["dropped"] = routed[5], routed[6]
+        c["dyn"] = dyn
+        if dyn:     # the routing writes the packed row space itself (no strided perm, no pack pass); nothing is dropped
+            c["loc"], c["counts"], gb_dyn, c["perm"], c["tok2row"], c["l_aux"] = o.route_top1_packed(c["idx"], c["gmax"], c["gates"],
+                                                                                                   seg_tokens, E, self.bpr)
+            if c["tail_fused"]:      # the fused tail's (empty) list of dropped tokens: a zero count, never written
+                key = ("dyn_nodrops", n_seg * E)
+                if key not in self._bufs:
+                    self._bufs[key] = (torch.zeros(n_seg * E + 1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+                c["drop_begin"], c["dropped"] = self._bufs[key]
+        else:
+            routed = o.route_top1(c["idx"], c["gmax"], c["gates"], seg_tokens, E, cap, self.bpr, want_perm=not packed, want_drops=want_drops)
+            c["loc"], c["counts"], c["perm"], c["tok2row"], c["l_aux"] = routed[:5]
+            if want_drops:
+                c["drop_begin"], c["dropped"] = routed[5], routed[6]
         # ---- expert chain (gathers its rows through perm; ragged groups = (segment, expert))
         rows = n_seg * E * cap
         ng = n_seg * E
@@ -652,14 +688,24 @@ class SwitchNeRF:
         # rows contiguously per expert (expert_locations_begin, tutel_fast_dispatch_nobatch.py:24-36).  Same layout here for the
         # inference forward: P rows instead of n_seg * E * seg_tokens, groups addressed through their first row.
         group_begin = None
-        if packed:
+        if dyn:
+            rows = P
+            group_begin = c["group_begin"] = gb_dyn
+        elif packed:
             rows = P
             group_begin, c["perm"], c["tok2row"] = o.route_pack(c["idx"], c["loc"], c["counts"], seg_tokens, E)
             c["group_begin"] = group_begin
+        # packed ReLU-mask slots (swn_chain_desc.packed_rows) in the no-drop row space: the masks follow the P rows too (and the persistent
+        # launch walks P / 256 + groups tiles instead of groups * seg_tokens / 256; an inference forward on another geometry: no masks)
+        pk = P if (dyn and (sv or c["geom"] in (0, 1, 7))) else 0
+        c["packed_rows"] = pk
         c["rows"], c["ng"] = rows, ng
         c["counts_flat"] = c["counts"].view(-1)
         c["saves"] = [_b(f"save{l}", (rows, M), dt) if sv else None for l in range(L - 1)]
-        nw = max(o.chain_mask_words(dt, ng, cap, M), n_seg * o.chain_mask_words(dt, E, cap, M))    # (expert parallel: one launch per segment)
+        if pk:
+            nw = o.chain_mask_words_packed(dt, P, ng, M)
+        else:
+            nw = max(o.chain_mask_words(dt, ng, cap, M), n_seg * o.chain_mask_words(dt, E, cap, M))    # (expert parallel: one launch per segment)
         c["masks"] = [_b(f"mask{l}", (nw,), torch.int32) if sv else None for l in range(L - 1)]
         skips = set(self.cfg["skips"])
         layers = [o.Layer(self._local_experts(self.wf[f"exp{l}"]), self._local_experts(self.p[f"exp{l}.b"]),
@@ -714,14 +760,14 @@ class SwitchNeRF:
                         o.Layer(self.wf["l2h_pad"], None, relu=1, rowbias=c["c_ray"], rows_per_bias=S)]
                 o.mlp_chain(c["h0"], lys, c["h2"] if save else None, n_groups=ng, n_wsets=E, group_stride=cap, group_rows=c["counts_flat"],
                             group_rows_clamp=cap, x_gather=c["perm"].view(-1), tag=7, geometry=7, heads=heads, group_begin=group_begin,
-                            tail=(L, c["gmax"], c["drop_begin"], c["dropped"], H2))
+                            tail=(L, c["gmax"], c["drop_begin"], c["dropped"], H2), packed_rows=pk)
             with self._timed("expert_fwd"):
                 run_experts()
             if self.profile:      # bench.py: the launch again on this step's live buffers, its save-free form, and the expert layers ALONE
                 def expert_gemm():    # (the grouped GEMM without the tail: tag 1, into a scratch output - what round 1-3's figure measured)
                     o.mlp_chain(c["h0"], [o.Layer(ly.w, ly.b, relu=ly.relu, skip=ly.skip) for ly in layers], _b("eo_probe", (rows, M), dt),
                                 n_groups=ng, n_wsets=E, group_stride=cap, group_rows=c["counts_flat"], group_rows_clamp=cap,
-                                x_gather=c["perm"].view(-1), tag=1, geometry=7, group_begin=group_begin)
+                                x_gather=c["perm"].view(-1), tag=1, geometry=7, group_begin=group_begin, packed_rows=pk)
                 c["_relaunch"] = {"expert_fwd": run_experts, "expert_fwd_nosave": lambda: run_experts(False), "expert_gemm_nosave": expert_gemm}
             return c
         elif self.ep is None:
@@ -729,7 +775,8 @@ class SwitchNeRF:
 
             def run_experts(lys=layers):
                 o.mlp_chain(c["h0"], lys, c["eo"], n_groups=ng, n_wsets=E, group_stride=cap, group_rows=c["counts_flat"],
-                            group_rows_clamp=cap, x_gather=c["perm"].view(-1), tag=1, geometry=c["geom"], group_begin=group_begin)
+                            group_rows_clamp=cap, x_gather=c["perm"].view(-1), tag=1, geometry=c["geom"], group_begin=group_begin,
+                            packed_rows=pk)
             with self._timed("expert_fwd"):
                 run_experts()
             if self.profile:      # bench.py: the same launch again, back to back, on this step's live buffers (and its save-free form)
@@ -967,7 +1014,7 @@ class SwitchNeRF:
                             n_wsets=n_loc, group_stride=cap, group_rows=grp_rows, group_rows_clamp=cap, x_gather=perm,
                             y_add=dz[skip_l] if skip_l is not None else None, tag=8, geometry=7, x_features=H2,
                             combine=(c["y"], dsig, self.p["sigma.w"], c["gmax"], dgmax, dws_dst[0]), head=(2, c["drop_begin"], c["dropped"]),
-                            group_begin=c.get("group_begin"))
+                            group_begin=c.get("group_begin"), packed_rows=c.get("packed_rows", 0))
             with self._timed("expert_bwd"):
                 run_expert_bwd()
             if self.profile and "_relaunch" in c:
@@ -983,7 +1030,8 @@ class SwitchNeRF:
             def run_expert_bwd():
                 o.mlp_chain(dz_last, bl, dx, n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows,
                             group_rows_clamp=cap, x_gather=perm, y_add=dz[skip_l] if skip_l is not None else None, tag=2,
-                            geometry=c["geom"])
+                            geometry=c["geom"], group_begin=c.get("group_begin") if c.get("packed_rows") else None,
+                            packed_rows=c.get("packed_rows", 0))
             with self._timed("expert_bwd"):
                 run_expert_bwd()
             if self.profile and "_relaunch" in c:
@@ -1023,6 +1071,10 @@ class SwitchNeRF:
             if ep is not None:      # received rows are packed: groups through their first rows (any width: wgrad_multi cuts 512-feature
                 o.wgrad_multi(items, n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows, group_rows_clamp=cap, tag=1,
                               group_begin=c["ep_begin"])      # operands into 256-column GEMMs of the same launch)
+                return
+            if c.get("packed_rows"):      # the no-drop row space (capacity_factor = 0): the same balanced launch over the packed groups -
+                o.wgrad_multi(items, n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows, group_rows_clamp=cap, tag=1,
+                              group_begin=c["group_begin"])      # it cuts the valid rows into equal shares (no row-split heuristic)
                 return
             for i0 in range(0, L, 8):
                 o.wgrad_batched(items[i0:i0 + 8], n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows,

@@ -8,7 +8,7 @@
 Mirrors `moe_layer` / `MOELayer` of /root/reference/switch_nerf/modules/tutel_moe_ext/tutel_moe_layer_nobatch.py (ctor
 :443-460, forward :733-797, TopKGate.apply_on_expert_fn :98-235, ExpertMLP :836-924) for the configuration the reference's
 NeRFMoE builds (models/nerf_moe.py:278-292): top-k gate (k = 1 in every shipped config; k > 1: _MoETopKFunction) with fp32 router (optionally with gate noise in training), post-score dispatch (the gate value is applied on
-the way back), capacity `int(cf * ceil(P / E))` with optional batch-prioritised ranking, `expertmlp` experts with the
+the way back), capacity `int(cf * ceil(P / E))` (cf <= 0: the dynamic capacity max(loc) + 1, layer_capacity) with optional batch-prioritised ranking, `expertmlp` experts with the
 residual skip, one routing problem per call (the P tokens of the call), no expert parallelism (`parallel.ExpertParallel`
 covers that inside SwitchNeRF).  Parameter names equal the reference's (`gates.0.wg.weight`, `experts.0.weights.{l}`
 [E, in, out], `experts.0.bias.{l}` [E, 1, out]) so its state_dict loads unchanged.
@@ -25,6 +25,28 @@ import torch
 from torch import nn
 
 from . import ops
+
+
+def layer_capacity(capacity_factor: float, n_tokens: int, n_experts: int, top_k: int = 1, max_rows: Optional[int] = None) -> int:
+    """The layer's capacity (tutel_fast_dispatch.py:210-216): cf > 0: k * int(cf * ceil(P / E)); cf <= 0: max_rows = max(loc) + 1 over
+    all choices (the most rows any expert receives; the caller MAX-reduces it over the layer's group), for cf < 0 clamped at
+    k * int(-cf * ceil(P / E))."""
+    static = top_k * int(abs(capacity_factor) * ((n_tokens + n_experts - 1) // n_experts))
+    if capacity_factor > 0:
+        return static
+    if max_rows is None:
+        raise ValueError("capacity_factor <= 0: the dynamic capacity needs max_rows (max(loc) + 1)")
+    return int(max_rows) if capacity_factor == 0 else min(int(max_rows), static)
+
+
+def _dynamic_capacity(layer, idx, P: int, E: int, K: int) -> int:
+    """capacity_factor <= 0: max(loc) + 1 over the choices idx (the rows the busiest expert receives = its count), MAX-all-reduced over
+    layer.group when one is given, read on the host like the reference's int(...), then layer_capacity's clamp."""
+    m = torch.bincount(idx.reshape(-1).long(), minlength=E).max().to(torch.int32)
+    if layer.group is not None:
+        import torch.distributed as dist
+        dist.all_reduce(m, op=dist.ReduceOp.MAX, group=layer.group)
+    return layer_capacity(layer.capacity_factor, P, E, K, int(m.item()))
 
 
 class _ExpertParams(nn.Module):
@@ -60,7 +82,10 @@ class _MoEFunction(torch.autograd.Function):
         wg32 = wg.detach().float().contiguous()
         # gate_noise: the [P, E] draw of a training forward under gate_noise > 0 (tutel_moe_layer_nobatch.py:119-122) or None
         gates, idx, gmax, stats = o.gate_fwd(gs, None, None, wg32, noise=gate_noise, noise_scale=layer._noise_scale if gate_noise is not None else 0.0)
-        cap = int(layer.capacity_factor * ((P + E - 1) // E))                                  # tutel_fast_dispatch.py:211
+        if layer.capacity_factor > 0:
+            cap = int(layer.capacity_factor * ((P + E - 1) // E))                              # tutel_fast_dispatch.py:211
+        else:
+            cap = _dynamic_capacity(layer, idx, P, E, 1)                                       # :212-216
         if layer.moe_no_batch:
             cap = P
         loc, counts, perm, tok2row, l_aux = o.route_top1(idx, gmax, gates, P, E, cap, layer.bpr)
@@ -146,10 +171,13 @@ class _MoETopKFunction(torch.autograd.Function):
         wg32 = wg.detach().float().contiguous()
         nscale = layer._noise_scale if gate_noise is not None else 0.0
         gates, _idx0, gmax, stats = o.gate_fwd(gs, None, None, wg32, noise=gate_noise, noise_scale=nscale)
-        cap = K * int(layer.capacity_factor * ((P + E - 1) // E))                              # tutel_fast_dispatch.py:211
+        idx, _gsel, gn = o.topk_select(gates, K)                                               # :177-182, 204-206
+        if layer.capacity_factor > 0:
+            cap = K * int(layer.capacity_factor * ((P + E - 1) // E))                          # tutel_fast_dispatch.py:211
+        else:
+            cap = _dynamic_capacity(layer, idx, P, E, K)                                       # :212-216 (max over every choice's loc)
         if layer.moe_no_batch:
             cap = P                                                                            # (k distinct experts per token: <= P rows each)
-        idx, _gsel, gn = o.topk_select(gates, K)                                               # :177-182, 204-206
         loc, counts, perm, _, group_rows, l_aux = o.route_topk(idx, gmax, gates, P, E, cap, layer.bpr)
         l_bal = l_aux.reshape(()) if layer.use_load_importance_loss else torch.zeros((), device=xs.device)    # (second output: extras only)
         li = ()
@@ -284,6 +312,7 @@ class MoELayer(nn.Module):
             # load-importance branch); refuse at construction instead
             raise ValueError("compute_balance_loss needs use_load_importance_loss (tutel_moe_layer_nobatch.py:128-135, 231-232)")
         self.moe_no_batch, self.return_gates, self.dtype = bool(moe_no_batch), bool(return_gates), dtype
+        self.group = group        # capacity_factor <= 0: the dynamic capacity is MAX-reduced over this process group (None: no reduction)
         gen = None
         if seeds is not None:                      # gate under seeds[0], experts under seeds[1] (tutel_moe_layer_nobatch.py:654-703)
             gen = torch.Generator().manual_seed(int(seeds[1]))

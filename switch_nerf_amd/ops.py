@@ -342,6 +342,29 @@ def route_top1(idx, gmax, gates, seg_tokens: int, n_experts: int, capacity: int,
     return loc, counts, perm, tok2row, l_aux
 
 
+def route_top1_packed(idx, gmax, gates, seg_tokens: int, n_experts: int, bpr: bool):
+    """Top-1 routing without dropping, straight into the packed row space (swn_route_top1_packed: capacity_factor = 0 in training)
+    -> (loc, counts, begin [n_seg * E], perm [P] row -> token, tok2row [P], l_aux).  loc / counts / l_aux equal route_top1's bit for
+    bit; begin / perm / tok2row equal route_pack's of that routing."""
+    P = idx.shape[0]
+    n_seg = P // seg_tokens
+    dev = idx.device
+    loc = torch.empty(P, dtype=torch.int32, device=dev)
+    counts = torch.empty(n_seg, n_experts, dtype=torch.int32, device=dev)
+    begin = torch.empty(n_seg * n_experts, dtype=torch.int32, device=dev)
+    perm = torch.empty(P, dtype=torch.int32, device=dev)
+    tok2row = torch.empty(P, dtype=torch.int32, device=dev)
+    l_aux = torch.empty(n_seg, dtype=torch.float32, device=dev) if gates is not None else None
+    nbytes = _lib.load().swn_route_workspace_bytes(P, n_seg, n_experts)
+    key = (dev, nbytes)
+    ws = _route_ws.get(key)
+    if ws is None:      # (kept for good, like route_top1's)
+        ws = _route_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("swn_route_top1_packed", _p(idx), _p(gmax), _p(gates), P, int(seg_tokens), int(n_experts), int(bool(bpr)), _p(loc), _p(counts),
+         _p(begin), _p(perm), _p(tok2row), _p(l_aux), _p(ws), nbytes, _stream())
+    return loc, counts, begin, perm, tok2row, l_aux
+
+
 def route_dropped(idx, loc, counts, seg_tokens: int, n_experts: int, capacity: int):
     """-> (drop_begin int32 [n_groups + 1], dropped int32 [P]): the tokens no expert kept, per (segment, expert) in location order;
     drop_begin[-1] = their number (a device scalar: nothing is read on the host).  Input of the fused tail (mlp_chain(tail=...))."""
@@ -761,9 +784,18 @@ def chain_mask_words(dtype, n_groups: int, group_stride: int, max_width: int = 2
     return int(_lib.load().swn_chain_mask_words(_code(dtype), int(n_groups), int(group_stride), int(max_width)))
 
 
+def chain_mask_words_packed(dtype, rows: int, n_groups: int, max_width: int = 256) -> int:
+    """uint32 words per layer mask buffer of a chain with packed mask slots (mlp_chain(packed_rows=rows)): at most `rows` packed rows
+    in n_groups groups - ceil(rows / tile rows) + n_groups tiles instead of n_groups * ceil(group_stride / tile rows)."""
+    w = C.c_int64(0)
+    call("swn_chain_mask_words_packed", _code(dtype), int(rows), int(n_groups), int(max_width), C.byref(w))
+    return int(w.value)
+
+
 def mlp_chain(x, layers: Sequence[Layer], y, n_groups=1, n_wsets=1, group_stride=None, group_rows=None,
               group_rows_clamp=None, x_gather=None, x_save=None, y_add=None, y_add_gather=None, tag=0, x_scale=None,
-              x_relu=False, geometry=0, group_begin=None, combine=None, heads=None, sched=None, x_features=0, tail=None, head=None):
+              x_relu=False, geometry=0, group_begin=None, combine=None, heads=None, sched=None, x_features=0, tail=None, head=None,
+              packed_rows=0):
     """geometry: 0 / 1 the 64-row tile kernels, 2 - 5 the chain_big.hip geometries (include/swn.h).  group_begin: first row of every
     group (packed / no-batch layout) instead of g * group_stride.  combine = (y_fwd, dsig, wsig, gate, dgate_out): the combine backward
     (ops.combine_bwd) fused into the write-out of the last layer.  heads = (w_sigma, b_sigma, w_color, b_color, sigma_noise or None, raw):
@@ -773,8 +805,11 @@ def mlp_chain(x, layers: Sequence[Layer], y, n_groups=1, n_wsets=1, group_stride
     tail_first: geometry 7, tag 7) - layers[tail_first:] are shared layers, the saves from layer tail_first - 1 on, y and the heads'
     raw are in token order (P rows), x_gather maps rows to tokens.
     head = (head_layers, drop_begin, dropped): the mirror image for the backward pass (include/swn.h, head_layers: geometry 7, tag 8) -
-    x = dh2 in token order, layers[:head_layers] shared, `combine` (token order) applied behind them, the expert backward layers after."""
+    x = dh2 in token order, layers[:head_layers] shared, `combine` (token order) applied behind them, the expert backward layers after.
+    packed_rows > 0: packed ReLU-mask slots (include/swn.h swn_chain_desc.packed_rows; group_begin required, geometry 0 / 1 / 7): the
+    masks of a row space of at most packed_rows rows, sized by chain_mask_words_packed - the forward and backward chains set it alike."""
     d = ChainDesc()
+    d.packed_rows = int(packed_rows)
     d.dtype = _dt(x)
     d.tag = int(tag)
     d.geometry = int(geometry)
@@ -815,7 +850,10 @@ def mlp_chain(x, layers: Sequence[Layer], y, n_groups=1, n_wsets=1, group_stride
         if len(combine) > 5 and combine[5] is not None:      # the sigma head's weight gradient += from the same pass (fused backward only)
             dws = combine[5]
             assert head is not None and dws.dtype == torch.float32 and dws.numel() == 256 and dws.is_contiguous()
-            nb = int(_lib.load().swn_chain_dwsig_workspace_bytes(int(n_groups), int(d.group_rows_clamp)))
+            if packed_rows > 0:      # (packed slots: ceil(packed_rows / 256) + n_groups tiles = one group of packed_rows + 256 n_groups rows)
+                nb = int(_lib.load().swn_chain_dwsig_workspace_bytes(1, int(packed_rows) + 256 * int(n_groups)))
+            else:
+                nb = int(_lib.load().swn_chain_dwsig_workspace_bytes(int(n_groups), int(d.group_rows_clamp)))
             ws = _dwsig_ws.get((x.device, nb))
             if ws is None:           # per-wave partial sums (zeroed and added up in a fixed order by the launch); never freed (graphs)
                 ws = _dwsig_ws[(x.device, nb)] = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
