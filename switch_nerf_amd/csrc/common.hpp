@@ -35,6 +35,7 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 hwf16x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 swn_mfma16_t __attribute__((ext_vector_type(8)));
 #define SWN_MFMA_32x32x16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(swn_mfma16_t, a), __builtin_bit_cast(swn_mfma16_t, b), c, 0, 0, 0)
+#define SWN_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(swn_mfma16_t, a), __builtin_bit_cast(swn_mfma16_t, b), c, 0, 0, 0)
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {      // round to nearest even (v_cvt_f16_f32 x 2 + pack)
   const hwf16x2_t v = {(_Float16)lo, (_Float16)hi};
@@ -46,6 +47,7 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {      // ro
 typedef __bf16 hwbf16x2_t __attribute__((ext_vector_type(2)));
 typedef short swn_mfma16_t __attribute__((ext_vector_type(8)));
 #define SWN_MFMA_32x32x16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(swn_mfma16_t, a), __builtin_bit_cast(swn_mfma16_t, b), c, 0, 0, 0)
+#define SWN_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(swn_mfma16_t, a), __builtin_bit_cast(swn_mfma16_t, b), c, 0, 0, 0)
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // round-to-nearest-even conversions: gfx950 has a packed hardware convert (v_cvt_pk_bf16_f32); going through the
 // __bf16 vector type lets hipcc emit it (one VALU op per two values instead of ~10 of integer rounding code).

@@ -4,9 +4,9 @@
 // /root/reference/switch_nerf/modules/tutel_moe_ext/tutel_moe_layer_nobatch.py:908) and of F.linear (Mlp,
 // models/nerf_moe.py:34).  The reduction runs over ROWS (tokens), which is the slow dimension of both row-major
 // operands, while the bf16 MFMA wants 8 consecutive k per lane.  Operand slabs [32 rows][<=256 cols] are staged
-// in LDS row-major; a lane reads an 8-byte (A) / 4-byte (B) piece of 8 rows and interleaves row pairs in registers,
-// which yields 4 (A) / 2 (B) fragments whose MFMA row/col labels are a fixed permutation of the real columns.
-// The bias gradient is one extra MFMA per step with an all-ones A fragment (no extra LDS traffic).
+// in LDS; the stream kernel's default 16-bit step reads them with the transposing LDS read into 16x16x32 fragments (see
+// WS_TR below); the row-split kernel (and -DSWN_WG_MFMA32) reads an 8-byte (A) / 4-byte (B) piece of 8 rows and interleaves
+// row pairs in registers, which yields 32x32x16 fragments whose MFMA row/col labels are a fixed permutation of the real columns.
 // The roofline of this kernel is HBM: each operand row is read exactly once ((m+n) elements per 2*m*n flops).
 //
 // Workgroup = 512 threads = 8 waves as 2 (m) x 4 (n); wave tile 128 x 64; full 256 x 256 dW tile per workgroup;
@@ -364,6 +364,24 @@ __device__ __forceinline__ int ws_first_slab(long x, long base, int w, int T) {
 }
 __device__ __forceinline__ long ws_cut(int k, long total, int n_wg) { return ((long)k * total) / n_wg; }
 
+// 16-bit operands (default build): 16x16x32 MFMAs on fragments read with ds_read_b64_tr_b16 - the lanes of a 16-lane group address a
+// [4 rows][16 columns] block, 8 bytes each, and each receives one column's 4 rows, i.e. 4 consecutive tokens of one feature, which is
+// what the MFMA wants - so the fragments need no VALU work.  -DSWN_WG_MFMA32: the previous 32x32x16 step on fragments put together
+// with v_perm_b32 from row-major dwords (A/B builds, SWN_VARIANT).
+#ifdef SWN_WG_MFMA32
+constexpr bool WS_TR = false;
+#else
+constexpr bool WS_TR = true;
+#endif
+// LDS image of a 16-bit slab (32 rows of 512 B): 16-byte chunk c of row r sits at chunk wg_chunk(r, c) of that row.  A transposed read
+// of one 32-lane half covers rows {8 g + 4 h + q : g = 0, 1; q = 0..3} (h fixed), 32 bytes (2 chunks) each: the XOR spreads those 8
+// rows over the 8 distinct 32-byte bank groups of the 256-byte bank row (unswizzled, all rows of a block sit on the same banks).  The
+// map is its own inverse: the fill uses it to pick the source chunk of the lane-linear LDS-DMA destination chunk.
+__device__ __forceinline__ int wg_chunk(int r, int c) { return c ^ (((r & 3) << 1) | (r & 8)); }
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef short ws_s4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) ws_s4_t* ws_lds_s4_t;
+
 template <typename T, int TAG>
 __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -461,6 +479,19 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   auto sa = [&](int b_) -> char* { return smem + b_ * 2 * SLAB; };
   auto sb = [&](int b_) -> char* { return smem + b_ * 2 * SLAB + SLAB; };
+  // TR: byte offsets in the slab of this lane's transposed reads, tokens 8 g .. 8 g + 3 (the reads of tokens 8 g + 4 .. + 7 are 4 rows =
+  // 2048 bytes further: the swizzle does not look at row bit 2).  Lane 4 q + p of group g addresses row 8 g + q, columns 4 p .. 4 p + 3
+  // of the fragment's 16: A fragment qa = columns wm * 128 + 16 qa .., B fragment qq = columns wn * 64 + 16 qq ..
+  constexpr bool TR = sizeof(T) == 2 && WS_TR;
+  uint32_t tra[8], trb[4];
+  {
+    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    const int r = 8 * g + q;
+#pragma unroll
+    for (int qa = 0; qa < 8; ++qa) tra[qa] = r * 512 + 16 * wg_chunk(r, 16 * wm + 2 * qa + (p >> 1)) + 8 * (p & 1);
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) trb[qq] = SLAB + r * 512 + 16 * wg_chunk(r, 8 * wn + 2 * qq + (p >> 1)) + 8 * (p & 1);
+  }
 
   for (int pi = 0; pi < n_pieces; ++pi) {
     {
@@ -468,7 +499,6 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
       const int pa = __builtin_amdgcn_readfirstlane(plist[3 + 4 * pi]), pb = __builtin_amdgcn_readfirstlane(plist[4 + 4 * pi]);
       const WsJob& it = p.job[j];
       const int m_dim = it.m_dim, n_dim = it.n_dim;
-      const int a_colb = pcol < m_dim * (int)sizeof(T) ? pcol : 0, b_colb = pcol < n_dim * (int)sizeof(T) ? pcol : 0;
       const bool active = (wm * 128 < m_dim) && (wn * 64 < n_dim);
       const bool do_bias = (it.db != nullptr) && wm == 0 && (wn * 64 < n_dim);
       // a column block of a wider operand pair: the block of A is read again by the job of the next column block of B, and the other way round
@@ -476,7 +506,13 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
       // ---------------------------------------------------------------- one piece: slabs [pa, pb) of (job j, weight set e)
       f32x16_t acc[4][2];
       f32x16_t accb[2];
-      float dbv[2] = {0.f, 0.f};                 // 16-bit operands: this lane's share of the bias gradient (its two columns, its 8 rows per step)
+      f32x4_t acc16[8][4];                       // TR: [16 m][16 n] tiles of the 128 x 64 wave tile
+      float dbv[2] = {0.f, 0.f};                 // 16-bit operands: this lane's share of the bias gradient (TR: a running sum of column
+                                                 // wn * 64 + 16 (f + 2 (lane >> 5)) + (lane & 15); else: its two columns, its 8 rows per step)
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) acc16[i][jj] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -509,8 +545,14 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
       // The loop prepares BEFORE it waits for the current slab and the barrier, so the copies go out right behind the barrier
       // (the address arithmetic used to sit between the barrier and the copies: ~300 instructions per slab on every wave).
       int gp = (ip % segs) * n_wsets + e;                  // group of the cursor (ordered group ip + 1 = group gp + n_wsets)
-      const char* a_lane = (const char*)it.a + a_colb;
-      const char* b_lane = (const char*)it.b + b_colb;
+      const char* a_lane[2];                               // this lane's source column in piece i of the wave: with TR the chunk of
+      const char* b_lane[2];                               // the swizzled image that lands in its destination (past the operand's
+#pragma unroll                                             // width: column 0, never used)
+      for (int i = 0; i < 2; ++i) {
+        const int cb = TR ? 16 * wg_chunk((2 * wave + i) * RPP + prow, lane % LPR) : pcol;
+        a_lane[i] = (const char*)it.a + (cb < m_dim * (int)sizeof(T) ? cb : 0);
+        b_lane[i] = (const char*)it.b + (cb < n_dim * (int)sizeof(T) ? cb : 0);
+      }
       const uint32_t a_rb = (uint32_t)it.lda * (uint32_t)sizeof(T), b_rb = (uint32_t)it.ldb * (uint32_t)sizeof(T);
       typedef const __attribute__((address_space(4))) int32_t* cidx_t;
       const cidx_t ag = (cidx_t)it.a_gather, bg = (cidx_t)it.b_gather;
@@ -551,8 +593,8 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
           const long b0 = bg ? (long)max(ib0[i], 0) : rr0[i], b1 = bg ? (long)max(ib1[i], 0) : rr1[i];
           const bool ok = live && (rf + prow < rows_p);
           const uint32_t as = (uint32_t)((RPP == 2 && prow) ? a1 : a0), bs = (uint32_t)((RPP == 2 && prow) ? b1 : b0);
-          src[2 * i] = ok ? a_lane + (uint64_t)as * a_rb : zero;
-          src[2 * i + 1] = ok ? b_lane + (uint64_t)bs * b_rb : zero;
+          src[2 * i] = ok ? a_lane[i] + (uint64_t)as * a_rb : zero;
+          src[2 * i + 1] = ok ? b_lane[i] + (uint64_t)bs * b_rb : zero;
         }
         if (live) {                                        // advance (wave-uniform)
           --left;
@@ -584,6 +626,10 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
       for (int n = 0; n < nsl; ++n) {
         prepare();
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        // TR: the gather indices fetch() just asked for have landed (the copies' wait above covers their latency).  With a scalar load
+        // in flight hipcc cannot count the LDS reads below (scalar loads complete out of order) and waits for all 24 in front of the
+        // first MFMA; this compiler-visible lgkmcnt(0) (vmcnt, expcnt: no wait) lets it wait per fragment.
+        if constexpr (TR) __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_s_barrier();
         issue((slot + WG_NS - 1) % WG_NS);
         const char* A = sa(slot);
@@ -593,7 +639,55 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
 #else
         if (active || do_bias) {
 #endif
-          if constexpr (sizeof(T) == 2) {
+          if constexpr (TR) {
+            // One slab = one K step of 16x16x32 (32 tokens).  The 24 transposed reads (two per fragment: tokens 8 g .. + 3 and 8 g + 4 ..
+            // + 7) go out at once, B first; the LDS returns them in order, so the MFMAs of A fragment qa need only its own reads and
+            // the later reads overlap the earlier products.  No VALU work on the fragments (the 32x32x16 step spent 48 v_perm_b32 per
+            // slab and wave putting them together).
+            const char* S = smem + slot * 2 * SLAB;
+            ws_s4_t rd[12][2];
+            auto tr = [&](uint32_t off) -> ws_s4_t { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((ws_lds_s4_t)(S + off)); };
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) { rd[8 + qq][0] = tr(trb[qq]); rd[8 + qq][1] = tr(trb[qq] + 4 * 512); }
+#pragma unroll
+            for (int qa = 0; qa < 8; ++qa) { rd[qa][0] = tr(tra[qa]); rd[qa][1] = tr(tra[qa] + 4 * 512); }
+            auto fr = [&](int i) -> bf16x8_t { return __builtin_shufflevector(rd[i][0], rd[i][1], 0, 1, 2, 3, 4, 5, 6, 7); };
+            if (active) {
+#pragma unroll
+              for (int qa = 0; qa < 8; ++qa)
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) acc16[qa][qq] = SWN_MFMA_16x16x32(fr(qa), fr(8 + qq), acc16[qa][qq]);
+              // db = the column sums of the B slab in VALU (not a matrix instruction against a fragment of ones: the launch is bound by
+              // the chip's power budget, profiles/r04_experiments.md 10, and an MFMA costs what hundreds of additions do), one fp32
+              // addition per element in the order of the 32x32x16 step, so that db keeps its bits: per column two running sums, rows
+              // 0-7 then 16-23 of every slab and rows 8-15 then 24-31, added at the end.  One v_permlane32_swap per dword gives lanes
+              // 0-31 the rows 16-31 of B fragments 0, 1 and lanes 32-63 the rows 0-15 of fragments 2, 3: lane group g then runs sum
+              // (g & 1) of fragment f + 2 (g >> 1) in slot f.
+              if (do_bias) {
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                  const u32x4_t x = __builtin_bit_cast(u32x4_t, fr(8 + f)), y = __builtin_bit_cast(u32x4_t, fr(10 + f));
+                  uint32_t lo[4], hi[4];
+#pragma unroll
+                  for (int t = 0; t < 4; ++t) {
+                    const auto r = __builtin_amdgcn_permlane32_swap(x[t], y[t], false, false);
+                    lo[t] = r[0];      // rows 8 (g & 1) + 2 t, + 1 of the slab
+                    hi[t] = r[1];      // rows 16 + 8 (g & 1) + 2 t, + 1
+                  }
+#pragma unroll
+                  for (int t = 0; t < 4; ++t) {
+                    dbv[f] += bf16_to_f32((bf16_t)(lo[t] & 0xFFFFu));
+                    dbv[f] += bf16_to_f32((bf16_t)(lo[t] >> 16));
+                  }
+#pragma unroll
+                  for (int t = 0; t < 4; ++t) {
+                    dbv[f] += bf16_to_f32((bf16_t)(hi[t] & 0xFFFFu));
+                    dbv[f] += bf16_to_f32((bf16_t)(hi[t] >> 16));
+                  }
+                }
+              }
+            }
+          } else if constexpr (sizeof(T) == 2) {
             // One slab = two K steps of 16 rows.  The 32 LDS reads of BOTH steps go out first (one round trip per slab), an operand
             // fragment (8 consecutive rows of one column) is put together from the row-major dwords with one v_perm_b32 per dword, and
             // the permutes of step 1 sit BETWEEN the matrix instructions of step 0: the workgroup's eight waves leave the slab's barrier
@@ -710,7 +804,17 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
 
       // ---- the piece's partial tile: slot k + pair (unique: both the cut and the pair index grow along the line) ----
       float* part = tiles + (size_t)(k + j * n_wsets + e) * WS_TILE;
-      if (active) {
+      if (TR && active) {         // 16x16x32 C map: row 4 (lane >> 4) + r, column lane & 15
+#pragma unroll
+        for (int qa = 0; qa < 8; ++qa)
+#pragma unroll
+          for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int m = wm * 128 + 16 * qa + 4 * (lane >> 4) + r, n = wn * 64 + 16 * qq + (lane & 15);
+              if (m < m_dim && n < n_dim) part[(size_t)m * n_dim + n] = acc16[qa][qq][r];
+            }
+      } else if (active) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -729,13 +833,25 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
               if (m < m_dim && n < n_dim) part[(size_t)m * n_dim + n] = acc[q][qq][r];
             }
       }
-      if constexpr (sizeof(T) == 2) {          // the two half-waves hold the two halves of every K step's rows
+      if constexpr (TR) {                      // lane groups 0 / 2 add the second running sum (groups 1 / 3) to their first
+        if (do_bias) {
+#pragma unroll
+          for (int f = 0; f < 2; ++f) dbv[f] += __shfl_xor(dbv[f], 16);
+          if ((lane & 16) == 0) {
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+              const int n = wn * 64 + 16 * (f + 2 * (lane >> 5)) + (lane & 15);
+              if (n < n_dim) part[(size_t)m_dim * n_dim + n] = dbv[f];
+            }
+          }
+        }
+      } else if constexpr (sizeof(T) == 2) {   // the two half-waves hold the two halves of every K step's rows
         if (do_bias) {
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq) dbv[qq] += __shfl_xor(dbv[qq], 32);
         }
       }
-      if (do_bias && lhi == 0) {
+      if (!TR && do_bias && lhi == 0) {
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) {
           int n;
