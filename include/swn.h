@@ -274,6 +274,34 @@ int swn_composite_fwd(const float* raw, const float* z, float last_delta, float 
 int swn_composite_bwd(const float* raw, const float* z, float last_delta, float rgb_padding, const float* d_rgb,
                       int n_rays, int n_samples, float* d_raw, void* stream);
 
+/* ---- per-sample point outputs and the point-cloud export (csrc/points.hip; off the training step) ------------------
+ * swn_point_fields: replaces the return_pts / return_alpha / return_pts_alpha results of _inference (rendering.py:299,
+ *   :443-452).  One pass of n_rays rays: z[N,T] / raw[N*T,4] the depths and outputs it composites (merged order with `order`),
+ *   last_delta the delta of its last sample (scalar, or last_delta_ray [N] when not NULL).
+ *   pts[N,n_pts,3] = rays_o + rays_d * z_pts (the pass's own unmerged depths [N,n_pts]; NULL = z), without FMA contraction;
+ *   alpha[N,T] = 1 - exp(-delta * sigma), the compositing kernel's delta and expression;
+ *   pts_alpha[N,n_pts]: with order [N,T] (swn_merge_samples: the first n_pts sources are this pass's samples)
+ *   pts_alpha[ray, order[t]] = alpha[t] for order[t] < n_pts; without order, alpha itself (n_pts == T).  Outputs may be NULL.
+ * swn_points_pack: replaces the per-point Python tuples of Runner._run_validation_points (runner.py:2024-2142): PLY vertex
+ *   bodies of the kept samples [:, :, ::skip] (ray-major, sample-minor), quantised as (x * 255).to(torch.uint8):
+ *     SWN_PLY_RGBA:      x y z f4 + red green blue alpha u1 (16 bytes): rgb[R,S,rgb_stride] (3: pts_rgb, 4: raw), alpha[R,S];
+ *     SWN_PLY_SEG_ALPHA: x y z f4 + palette[idx] rgb + alpha u1 (16 bytes; :2080-2110);
+ *     SWN_PLY_SEG_RGB:   x y z f4 + palette[idx] rgb u1 (15 bytes), the last kept sample of each ray in pixel_rgb[R,3] (:2119-2142).
+ *   palette[E,3] u8 (voc_palette()[1:], utils/functions.py:299); idx[R*S] i32 expert of each sample (NULL: no partition).
+ *   out_all[R*ceil(S/skip)] records (may be NULL); out_experts (NULL: none) the same records partitioned stably by idx - expert 0's,
+ *   then expert 1's, ... (the boolean masks of :2064) - and counts[E] the records of each expert.  Deterministic (no global
+ *   atomics): per-block counts, a scan, a ballot-ranked scatter; with out_experts the workspace holds the block counts:
+ *   workspace_bytes >= 4 E ceil(n_rays ceil(n_samples / skip) / 2048).  E <= 64.                                    */
+#define SWN_PLY_RGBA 0
+#define SWN_PLY_SEG_ALPHA 1
+#define SWN_PLY_SEG_RGB 2
+int swn_point_fields(const float* rays, const float* z_pts, int n_pts, const float* z, const float* raw, int n_rays, int n_samples,
+                     float last_delta, const float* last_delta_ray, const int32_t* order, float* pts, float* alpha,
+                     float* pts_alpha, void* stream);
+int swn_points_pack(const float* pts, const float* rgb, int rgb_stride, const float* alpha, const int32_t* idx,
+                    const float* pixel_rgb, const uint8_t* palette, int n_rays, int n_samples, int skip, int n_experts, int mode,
+                    void* out_all, void* out_experts, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- mip path (rendering_mip.py, MipNeRFMoE) -------------------------------------------------------------------
  * swn_sample_z: the n_samples interval edges of a level, z = near (1 - t) + far t with the stratified perturbation of
  *   rendering.py:573-584 (perturb_rand [N,S] U[0,1) supplied by the caller, NULL / perturb = 0: none).

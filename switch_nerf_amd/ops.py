@@ -711,6 +711,64 @@ def composite_bounded_fwd(raw, z, last_delta=None, flip=False, depth_real=None, 
     return rgb, depth, dvar, w, lam
 
 
+PLY_RGBA, PLY_SEG_ALPHA, PLY_SEG_RGB = 0, 1, 2        # swn_points_pack modes (include/swn.h)
+PLY_RECORD_BYTES = {PLY_RGBA: 16, PLY_SEG_ALPHA: 16, PLY_SEG_RGB: 15}
+
+
+def point_fields(rays, z, raw, last_delta=1e10, z_pts=None, order=None, want_pts=True, want_alpha=True, want_pts_alpha=True):
+    """Per-sample point outputs of one pass (rendering.py:299, :443-452): z [N,T] / raw [N*T,4] the depths and outputs it
+    composites (merged order when `order` [N,T] is given), last_delta a float or a per-ray [N] tensor, z_pts [N,n] the pass's own
+    unmerged depths (None = z).  -> pts [N,n,3], alpha [N,T], pts_alpha [N,n] (None where not wanted)."""
+    N, T = z.shape
+    zp = z if z_pts is None else z_pts
+    n = zp.shape[1]
+    dev = z.device
+    pts = torch.empty(N, n, 3, dtype=torch.float32, device=dev) if want_pts else None
+    alpha = torch.empty(N, T, dtype=torch.float32, device=dev) if want_alpha else None
+    pa = torch.empty(N, n, dtype=torch.float32, device=dev) if want_pts_alpha else None
+    ld_ray = last_delta.contiguous() if torch.is_tensor(last_delta) else None
+    ld = 1e10 if ld_ray is not None else float(last_delta)
+    call("swn_point_fields", _p(rays), _p(zp), n, _p(z), _p(raw), N, T, ld, _p(ld_ray), _p(order), _p(pts), _p(alpha), _p(pa),
+         _stream())
+    return pts, alpha, pa
+
+
+def _rgb_arg(rgb, R, S):
+    """pts_rgb [R,S,3]: contiguous (stride 3) or the raw[:, :3] view of a contiguous raw [R*S,4] (stride 4); anything else is
+    copied.  -> (tensor to keep alive until the launch, pointer, sample stride)."""
+    assert rgb.is_cuda and rgb.dtype == torch.float32 and tuple(rgb.shape) == (R, S, 3)
+    for cs in (3, 4):
+        if rgb.stride() == (S * cs, cs, 1):
+            return rgb, C.c_void_p(rgb.data_ptr()), cs
+    rgb = rgb.contiguous()
+    return rgb, C.c_void_p(rgb.data_ptr()), 3
+
+
+def points_pack(pts, pts_alpha, mode, skip=1, idx=None, n_experts=1, pts_rgb=None, pixel_rgb=None, palette=None, want_all=True,
+                want_experts=True):
+    """PLY vertex bodies of the kept samples [:, :, ::skip] on the device (swn_points_pack): -> (all [K * rec] uint8 or None,
+    experts [K * rec] uint8 - expert 0's records, then expert 1's, ... - or None, counts [E] int32 or None), K = R * ceil(S / skip)."""
+    R, S = pts.shape[0], pts.shape[1]
+    dev = pts.device
+    rec = PLY_RECORD_BYTES[mode]
+    K = R * ((S + skip - 1) // skip)
+    part = want_experts and idx is not None
+    out_all = torch.empty(K * rec, dtype=torch.uint8, device=dev) if want_all else None
+    out_exp = torch.empty(K * rec, dtype=torch.uint8, device=dev) if part else None
+    counts = torch.zeros(n_experts, dtype=torch.int32, device=dev) if part else None
+    ws_bytes = 4 * n_experts * ((K + 2047) // 2048) if part else 0        # the block counts (include/swn.h)
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev) if part else None
+    _rgb, rgb_p, rgb_stride = _rgb_arg(pts_rgb, R, S) if pts_rgb is not None else (None, None, 3)
+    if idx is not None:
+        idx = idx.reshape(-1)
+        idx = idx if idx.dtype == torch.int32 else idx.to(torch.int32)
+        assert idx.numel() == R * S
+    call("swn_points_pack", _p(pts.contiguous()), rgb_p, rgb_stride, _p(None if pts_alpha is None else pts_alpha.contiguous()),
+         _p(None if idx is None else idx.contiguous()), _p(None if pixel_rgb is None else pixel_rgb.contiguous()), _p(palette), R, S,
+         int(skip), int(n_experts), int(mode), _p(out_all), _p(out_exp), _p(counts), _p(ws), ws_bytes, _stream())
+    return out_all, out_exp, counts
+
+
 def composite_bounded_bwd(raw, z, d_rgb, last_delta=None, flip=False, d_bg_lambda=None):
     N, S = z.shape
     d_raw = torch.empty(N * S, 4, dtype=torch.float32, device=z.device)

@@ -10,12 +10,44 @@ Result keys follow the reference: rgb_coarse, depth_coarse, depth_variance_coars
 ([chunks * moe layers], rendering.py:388-390), moe_gates_coarse [N, S, 1, 1], sigma_coarse (hparams.return_sigma);
 with fine_samples > 0: rgb_fine, depth_fine, depth_variance_fine, gate_loss_fine, gate_loss_coarse (and no rgb_coarse,
 exactly like the reference's composite_rgb=False coarse pass, rendering.py:227).
+Per-sample point outputs (hparams.return_pts / return_pts_rgb / return_pts_alpha / return_alpha, rendering.py:299, :413-417,
+:443-452) for typ in coarse and fine: pts_{typ} [N,S,3], pts_rgb_{typ} [N,S,3], pts_alpha_{typ} [N,S] and alpha_{typ} ([N,S] for
+the coarse pass, [N,S+F] in merged order for the fine pass); computed by swn_point_fields, off the compositing kernels.
 """
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
 
 import torch
+
+_POINT_FLAGS = ("return_pts", "return_pts_rgb", "return_pts_alpha", "return_alpha")
+
+
+def _want_points(hparams) -> bool:
+    return any(getattr(hparams, f, False) for f in _POINT_FLAGS)
+
+
+def _point_keys(res, hparams, typ, rays, raw_pass, z, raw, last_delta=1e10, z_pts=None, order=None):
+    """The point results of one pass: raw_pass [N*n,4] the pass's own network outputs, z [N,T] / raw [N*T,4] what it composites
+    (merged with `order` for the fine pass, z_pts [N,n] its own depths then), last_delta of its last sample (float or per ray)."""
+    from . import ops
+    if not _want_points(hparams):
+        return
+    N = z.shape[0]
+    n = (z if z_pts is None else z_pts).shape[1]
+    want_pts, want_pa = bool(getattr(hparams, "return_pts", False)), bool(getattr(hparams, "return_pts_alpha", False))
+    want_alpha = bool(getattr(hparams, "return_alpha", False))
+    if want_pts or want_pa or want_alpha:
+        pts, alpha, pa = ops.point_fields(rays.contiguous(), z.contiguous(), raw, last_delta, z_pts, order, want_pts, want_alpha, want_pa)
+        if want_pts:
+            res[f"pts_{typ}"] = pts
+        if want_alpha:
+            res[f"alpha_{typ}"] = alpha
+        if want_pa:
+            res[f"pts_alpha_{typ}"] = pa
+    if getattr(hparams, "return_pts_rgb", False):
+        res[f"pts_rgb_{typ}"] = raw_pass[:, :3].detach().view(N, n, 3)
+
 
 
 def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch.Tensor], hparams, sphere_center=None,
@@ -68,8 +100,12 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
             res["sigma_coarse"] = st[0]["raw"][:, 3].view(N, S)
             if F > 0:
                 res["sigma_fine"] = st[1]["raw"][:, 3].view(N, F)
+        _point_keys(res, hparams, "coarse", rays, st[0]["raw"], st[0]["z"], st[0]["raw"])
+        if F > 0:
+            out = st[2]
+            _point_keys(res, hparams, "fine", rays, st[1]["raw"], out["z"], out["raw"], z_pts=out["z_fine"], order=out["order"])
         return res, False
-    if not nerf.training and getattr(nerf, "graph_eval", False) and getattr(nerf, "ep", None) is None:
+    if not nerf.training and getattr(nerf, "graph_eval", False) and getattr(nerf, "ep", None) is None and not _want_points(hparams):
         return _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get_depth, get_depth_variance), False
     if F > 0:
         c, cf, out = nerf.forward_hier(rays.contiguous(), image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
@@ -85,6 +121,8 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
         if getattr(hparams, "return_sigma", False):
             res["sigma_coarse"] = c["raw"][:, 3].view(N, S)
             res["sigma_fine"] = cf["raw"][:, 3].view(N, F)
+        _point_keys(res, hparams, "coarse", rays, c["raw"], c["z"], c["raw"])
+        _point_keys(res, hparams, "fine", rays, cf["raw"], out["z"], out["raw"], z_pts=out["z_fine"], order=out["order"])
         return res, False
     c = nerf.forward_rays(rays.contiguous(), image_indices, S, chunk, float(perturb), pr, noise, training=nerf.training,
                           no_batch=nerf.moe_no_batch)
@@ -97,6 +135,7 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
         res["moe_gates_coarse"] = c["idx"].long().view(N, S, 1, 1)
     if getattr(hparams, "return_sigma", False):
         res["sigma_coarse"] = c["raw"][:, 3].view(N, S)
+    _point_keys(res, hparams, "coarse", rays, c["raw"], c["z"], c["raw"])
     return res, False
 
 
@@ -166,6 +205,17 @@ def _render_rays_bg(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, 
         res["moe_gates_coarse"] = ctx["c"]["idx"].long().view(N, S, 1, 1)
         if F > 0:
             res["moe_gates_fine"] = ctx["cf"]["idx"].long().view(N, F, 1, 1)
+    if _want_points(hparams):                                            # foreground keys only, like the reference
+        c = ctx["c"]
+        if F > 0:
+            # the coarse pass was composited (for its weights) with the 1e10 last delta; its alpha takes the reference's
+            # fg_far - max(z_coarse) on rays with a background (rendering.py:214-220)
+            ld_c = torch.where(ctx["has_bg"] > 0, ctx["fg_far"] - c["z"].max(dim=-1)[0], torch.full_like(ctx["fg_far"], 1e10))
+            _point_keys(res, hparams, "coarse", rays, c["raw"], c["z"], c["raw"], ld_c.contiguous())
+            _point_keys(res, hparams, "fine", rays, ctx["cf"]["raw"], ctx["z"], ctx["raw"], ctx["last_delta"], z_pts=ctx["z_fine"],
+                        order=ctx["order"])
+        else:
+            _point_keys(res, hparams, "coarse", rays, c["raw"], ctx["z"], ctx["raw"], ctx["last_delta"])
     return res, ctx["Nb"] > 0
 
 
