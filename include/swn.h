@@ -274,6 +274,21 @@ int swn_composite_fwd(const float* raw, const float* z, float last_delta, float 
 int swn_composite_bwd(const float* raw, const float* z, float last_delta, float rgb_padding, const float* d_rgb,
                       int n_rays, int n_samples, float* d_raw, void* stream);
 
+/* ---- the residual-expert mix of the MoE layer (csrc/residual.hip; use_residual, tutel_moe_layer_nobatch.py:777-788) -------
+ * swn_residual_mix_fwd: per token t of x / y_moe / y_res [n_tokens, model_dim] (dtype), wc [2, model_dim] f32, bc [2] f32:
+ *   l = x[t] wc^T + bc (fp32 dot products), coef[t] = softmax(l) [n_tokens, 2] f32 (saved for the backward),
+ *   y[t] = y_moe[t] * coef[t][0] + y_res[t] * coef[t][1]   (fp32, rounded once to dtype).
+ * swn_residual_mix_bwd: d_moe = coef[:, 0] dy, d_res = coef[:, 1] dy, dx = dl wc with dl[t] the softmax backward of
+ *   (<dy, y_moe>, <dy, y_res>) (all dtype); d_wc [2, model_dim] = sum_t dl[t] (x) x[t], d_bc [2] = sum_t dl[t] (f32, written, not
+ *   accumulated): per-block partial sums in the workspace of swn_residual_mix_workspace_bytes(), added in a fixed order (no atomics).
+ * model_dim in {64, 128, 256, 512}; row operands, coef and wc 16-byte aligned.                                                    */
+int swn_residual_mix_fwd(const void* x, const void* y_moe, const void* y_res, const float* wc, const float* bc, int dtype, int n_tokens,
+                         int model_dim, void* y, float* coef, void* stream);
+int swn_residual_mix_workspace_bytes(int dtype, int n_tokens, int model_dim, size_t* bytes);
+int swn_residual_mix_bwd(const void* dy, const void* x, const void* y_moe, const void* y_res, const float* coef, const float* wc,
+                         int dtype, int n_tokens, int model_dim, void* d_moe, void* d_res, void* dx, float* d_wc, float* d_bc,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- per-sample point outputs and the point-cloud export (csrc/points.hip; off the training step) ------------------
  * swn_point_fields: replaces the return_pts / return_alpha / return_pts_alpha results of _inference (rendering.py:299,
  *   :443-452).  One pass of n_rays rays: z[N,T] / raw[N*T,4] the depths and outputs it composites (merged order with `order`),

@@ -111,6 +111,9 @@ SIGNATURES = {
     "swn_composite_bounded_bwd": [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp],
     "swn_point_fields": [vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp],
     "swn_points_pack": [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp],
+    "swn_residual_mix_fwd": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
+    "swn_residual_mix_workspace_bytes": [i32, i32, i32, vp],
+    "swn_residual_mix_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp],
     "swn_hash_encode_fwd": [vp, vp, i32, i32, C.POINTER(HashCfg), vp, i32, vp, i32, vp],
     "swn_hash_encode_bwd": [vp, vp, i32, i32, C.POINTER(HashCfg), vp, i32, i32, vp, vp],
     "swn_hash_encode_bwd_xcd": [vp, vp, i32, i32, C.POINTER(HashCfg), vp, i32, i32, vp, vp, vp],

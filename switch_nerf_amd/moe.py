@@ -13,6 +13,12 @@ residual skip, one routing problem per call (the P tokens of the call), no exper
 covers that inside SwitchNeRF).  Parameter names equal the reference's (`gates.0.wg.weight`, `experts.0.weights.{l}`
 [E, in, out], `experts.0.bias.{l}` [E, 1, out]) so its state_dict loads unchanged.
 
+use_residual=True adds the residual MoE (DeepSpeed PR-MoE, tutel_moe_layer_nobatch.py:504-505, 666-671, 777-788) on every path above
+(top-1, top-k, load / importance loss, dynamic capacity, moe_no_batch, eval): `coefficient` (Linear [M -> 2], fp32) and
+`residual_expert` (`weights.{l}` [1, in, out], `bias.{l}` [1, 1, out]), y = y_moe * c0 + residual_expert(x) * c1 with
+c = softmax(coefficient(x)); the residual expert runs on the experts' chain kernels as one group of all P rows (_ResidualExpertFunction),
+the mix on swn_residual_mix_fwd / _bwd (_ResidualMixFunction).  l_aux and the gate extras are unchanged.
+
 SwitchNeRF (model.py) does NOT go through this class: it fuses the layer's combine into the next chain and keeps flat
 parameter buffers.  This is the drop-in for code that keeps the reference's own NeRFMoE module and only swaps the layer.
 """
@@ -270,10 +276,90 @@ class _MoETopKFunction(torch.autograd.Function):
         return (None, dx.to(ctx.x_dtype), dg.to(ctx.g_dtype), d_wg, None, None, *dws, *[b.view(E, 1, M) for b in dbs])
 
 
+def _residual_geometry(M, dt, P):
+    return 7 if (M == 256 and dt != torch.float32 and P >= 256) else 1      # (the experts' choice, with all P rows as one group)
+
+
+class _ResidualExpertFunction(torch.autograd.Function):
+    """The residual expert (use_residual: an ExpertMLP with one local expert run over every token, tutel_moe_layer_nobatch.py:666-671,
+    777-783): the experts' chain kernels with one group of all P rows, no gather; its weight gradients on the same wgrad launch."""
+
+    @staticmethod
+    def forward(ctx, layer, xs, *wb):
+        o, dt = ops, layer.dtype
+        L, M = layer.layer_num, layer.model_dim
+        P = xs.shape[0]
+        dev = xs.device
+        xs = xs.detach().contiguous()
+        need_grad = any(ctx.needs_input_grad[1:])
+        wf = [o.pack_weights(w.detach().float().contiguous(), dt, True) for w in wb[:L]]
+        bias = [b.detach().float().reshape(1, M).contiguous() for b in wb[L:]]
+        saves = [torch.empty(P, M, dtype=dt, device=dev) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
+        nw = o.chain_mask_words(dt, 1, P, M)
+        masks = [torch.empty(nw, dtype=torch.int32, device=dev) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
+        layers = [o.Layer(wf[l], bias[l], relu=1 if l < L - 1 else 0, skip=(l in layer.skips), save=saves[l] if l < L - 1 else None,
+                          mask=masks[l] if l < L - 1 else None) for l in range(L)]
+        rows = torch.full((1,), P, dtype=torch.int32, device=dev)
+        y = torch.empty(P, M, dtype=dt, device=dev)
+        o.mlp_chain(xs, layers, y, n_groups=1, n_wsets=1, group_stride=P, group_rows=rows, group_rows_clamp=P, tag=1,
+                    geometry=_residual_geometry(M, dt, P))
+        ctx.layer = layer
+        ctx.save_for_backward(xs, rows, *wb[:L], *[s for s in saves if s is not None], *[m for m in masks if m is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        o, layer = ops, ctx.layer
+        dt, L, M = layer.dtype, layer.layer_num, layer.model_dim
+        sv = ctx.saved_tensors
+        xs, rows = sv[:2]
+        ws = sv[2:2 + L]
+        saves = list(sv[2 + L:2 + L + (L - 1)])
+        masks = list(sv[2 + L + (L - 1):])
+        P = xs.shape[0]
+        dev = xs.device
+        dout = dy.to(dt).contiguous()
+        wbk = [o.pack_weights(w.detach().float().contiguous(), dt, False) for w in ws]
+        dz = [torch.empty(P, M, dtype=dt, device=dev) for _ in range(L - 1)]
+        dx = torch.empty(P, M, dtype=dt, device=dev)
+        skip_l = layer.skips[0] if layer.skips else None
+        bl = [o.Layer(wbk[l], None, relu=2 if l > 0 else 0, mask=masks[l - 1] if l > 0 else None, save=dz[l - 1] if l > 0 else None)
+              for l in range(L - 1, -1, -1)]
+        o.mlp_chain(dout, bl, dx, n_groups=1, n_wsets=1, group_stride=P, group_rows=rows, group_rows_clamp=P,
+                    y_add=dz[skip_l] if skip_l is not None else None, tag=2, geometry=_residual_geometry(M, dt, P))
+        dws = [torch.zeros(1, M, M, dtype=torch.float32, device=dev) for _ in range(L)]
+        dbs = [torch.zeros(1, M, dtype=torch.float32, device=dev) for _ in range(L)]
+        items = [(xs if l == 0 else saves[l - 1], dout if l == L - 1 else dz[l], dws[l], dbs[l], None, None) for l in range(L)]
+        for i0 in range(0, L, 8):
+            # (one group: the balanced launch; n_splits only sizes the fallback's workspace)
+            o.wgrad_batched(items[i0:i0 + 8], n_groups=1, n_wsets=1, group_stride=P, group_rows=rows, group_rows_clamp=P, n_splits=1, tag=1)
+        return (None, dx, *dws, *[b.view(1, 1, M) for b in dbs])
+
+
+class _ResidualMixFunction(torch.autograd.Function):
+    """y = y_moe * c0 + y_res * c1, c = softmax(coefficient(x)) (tutel_moe_layer_nobatch.py:785-787): swn_residual_mix_fwd / _bwd.
+    x, y_moe, y_res in the layer dtype; the coefficient Linear in fp32 like the router."""
+
+    @staticmethod
+    def forward(ctx, layer, x, y_moe, y_res, wc, bc):
+        xs, ym, yr = x.detach().contiguous(), y_moe.detach().contiguous(), y_res.detach().contiguous()
+        wc32 = wc.detach().float().contiguous()
+        y, coef = ops.residual_mix_fwd(xs, ym, yr, wc32, bc.detach().float().contiguous())
+        layer.residual_coef = coef
+        ctx.save_for_backward(xs, ym, yr, coef, wc32)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xs, ym, yr, coef, wc32 = ctx.saved_tensors
+        d_moe, d_res, dx, d_wc, d_bc = ops.residual_mix_bwd(dy.to(xs.dtype).contiguous(), xs, ym, yr, coef, wc32)
+        return None, dx, d_moe, d_res, d_wc, d_bc
+
+
 class MoELayer(nn.Module):
     def __init__(self, gate_type: dict, model_dim: int, experts: dict, scan_expert_func=None, result_func=None, group=None,
                  seeds=None, a2a_ffn_overlap_degree=1, parallel_type="auto", pad_samples=False, moe_no_batch=False,
-                 return_gates=False, return_gate_logits=False, dtype=torch.bfloat16):
+                 use_residual=False, return_gates=False, return_gate_logits=False, dtype=torch.bfloat16):
         super().__init__()
         if gate_type.get("type", "top") != "top":
             raise NotImplementedError("gate type 'top' only (the one the reference's NeRFMoE builds)")
@@ -317,7 +403,14 @@ class MoELayer(nn.Module):
         if seeds is not None:                      # gate under seeds[0], experts under seeds[1] (tutel_moe_layer_nobatch.py:654-703)
             gen = torch.Generator().manual_seed(int(seeds[1]))
         self.gates = nn.ModuleList([_Gate(self.gate_dim, self.n_experts)])
+        # use_residual (--moe_use_residual; the DeepSpeed PR-MoE form, tutel_moe_layer_nobatch.py:504-505, 666-671): a [M -> 2] fp32
+        # Linear mixing the MoE output with one more expert MLP run over every token, drawn after the experts from the same seed
+        self.use_residual = bool(use_residual)
+        if self.use_residual:
+            self.coefficient = nn.Linear(self.model_dim, 2)
         self.experts = nn.ModuleList([_ExpertParams(self.n_experts, self.model_dim, self.layer_num, gen)])
+        if self.use_residual:
+            self.residual_expert = _ExpertParams(1, self.model_dim, self.layer_num, gen)
 
     def forward(self, input: torch.Tensor, gate_input: Optional[torch.Tensor] = None, gate_noise_draw: Optional[torch.Tensor] = None,
                 normal_noise_draw: Optional[torch.Tensor] = None):
@@ -348,6 +441,8 @@ class MoELayer(nn.Module):
             y, l_aux, idx = _MoEFunction.apply(self, x, g, self.gates[0].wg.weight, noise, *ex.weights, *ex.bias)
         else:
             y, l_aux, l_bal, idx = _MoETopKFunction.apply(self, x, g, self.gates[0].wg.weight, noise, clean, *ex.weights, *ex.bias)
+        if self.use_residual:
+            y = self._residual(x, y)
         y = y.view(shape)
         y.l_aux = l_aux                                                                         # :792-796
         extras = {}
@@ -358,6 +453,16 @@ class MoELayer(nn.Module):
         if extras:
             y.gate_extras = extras
         return y
+
+    def _residual(self, x, y_moe):
+        """y_moe * c0 + residual_expert(x) * c1, c = softmax(coefficient(x)) (tutel_moe_layer_nobatch.py:777-788), on x in the layer
+        dtype; l_aux and the gate extras are the MoE path's.  self.residual_coef: the [P, 2] fp32 mixing weights of the last forward."""
+        dt = self.dtype
+        xs = x.to(dt)
+        rex = self.residual_expert
+        y_res = _ResidualExpertFunction.apply(self, xs, *rex.weights, *rex.bias)
+        y = _ResidualMixFunction.apply(self, xs, y_moe.to(dt), y_res, self.coefficient.weight, self.coefficient.bias)
+        return y.to(x.dtype)
 
 
 def moe_layer(*args, **kw):

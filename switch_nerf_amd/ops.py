@@ -471,6 +471,34 @@ def combine_bwd(dy_in, y, dsig, wsig, gate):
     return dout, dgate
 
 
+def residual_mix_fwd(x, y_moe, y_res, wc, bc):
+    """The residual-expert mix (swn_residual_mix_fwd): x / y_moe / y_res [P, M] in one dtype, wc [2, M] / bc [2] f32 ->
+    (y [P, M] in that dtype, coef [P, 2] f32 = softmax(x wc^T + bc))."""
+    P, M = x.shape
+    assert y_moe.shape == x.shape and y_res.shape == x.shape and y_moe.dtype == x.dtype and y_res.dtype == x.dtype
+    assert wc.dtype == torch.float32 and bc.dtype == torch.float32 and wc.shape == (2, M) and bc.numel() == 2
+    y = torch.empty_like(x)
+    coef = torch.empty(P, 2, dtype=torch.float32, device=x.device)
+    call("swn_residual_mix_fwd", _p(x), _p(y_moe), _p(y_res), _p(wc), _p(bc), _dt(x), P, M, _p(y), _p(coef), _stream())
+    return y, coef
+
+
+def residual_mix_bwd(dy, x, y_moe, y_res, coef, wc):
+    """Backward of residual_mix_fwd (swn_residual_mix_bwd) -> (d_moe, d_res, dx) in x's dtype, d_wc [2, M] and d_bc [2] f32 (ordered
+    per-block sums: the same bits on every launch)."""
+    P, M = x.shape
+    assert all(t.shape == x.shape and t.dtype == x.dtype for t in (dy, y_moe, y_res)) and coef.shape == (P, 2)
+    nb = C.c_size_t(0)
+    call("swn_residual_mix_workspace_bytes", _dt(x), P, M, C.byref(nb))
+    ws = torch.empty(max(int(nb.value), 4) // 4, dtype=torch.float32, device=x.device)
+    d_moe, d_res, dx = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    d_wc = torch.empty(2, M, dtype=torch.float32, device=x.device)
+    d_bc = torch.empty(2, dtype=torch.float32, device=x.device)
+    call("swn_residual_mix_bwd", _p(dy), _p(x), _p(y_moe), _p(y_res), _p(coef), _p(wc), _dt(x), P, M, _p(d_moe), _p(d_res), _p(dx),
+         _p(d_wc), _p(d_bc), _p(ws), ws.numel() * 4, _stream())
+    return d_moe, d_res, dx, d_wc, d_bc
+
+
 def heads_fwd(y, h2, w_sigma, b_sigma, w_color, b_color, sigma_noise):
     P, M = y.shape
     H2 = h2.shape[1]
