@@ -381,6 +381,7 @@ __device__ __forceinline__ int wg_chunk(int r, int c) { return c ^ (((r & 3) << 
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef short ws_s4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) ws_s4_t* ws_lds_s4_t;
+template <bool V> struct WsFlag { static constexpr bool value = V; };
 
 template <typename T, int TAG>
 __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
@@ -493,14 +494,21 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
     for (int qq = 0; qq < 4; ++qq) trb[qq] = SLAB + r * 512 + 16 * wg_chunk(r, 8 * wn + 2 * qq + (p >> 1)) + 8 * (p & 1);
   }
 
-  for (int pi = 0; pi < n_pieces; ++pi) {
+  // One piece, in four copies: GATHER = the job reads an operand through an index (a_gather or b_gather), BIAS = it has a db.  The
+  // copy is picked once per piece (workgroup-uniform), so the slab loop of a plain job holds no index loads and keeps the counted
+  // waits on its LDS reads, that of a gathered job does not drain its index loads at the barrier (it waits once for indices and LDS
+  // reads together, in front of the first MFMA), and a job without db holds no bias instruction.
+  auto run_piece = [&](auto gflag, auto bflag, const int pi) {
+    constexpr bool GATHER = decltype(gflag)::value, BIAS = decltype(bflag)::value;
     {
       const int j = __builtin_amdgcn_readfirstlane(plist[1 + 4 * pi]), e = __builtin_amdgcn_readfirstlane(plist[2 + 4 * pi]);
       const int pa = __builtin_amdgcn_readfirstlane(plist[3 + 4 * pi]), pb = __builtin_amdgcn_readfirstlane(plist[4 + 4 * pi]);
       const WsJob& it = p.job[j];
       const int m_dim = it.m_dim, n_dim = it.n_dim;
       const bool active = (wm * 128 < m_dim) && (wn * 64 < n_dim);
-      const bool do_bias = (it.db != nullptr) && wm == 0 && (wn * 64 < n_dim);
+      // (giving the wave row wm = 1 one of the two B fragment pairs of the bias sums: expert launch -1..2 %, dense front +1..3 %, no net
+      //  gain in the step: profiles/r08_wgrad_expert.md)
+      const bool do_bias = BIAS && wm == 0 && (wn * 64 < n_dim);
       // a column block of a wider operand pair: the block of A is read again by the job of the next column block of B, and the other way round
       const bool a_shared = it.ldb > n_dim, b_shared = it.lda > m_dim;
       // ---------------------------------------------------------------- one piece: slabs [pa, pb) of (job j, weight set e)
@@ -565,7 +573,6 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
       // (The loads are unconditional straight-line code - without a gather they read a zero word - and the choice between the loaded
       //  index and the row itself is made where the value is used: a load inside `if (gather)` is waited for at the end of its branch.)
       const cidx_t agp = ag ? ag : (cidx_t)g_zero_page, bgp = bg ? bg : (cidx_t)g_zero_page;
-      const bool gathered = ag != nullptr || bg != nullptr;
       long rr0[2], rr1[2];
       int ia0[2], ia1[2], ib0[2], ib1[2];
       auto group_row0 = [&]() -> long { return p.group_begin ? (long)((cidx_t)p.group_begin)[gp] : (long)gp * p.group_stride; };
@@ -577,8 +584,8 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
           rr0[i] = grow0 + max(min(rf, rows_p - 1), 0);
           rr1[i] = grow0 + max(min(rf + RPP - 1, rows_p - 1), 0);
         }
-        if (gathered) {                                    // (jobs without a gathered operand - five of the expert launch's seven, all dense
-          ia0[0] = agp[ag ? rr0[0] : 0]; ia1[0] = agp[ag ? rr1[0] : 0];      //  ones - skip the loads; ia / ib are then never looked at)
+        if constexpr (GATHER) {                            // (jobs without a gathered operand - five of the expert launch's seven, all dense
+          ia0[0] = agp[ag ? rr0[0] : 0]; ia1[0] = agp[ag ? rr1[0] : 0];      //  ones - run the copy without the loads)
           ia0[1] = agp[ag ? rr0[1] : 0]; ia1[1] = agp[ag ? rr1[1] : 0];
           ib0[0] = bgp[bg ? rr0[0] : 0]; ib1[0] = bgp[bg ? rr1[0] : 0];
           ib0[1] = bgp[bg ? rr0[1] : 0]; ib1[1] = bgp[bg ? rr1[1] : 0];
@@ -589,8 +596,11 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int rf = rp + (2 * wave + i) * RPP;
-          const long a0 = ag ? (long)max(ia0[i], 0) : rr0[i], a1 = ag ? (long)max(ia1[i], 0) : rr1[i];      // (-1 = an empty slot of the permutation)
-          const long b0 = bg ? (long)max(ib0[i], 0) : rr0[i], b1 = bg ? (long)max(ib1[i], 0) : rr1[i];
+          long a0 = rr0[i], a1 = rr1[i], b0 = rr0[i], b1 = rr1[i];
+          if constexpr (GATHER) {                          // (-1 = an empty slot of the permutation)
+            if (ag) { a0 = (long)max(ia0[i], 0); a1 = (long)max(ia1[i], 0); }
+            if (bg) { b0 = (long)max(ib0[i], 0); b1 = (long)max(ib1[i], 0); }
+          }
           const bool ok = live && (rf + prow < rows_p);
           const uint32_t as = (uint32_t)((RPP == 2 && prow) ? a1 : a0), bs = (uint32_t)((RPP == 2 && prow) ? b1 : b0);
           src[2 * i] = ok ? a_lane[i] + (uint64_t)as * a_rb : zero;
@@ -626,10 +636,11 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
       for (int n = 0; n < nsl; ++n) {
         prepare();
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        // TR: the gather indices fetch() just asked for have landed (the copies' wait above covers their latency).  With a scalar load
-        // in flight hipcc cannot count the LDS reads below (scalar loads complete out of order) and waits for all 24 in front of the
-        // first MFMA; this compiler-visible lgkmcnt(0) (vmcnt, expcnt: no wait) lets it wait per fragment.
-        if constexpr (TR) __builtin_amdgcn_s_waitcnt(0xC07F);
+        // TR, plain copy: nothing is in flight on lgkmcnt here but the odd group_begin load of prepare(); this compiler-visible
+        // lgkmcnt(0) (vmcnt, expcnt: no wait) tells hipcc so, and it waits for the 24 LDS reads below per fragment.  The gathered copy
+        // must not wait here: it would sit through the index loads fetch() has just issued, which are not needed before the next
+        // prepare() (profiles/r08_wgrad_expert.md).
+        if constexpr (TR && !GATHER) __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_s_barrier();
         issue((slot + WG_NS - 1) % WG_NS);
         const char* A = sa(slot);
@@ -663,7 +674,7 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
               // 0-7 then 16-23 of every slab and rows 8-15 then 24-31, added at the end.  One v_permlane32_swap per dword gives lanes
               // 0-31 the rows 16-31 of B fragments 0, 1 and lanes 32-63 the rows 0-15 of fragments 2, 3: lane group g then runs sum
               // (g & 1) of fragment f + 2 (g >> 1) in slot f.
-              if (do_bias) {
+              if constexpr (BIAS) if (do_bias) {
 #pragma unroll
                 for (int f = 0; f < 2; ++f) {
                   const u32x4_t x = __builtin_bit_cast(u32x4_t, fr(8 + f)), y = __builtin_bit_cast(u32x4_t, fr(10 + f));
@@ -834,7 +845,7 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
             }
       }
       if constexpr (TR) {                      // lane groups 0 / 2 add the second running sum (groups 1 / 3) to their first
-        if (do_bias) {
+        if constexpr (BIAS) if (do_bias) {
 #pragma unroll
           for (int f = 0; f < 2; ++f) dbv[f] += __shfl_xor(dbv[f], 16);
           if ((lane & 16) == 0) {
@@ -861,6 +872,15 @@ __global__ __launch_bounds__(WG_NT) void wgrad_stream_kernel(const WsArgs p) {
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (stores and copies share vmcnt: the next piece counts from zero)
       __syncthreads();                                       // every wave has left the ring before the next piece refills it
+    }
+  };
+  for (int pi = 0; pi < n_pieces; ++pi) {
+    const WsJob& it = p.job[__builtin_amdgcn_readfirstlane(plist[1 + 4 * pi])];
+    const bool g = it.a_gather != nullptr || it.b_gather != nullptr, b = it.db != nullptr;
+    if (g) {
+      if (b) run_piece(WsFlag<true>{}, WsFlag<true>{}, pi); else run_piece(WsFlag<true>{}, WsFlag<false>{}, pi);
+    } else {
+      if (b) run_piece(WsFlag<false>{}, WsFlag<true>{}, pi); else run_piece(WsFlag<false>{}, WsFlag<false>{}, pi);
     }
   }
 }
