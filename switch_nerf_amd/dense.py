@@ -154,10 +154,9 @@ class DenseNeRF(SwitchNeRF):
         W, L, H2, s = self.M, self.L, self.H2, self.skip_l
         c = dict(N=N, S=S, P=P, n_seg=max(1, P // seg_tokens), seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
         c["pe"], c["pe_dir"] = pe, pe_dir
-        _b = lambda name, shape, dtype: self._buf(tag + ":" + name, shape, dtype)
-        c["acts"] = [_b(f"act{i}", (P, W), dt) for i in range(L)]          # post-ReLU outputs; acts[L-1] = xyz_ (c["y"])
+        c["acts"] = [self._cbuf(c, f"act{i}", (P, W), dt) for i in range(L)]          # post-ReLU outputs; acts[L-1] = xyz_ (c["y"])
         mw = o.chain_mask_words(dt, 1, P, max(W, self.KP))
-        c["masks"] = [_b(f"mask{i}", (mw,), torch.int32) for i in range(L)]
+        c["masks"] = [self._cbuf(c, f"mask{i}", (mw,), torch.int32) for i in range(L)]
         sv = self._saving
         c["no_grad"] = not sv
         layers = []
@@ -173,18 +172,8 @@ class DenseNeRF(SwitchNeRF):
             o.mlp_chain(pe, layers, c["acts"][L - 1], tag=1)
         c["y"] = c["acts"][L - 1]
         # ---- per-ray part of dir_a_encoding: [PE(dir), appearance embedding] @ W2r + b2 (nerf.py:173-181)
-        c["ray_feat"], c["c_ray"] = o.ray_feat_fwd(pe_dir, self.in_dir, self.p["emb"], image_indices.contiguous(), self.p["l2r.w"], self.p["l2.b"])
-        from .model import c_esz
-        fused = self.sw["fused_heads"] and W in (256, 512) and H2 in (128, 256) and W * c_esz(dt) <= 1024      # heads inside the tail chain's launch (swn.h: heads_raw)
-        c["h1"] = _b("h1", (P, W), dt) if sv else None
-        c["h2"] = _b("h2", (P, H2), dt) if (sv or not fused) else None      # an inference forward writes nothing but raw
-        c["raw"] = torch.empty(P, 4, dtype=torch.float32, device=self.dev) if fused else None
-        o.mlp_chain(c["y"], [o.Layer(self.wf["l1"], self.p["l1.b"].view(1, W), save=c["h1"] if sv else None),
-                             o.Layer(self.wf["l2h"], None, relu=1, rowbias=c["c_ray"], rows_per_bias=S)], c["h2"], tag=4, group_stride=P,
-                    heads=(self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"], sigma_noise, c["raw"]) if fused else None)
-        if not fused:
-            c["raw"] = o.heads_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
-                                   sigma_noise)
+        self._ray_feat(c, pe_dir, image_indices)
+        self._tail_forward(c, c["y"], sigma_noise, c["c_ray"], S)      # (heads inside the tail chain's launch, swn.h: heads_raw)
         c["l_aux"] = torch.zeros(c["n_seg"], dtype=torch.float32, device=self.dev)     # no gate loss (runner.py:1104 guards on use_moe)
         c["idx"] = None
         return c
@@ -197,28 +186,22 @@ class DenseNeRF(SwitchNeRF):
         S, P = c["S"], c["P"]
         W, L, H2, s = self.M, self.L, self.H2, self.skip_l
         g, acts, masks = self.g, c["acts"], c["masks"]
-        _b = lambda name, shape, dtype: self._buf(c["tag"] + ":" + name, shape, dtype)
         dh2, dsig, dc_ray = o.heads_bwd(c["y"], c["h2"], self.p["color.w"], c["raw"], d_raw, g["sigma.w"], g["sigma.b"], g["color.w"],
                                         g["color.b"], rows_per_group=S)
-        if dc_ray.shape[1] in (64, 128, 256) and c["ray_feat"].shape[1] <= 256:      # split over the rays + ordered reduce (one launch)
-            o.ray_feat_wgrad(c["ray_feat"], dc_ray, g["l2r.w"], g["l2.b"])
-        else:
-            g["l2r.w"].addmm_(c["ray_feat"].t(), dc_ray)
-            g["l2.b"].add_(dc_ray.sum(0))
-        o.emb_grad(dc_ray @ self.p["l2r.w"][self.in_dir:].t(), c["image_indices"].contiguous(), g["emb"])
-        dh1 = _b("dh1", (P, W), dt)
+        self._ray_level_grads(c, dc_ray)
+        dh1 = self._cbuf(c, "dh1", (P, W), dt)
         nsp = max(1, min(256, P // 1024))
         # d(pre-activation of the last trunk layer) = (dy + dsigma * w_sigma) * (xyz_ > 0): the combine backward with a unit gate
         if getattr(self, "_ones", None) is None or self._ones.numel() < P:
             self._ones = torch.ones(P, dtype=torch.float32, device=self.dev)
         ones = self._ones[:P]
-        dz = [_b(f"dz{i}", (P, W), dt) for i in range(L - 1)]
+        dz = [self._cbuf(c, f"dz{i}", (P, W), dt) for i in range(L - 1)]
         if W * dh1.element_size() <= 1024:      # ... applied in the write-out of the tail backward chain (swn.h comb_*: swn_combine_bwd's
-            dz.append(_b(f"dz{L - 1}", (P, W), dt))                      # arithmetic, value for value): dy never reaches memory
+            dz.append(self._cbuf(c, f"dz{L - 1}", (P, W), dt))                      # arithmetic, value for value): dy never reaches memory
             o.mlp_chain(dh2, [o.Layer(self.wb["l2h"], None, save=dh1), o.Layer(self.wb["l1"], None)], dz[L - 1], tag=5,
-                        combine=(c["y"], dsig, self.p["sigma.w"], ones, _b("dgate_unused", (P,), torch.float32)))
+                        combine=(c["y"], dsig, self.p["sigma.w"], ones, self._cbuf(c, "dgate_unused", (P,), torch.float32)))
         else:
-            dy = _b("dy", (P, W), dt)
+            dy = self._cbuf(c, "dy", (P, W), dt)
             o.mlp_chain(dh2, [o.Layer(self.wb["l2h"], None, save=dh1), o.Layer(self.wb["l1"], None)], dy, tag=5)
             dz.append(o.combine_bwd(dy, c["y"], dsig, self.p["sigma.w"], ones)[0])
         o.wgrad(c["h1"], dh2, g["l2h.w"].view(1, W, H2), None, n_splits=nsp)

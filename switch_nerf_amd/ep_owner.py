@@ -108,13 +108,14 @@ def _send_order(m, c, pl):
     return perm, row_of_tok.view(-1)
 
 
-def forward(m, c, pe_dir, image_indices, sigma_noise, sv):
-    """The expert-parallel branch of SwitchNeRF._net_forward_rows behind the routing: fills c["raw"] (token order) and what backward_a needs."""
+def forward(m, c, layers, pe_dir, image_indices, sigma_noise, sv):
+    """The owner-tail mode of SwitchNeRF._net_forward_rows behind the routing (layers: the local experts' forward layer list): fills c["raw"]
+    (token order) and what backward_a needs."""
     o, ep, dev, dt = ops, m.ep, m.dev, m.dtype
     W, El, E, M, H2, L = ep.world, ep.El, m.E, m.M, m.H2, m.L
     P, S, N, n_seg, cap, tag = c["P"], c["S"], c["N"], c["n_seg"], c["cap"], c["tag"]
     _b = lambda name, shape, dtype: m._buf(tag + ":ot_" + name, shape, dtype)
-    c["ray_feat"], c["c_ray"] = o.ray_feat_fwd(pe_dir, m.in_dir, m.p["emb"], image_indices.contiguous(), m.p["l2r.w"], m.p["l2.b"])
+    m._ray_feat(c, pe_dir, image_indices)
     c_ray_all = _all_gather(ep, c["c_ray"])                   # the per-ray half of layer "2" of EVERY rank's rays (512 B per ray)
     pl = _plan(m, c)
     n_kept, Rk, n_drop = pl["n_kept"], pl["Rk"], pl["n_drop"]
@@ -150,18 +151,13 @@ def forward(m, c, pe_dir, image_indices, sigma_noise, sv):
     dropped_t = torch.arange(Rk, Rk + max(n_drop, 1), dtype=torch.int32, device=dev)      # (one spare entry: the list must not be empty)
     drop_begin_t = torch.tensor([0, n_drop], dtype=torch.int32, device=dev)
     saves, masks = c["saves"], c["masks"]                     # (the context's expert buffers: n_seg * E * cap rows, one mask word set per tile)
-    skips = set(m.cfg["skips"])
     y_t = _b("y", (TB, M), dt)[:T] if sv else None
     h1_t = _b("h1", (TB, M), dt)[:T] if sv else None
     h2_t = _b("h2", (TB, H2), dt)[:T] if sv else None
     raw_t = _b("raw", (TB, 4), torch.float32)[:T]
-    if "l2h_pad" not in m.wf:
-        m.wf["l2h_pad"] = o.pack_weights_padded(m.p["l2h.w"].unsqueeze(0), dt, True, 0, 256)
-    lys = [o.Layer(m._local_experts(m.wf[f"exp{l}"]), m._local_experts(m.p[f"exp{l}.b"]), relu=1 if l < L - 1 else 0, skip=(l in skips),
-                   save=saves[l] if (sv and l < L - 1) else None, mask=masks[l] if (sv and l < L - 1) else None) for l in range(L)]
-    lys[-1].save = y_t
-    lys += [o.Layer(m.wf["l1"], m.p["l1.b"].view(1, M), save=h1_t),
-            o.Layer(m.wf["l2h_pad"], None, relu=1, rowbias=c_ray_all, rows_per_bias=0)]      # (the bias row of token t: ray_t[t])
+    last = layers[-1]
+    lys = layers[:-1] + [o.Layer(last.w, last.b, relu=last.relu, skip=last.skip, save=y_t), o.Layer(m.wf["l1"], m.p["l1.b"].view(1, M), save=h1_t),
+                         o.Layer(m._l2h_pad(True), None, relu=1, rowbias=c_ray_all, rows_per_bias=0)]      # (the bias row of token t: ray_t[t])
     heads = (m.p["sigma.w"], m.p["sigma.b"], m.p["color.w"], m.p["color.b"], noise_t, raw_t)
     with m._timed("expert_fwd"):
         o.mlp_chain(xr, lys, h2_t, n_groups=ngs, n_wsets=El, group_stride=cap, group_rows=grp_rows, group_rows_clamp=cap, x_gather=ident,
@@ -198,12 +194,7 @@ def backward_a(m, c, d_raw, d_laux):
     _b = lambda name, shape, dtype: m._buf(tag + ":ot_" + name, shape, dtype)
     # ---- source: the per-ray bias gradient from d_raw, raw and the sign of h2 (dh2 = (h2 > 0) * the colour heads' input gradient) ----
     dc_ray = o.ray_bias_grad_bits(c["h2_bits"], c["raw"], d_raw.contiguous(), m.p["color.w"], S)
-    if dc_ray.shape[1] in (64, 128, 256) and c["ray_feat"].shape[1] <= 256:
-        o.ray_feat_wgrad(c["ray_feat"], dc_ray, g["l2r.w"], g["l2.b"])
-    else:
-        g["l2r.w"].addmm_(c["ray_feat"].t(), dc_ray)
-        g["l2.b"].add_(dc_ray.sum(0))
-    o.emb_grad(dc_ray @ m.p["l2r.w"][m.in_dir:].t(), c["image_indices"].contiguous(), g["emb"])
+    m._ray_level_grads(c, dc_ray)
     # ---- d_raw to the owners ----
     d_raw = d_raw.contiguous()
     d_raw_t = _b("d_raw", (q["TB"], 4), torch.float32)[:T]
@@ -224,27 +215,18 @@ def backward_a(m, c, d_raw, d_laux):
     dz_last = _b("dz_last", (rows_b, M), dt)
     dx = m._buf(tag + ":dx", (c["rows"], M), dt)
     dx_r = dx if ep.local else _b("dx_r", (rows_b, M), dt)      # (no process group: the input gradients are written where the front backward reads)
-    if "l2h_pad" not in m.wb:
-        m.wb["l2h_pad"] = o.pack_weights_padded(m.p["l2h.w"].unsqueeze(0), dt, False, 0, 256)
     skip_l = list(m.cfg["skips"])[0] if len(m.cfg["skips"]) else None
-    bl = []
-    for i in range(L):
-        l = L - 1 - i
-        bl.append(o.Layer(m._local_experts(m.wb[f"exp{l}"]), None, relu=2 if l > 0 else 0, mask=q["masks"][l - 1] if l > 0 else None,
-                          save=dz[l - 1] if l > 0 else None))
+    bl = o.expert_bwd_layers([m._local_experts(m.wb[f"exp{l}"]) for l in range(L)], q["masks"], dz)
     with m._timed("expert_bwd"):
-        o.mlp_chain(dh2_t, [o.Layer(m.wb["l2h_pad"], None, save=dh1_t), o.Layer(m.wb["l1"], None, save=dz_last)] + bl, dx_r, n_groups=ngs,
+        o.mlp_chain(dh2_t, [o.Layer(m._l2h_pad(False), None, save=dh1_t), o.Layer(m.wb["l1"], None, save=dz_last)] + bl, dx_r, n_groups=ngs,
                     n_wsets=El, group_stride=cap, group_rows=q["grp_rows"], group_rows_clamp=cap, x_gather=q["ident"],
                     y_add=dz[skip_l] if skip_l is not None else None, tag=8, geometry=7, x_features=H2,
                     combine=(q["y"], dsig_t, m.p["sigma.w"], q["gmax"], dgmax_t, g["sigma.w"].view(-1) if fused_dws else None),
                     head=(2, q["drop_begin"], q["dropped"]), group_begin=q["ep_begin"])
     nsp = max(1, min(256, T // 1024))
     m._dense_wgrads([(q["h1"], dh2_t, g["l2h.w"].view(1, M, H2), None), (q["y"], dh1_t, g["l1.w"].view(1, M, M), g["l1.b"].view(1, M))], nsp)
-    items = []
-    for l in range(L):
-        a = q["xr"] if l == 0 else q["saves"][l - 1]
-        bz = dz_last if l == L - 1 else dz[l]
-        items.append((a, bz, m._local_experts(g[f"exp{l}.w"]), m._local_experts(g[f"exp{l}.b"]), None, None))
+    items = o.expert_wgrad_items(q["xr"], q["saves"], dz, dz_last, [m._local_experts(g[f"exp{l}.w"]) for l in range(L)],
+                                 [m._local_experts(g[f"exp{l}.b"]) for l in range(L)])      # (received rows: no gather on either side)
     with m._timed("expert_wgrad"):
         o.wgrad_multi(items, n_groups=ngs, n_wsets=El, group_stride=cap, group_rows=q["grp_rows"], group_rows_clamp=cap, tag=1,
                       group_begin=q["ep_begin"])

@@ -343,18 +343,13 @@ class SwitchNeRF:
                 self.wf["xyz_pad"] = ops.pack_weights_padded(w3, self.dtype, True, 256)
             else:
                 pairs.append((w3, self.wf["xyz_pad"], True, 256))
-        if self._tail_big() or self._tail_fused() or "l2h_pad" in self.wb:      # the tail BACKWARD layers likewise: dh2 (128 features) under the backward-data copy of layer "2" padded in K
-            w3 = self.p["l2h.w"].unsqueeze(0)
-            if "l2h_pad" not in self.wb:
-                self.wb["l2h_pad"] = ops.pack_weights_padded(w3, self.dtype, False, 0, 256)
-            else:
-                pairs.append((w3, self.wb["l2h_pad"], False, 0, 256))
-        if self._tail_fused() or "l2h_pad" in self.wf:    # the tail folded into the expert forward chain: layer "2" (256 -> 128) zero-padded to 256 outputs
-            w3 = self.p["l2h.w"].unsqueeze(0)
-            if "l2h_pad" not in self.wf:
-                self.wf["l2h_pad"] = ops.pack_weights_padded(w3, self.dtype, True, 0, 256)
-            else:
-                pairs.append((w3, self.wf["l2h_pad"], True, 0, 256))
+        # the tail BACKWARD layers likewise: dh2 (128 features) under the backward-data copy of layer "2" padded in K; the tail folded into
+        # the expert forward chain: layer "2" (256 -> 128) zero-padded to 256 outputs
+        for fwd, d, want in ((False, self.wb, self._tail_big() or self._tail_fused()), (True, self.wf, self._tail_fused())):
+            if "l2h_pad" in d:
+                pairs.append((self.p["l2h.w"].unsqueeze(0), d["l2h_pad"], fwd, 0, 256))
+            elif want:
+                self._l2h_pad(fwd)
         if pairs:
             ops.repack_weights_batched(pairs)      # one launch (was 23 of ~5 us each: a tenth of the step at 1024 rays per GPU)
         if self._flat_param is not None:           # the copies now match the master weights as of this version of flat_param
@@ -418,7 +413,7 @@ class SwitchNeRF:
                   reference only makes max(loc) + 1 larger; only its padded buffer's size differs) - used as is, expert parallelism
                   included;
           cf = 0: max(loc) + 1, every token kept: seg_tokens, a capacity no group exceeds (the training step then runs on the packed
-                  row space, one row per token - _net_forward_rows)."""
+                  row space, one row per token - _route)."""
         if self.cf == 0:
             return int(seg_tokens)
         return int(abs(self.cf) * ((int(seg_tokens) + self.E - 1) // self.E))      # tutel_fast_dispatch.py:211 / :216
@@ -496,6 +491,10 @@ class SwitchNeRF:
             b = torch.empty(shape, dtype=dtype, device=self.dev)
             self._bufs[key] = b
         return b
+
+    def _cbuf(self, c, name, shape, dtype):
+        """The buffer `name` of context c's pass (tag)."""
+        return self._buf(c["tag"] + ":" + name, shape, dtype)
 
     def _linspace(self, n):
         """torch.linspace(0, 1, n) computed on the host like the reference's CPU path, cached on the device (no host-to-device copy
@@ -583,10 +582,47 @@ class SwitchNeRF:
                 if t is not None and t.is_cuda:
                     t.record_stream(torch.cuda.current_stream())
 
+    def _on_side(self, fn):
+        """fn() on the side stream, behind an event recorded on the launch stream now; returns the event that marks its completion."""
+        # (the shape of EVERY side-stream section: _join_side_outputs.  What fn allocates is allocated on the side stream.)
+        ready = torch.cuda.Event()
+        ready.record()
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ready)
+            fn()
+            done = torch.cuda.Event()
+            done.record()
+        return done
+
+    def _ray_feat(self, c, pe_dir, image_indices):
+        """The per-ray part of layer "2": [PE(dir), appearance embedding] @ W2r + b2 (N_rays x 75) -> c["ray_feat"], c["c_ray"]."""
+        # (one launch: swn_ray_feat_fwd - was cat / embedding lookup / addmm in torch)
+        c["ray_feat"], c["c_ray"] = ops.ray_feat_fwd(pe_dir, self.in_dir, self.p["emb"], image_indices.contiguous(), self.p["l2r.w"], self.p["l2.b"])
+
+    def _l2h_pad(self, forward: bool):
+        """Layer "2" (256 -> 128) zero-padded to 256 (outputs of the forward copy, K of the backward-data copy) for the fused launches."""
+        # (packed here when the fused kernels were switched on after the compute copies were made; refresh_compute_copies keeps it current)
+        d = self.wf if forward else self.wb
+        if "l2h_pad" not in d:
+            d["l2h_pad"] = ops.pack_weights_padded(self.p["l2h.w"].unsqueeze(0), self.dtype, forward, 0, 256)
+        return d["l2h_pad"]
+
+    def _heads_fused(self) -> bool:
+        """The sigma / colour heads inside the tail forward chain's launch (swn.h: heads_raw): rows of at most 1 KiB."""
+        return self.sw["fused_heads"] and self.M in (256, 512) and self.H2 in (128, 256) and self.M * c_esz(self.dtype) <= 1024
+
+    def _group_args(self, c, gather=True):
+        """The local experts' (segment, expert) groups of the row space as launch arguments (rows gathered through the routing permutation)."""
+        kw = dict(n_groups=c["ng"], n_wsets=self.E, group_stride=c["cap"], group_rows=c["counts_flat"], group_rows_clamp=c["cap"])
+        if gather:
+            kw["x_gather"] = c["perm"].view(-1)
+        return kw
+
     def _net_forward_rows(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, row_range):
         """One or more whole model chunks: front chain, gate, routing, expert chain, tail chain, heads -> c["raw"] [P, 4].
         row_range = None: all N*S points; (r0, r1): that row range of the ray-major point grid (ragged evaluation)."""
-        o, dt, dev = ops, self.dtype, self.dev
+        # The driver of the forward phases: _front_forward, _route (every row-space key of the context), _expert_forward_layers, ONE
+        # _experts_forward_* (the mode is chosen here), _tail_forward.
         P = N * S
         if row_range is not None:
             r0, r1 = row_range
@@ -594,38 +630,54 @@ class SwitchNeRF:
             pe = pe[r0:r1]
             sigma_noise = None if sigma_noise is None else sigma_noise[r0:r1]
             routing_override = None if routing_override is None else routing_override[r0:r1]
-        M, E, L, G, H2 = self.M, self.E, self.L, self.G, self.H2
         assert P % seg_tokens == 0, "points must be a multiple of the segment (model chunk) size"
-        n_seg = P // seg_tokens
-        cap = self.capacity(seg_tokens)     # tutel_fast_dispatch.py:210-216
-        if no_batch:        # eval path (apply_on_expert_fn_nobatch): nothing is dropped == a capacity nothing exceeds
-            cap = seg_tokens
-        # capacity_factor = 0 (the reference's dynamic capacity: nothing dropped) outside the no-batch forms: the packed row space, one row
-        # per token (the strided one would hold n_seg * E * seg_tokens rows - E times the saves, masks and perm)
-        dyn = self.cf == 0 and not no_batch
-        if dyn and self.ep is not None:
+        # tutel_fast_dispatch.py:210-216; eval path (apply_on_expert_fn_nobatch): nothing is dropped == a capacity nothing exceeds
+        cap = seg_tokens if no_batch else self.capacity(seg_tokens)
+        if self.cf == 0 and not no_batch and self.ep is not None:
             raise ValueError(DYNCAP_EP_ERROR)
-        c = dict(N=N, S=S, P=P, n_seg=n_seg, cap=cap, seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
+        c = dict(N=N, S=S, P=P, n_seg=P // seg_tokens, cap=cap, seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
         c["pe"], c["pe_dir"] = pe, pe_dir
         # the per-ray half of layer "2" (gather + a 75 x 128 GEMM per ray: one small launch) only needs the direction encoding: on the side
         # stream it runs under the front chain / the router instead of between the routing and the expert launch
         ray_feat_ev = None
         if (self.overlap and self.side is not None and not self.profile and self.ep is None and row_range is None and self._tail_fused()
                 and "l2r.w" in self.p):
-            ev0 = torch.cuda.Event()
-            ev0.record()
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ev0)
-                c["ray_feat"], c["c_ray"] = ops.ray_feat_fwd(pe_dir, self.in_dir, self.p["emb"], image_indices.contiguous(), self.p["l2r.w"],
-                                                             self.p["l2.b"])
-                ray_feat_ev = torch.cuda.Event()
-                ray_feat_ev.record()
-        _b = lambda name, shape, dtype: self._buf(tag + ":" + name, shape, dtype)
-        # ---- front chain: PE -> xyz -> gate MLP
-        c["h0"] = _b("h0", (P, M), dt)
-        c["a1"] = _b("a1", (P, G), dt)
-        c["g"] = _b("g", (P, G), dt)
-        c["m_a1"] = _b("m_a1", (o.chain_mask_words(dt, 1, P, max(M, G, self.KP)),), torch.int32)
+            ray_feat_ev = self._on_side(lambda: self._ray_feat(c, pe_dir, image_indices))
+        gnoise = self._front_forward(c, N, row_range)
+        owner = self._route(c, gnoise, routing_override, no_batch, row_range)
+        layers = self._expert_forward_layers(c)
+        # ---- the expert chain (gathers its rows through perm; ragged groups = (segment, expert)): ONE mode per forward
+        if no_batch and not self._saving and self.ep is not None:
+            self._experts_forward_ep_nobatch(c, layers)
+        elif self.ep is None and c["tail_fused"]:
+            return self._experts_forward_fused(c, layers, pe_dir, image_indices, sigma_noise, ray_feat_ev)
+        elif self.ep is None:
+            self._experts_forward_local(c, layers)
+        elif owner:
+            from . import ep_owner
+            return ep_owner.forward(self, c, layers, pe_dir, image_indices, sigma_noise, self._saving)
+        else:
+            self._experts_forward_ep(c, layers)
+        # ---- per-ray part of layer "2"
+        if ray_feat_ev is not None:        # (issued on the side stream above; this branch: the fused tail was not taken after all)
+            self._join_side_outputs(ray_feat_ev, c["ray_feat"], c["c_ray"])
+        else:
+            self._ray_feat(c, pe_dir, image_indices)
+        rowbias, rpb = c["c_ray"], S
+        if row_range is not None:  # a row range of the point grid: the rows' rays through an explicit per-row gather
+            rowbias, rpb = c["c_ray"].index_select(0, torch.arange(r0, r1, device=self.dev) // S), 1
+            c["ragged"], c["row0"] = True, r0
+        self._tail_forward(c, c["eo"], sigma_noise, rowbias, rpb, combine=(c["row_of_tok"], c["gmax"]))
+        return c
+
+    def _front_forward(self, c, N, row_range):
+        """Front chain PE -> xyz -> gate MLP (c["h0"], c["a1"], c["g"]); returns the gate-noise draw of a training forward (or None)."""
+        o, dt, dev = ops, self.dtype, self.dev
+        P, S, M, G, E = c["P"], c["S"], self.M, self.G, self.E
+        c["h0"] = self._cbuf(c, "h0", (P, M), dt)
+        c["a1"] = self._cbuf(c, "a1", (P, G), dt)
+        c["g"] = self._cbuf(c, "g", (P, G), dt)
+        c["m_a1"] = self._cbuf(c, "m_a1", (o.chain_mask_words(dt, 1, P, max(M, G, self.KP)),), torch.int32)
         sv = self._saving
         c["no_grad"] = not sv
         # (the 64-row kernels re-stream the 320 KB of weights from L2 for every 64 rows - 11.8 GB of L2 reads per 2M-point launch against
@@ -637,28 +689,37 @@ class SwitchNeRF:
                                       save=c["a1"] if sv else None),
                               o.Layer(self.wf["gate1"], self.p["gate1.b"].view(1, G))], c["g"], tag=3, geometry=c["front_geom"] if big else 0,
                     x_features=self.KP if big else 0)
-        # ---- gate + routing
-        gnoise = None
-        if sv and self.gate_noise > 0:       # (training only, like `self.training and self.gate_noise > 0`)
-            if self.gate_noise_draw is not None:      # a supplied draw (tests): [N * S, E] of this pass's point grid; a row range takes its rows
-                draw = self.gate_noise_draw.to(dev, torch.float32)
-                if draw.numel() != N * S * E:
-                    raise ValueError(f"gate_noise_draw holds {draw.numel()} values, this pass needs [{N * S}, {E}] (one row per point)")
-                draw = draw.reshape(N * S, E)
-                gnoise = (draw if row_range is None else draw[row_range[0]:row_range[1]]).contiguous()
-            else:
-                gnoise = torch.randn(P, E, device=dev, dtype=torch.float32)
+        if not (sv and self.gate_noise > 0):       # (training only, like `self.training and self.gate_noise > 0`)
+            return None
+        if self.gate_noise_draw is None:
+            return torch.randn(P, E, device=dev, dtype=torch.float32)
+        # a supplied draw (tests): [N * S, E] of this pass's point grid; a row range takes its rows
+        draw = self.gate_noise_draw.to(dev, torch.float32)
+        if draw.numel() != N * S * E:
+            raise ValueError(f"gate_noise_draw holds {draw.numel()} values, this pass needs [{N * S}, {E}] (one row per point)")
+        draw = draw.reshape(N * S, E)
+        return (draw if row_range is None else draw[row_range[0]:row_range[1]]).contiguous()
+
+    def _route(self, c, gnoise, routing_override, no_batch, row_range):
+        """Gate, routing override, the packed / dyn / want_drops decisions, routing; returns whether the step hands over to ep_owner.py."""
+        # Fills EVERY row-space key of the context: idx, gmax, geom, tail_fused, dyn, loc, counts, perm, tok2row, l_aux, drop_begin / dropped,
+        # group_begin, packed_rows, rows, ng, counts_flat.
+        o, dt, dev, sv = ops, self.dtype, self.dev, self._saving
+        P, n_seg, cap, seg_tokens, M, E = c["P"], c["n_seg"], c["cap"], c["seg_tokens"], self.M, self.E
         c["gates"], c["idx"], c["gmax"], c["stats"] = o.gate_fwd(c["g"], self.p["ln.w"], self.p["ln.b"], self.p["wg"], noise=gnoise,
                                                                  noise_scale=self.gate_noise / E)
         if routing_override is not None:     # tests: inject the oracle's expert choice (near-tie robustness)
             c["idx"] = routing_override.to(dev).int().contiguous()
             c["gmax"] = c["gates"].gather(1, c["idx"].long()[:, None])[:, 0].contiguous()
+        # capacity_factor = 0 (the reference's dynamic capacity: nothing dropped) outside the no-batch forms: the packed row space, one row
+        # per token (the strided one would hold n_seg * E * seg_tokens rows - E times the saves, masks and perm)
+        dyn = c["dyn"] = self.cf == 0 and not no_batch
         packed = (bool(no_batch) and not sv and self.ep is None) or dyn      # (see below: the packed row layout)
         # expert chains (forward here, backward-data in backward_net - the pair shares its ReLU mask layout): the 256-row geometry
         # with phase-shifted row groups as a persistent launch (chain_big.hip, geometry 7 = geometry 4 walking a tile queue) for 256-feature
         # experts in a 16-bit compute dtype once a group holds at least one full tile.  The chain_geom switch picks another one (1: the
         # 64-row kernels, 2 / 4 / 5 / 6: see include/swn.h) - tests.
-        c["geom"] = self.sw["chain_geom"] if (M == 256 and dt != torch.float32 and cap >= 256) else 1
+        c["geom"] = o.expert_geometry(M, dt, cap, self.sw["chain_geom"])
         # the tail inside the expert launch (local experts, standard row space, whole point grid): the expert output never reaches memory
         c["tail_fused"] = (self._tail_fused() and self.ep is None and c["geom"] == 7 and row_range is None
                            and P * M * c_esz(dt) < (1 << 32) - 64)
@@ -667,10 +728,9 @@ class SwitchNeRF:
         owner = ep_owner.eligible(self, c, no_batch, row_range)
         # (the fused tail's list of dropped tokens comes out of the routing launch)
         want_drops = (c["tail_fused"] or owner) and not packed
-        c["dyn"] = dyn
         if dyn:     # the routing writes the packed row space itself (no strided perm, no pack pass); nothing is dropped
-            c["loc"], c["counts"], gb_dyn, c["perm"], c["tok2row"], c["l_aux"] = o.route_top1_packed(c["idx"], c["gmax"], c["gates"],
-                                                                                                   seg_tokens, E, self.bpr)
+            c["loc"], c["counts"], c["group_begin"], c["perm"], c["tok2row"], c["l_aux"] = o.route_top1_packed(c["idx"], c["gmax"], c["gates"],
+                                                                                                             seg_tokens, E, self.bpr)
             if c["tail_fused"]:      # the fused tail's (empty) list of dropped tokens: a zero count, never written
                 key = ("dyn_nodrops", n_seg * E)
                 if key not in self._bufs:
@@ -681,196 +741,190 @@ class SwitchNeRF:
             c["loc"], c["counts"], c["perm"], c["tok2row"], c["l_aux"] = routed[:5]
             if want_drops:
                 c["drop_begin"], c["dropped"] = routed[5], routed[6]
-        # ---- expert chain (gathers its rows through perm; ragged groups = (segment, expert))
-        rows = n_seg * E * cap
-        ng = n_seg * E
         # evaluation without token dropping (apply_on_expert_fn_nobatch, tutel_moe_layer_nobatch.py:237-352): the reference packs the
         # rows contiguously per expert (expert_locations_begin, tutel_fast_dispatch_nobatch.py:24-36).  Same layout here for the
         # inference forward: P rows instead of n_seg * E * seg_tokens, groups addressed through their first row.
-        group_begin = None
-        if dyn:
-            rows = P
-            group_begin = c["group_begin"] = gb_dyn
-        elif packed:
-            rows = P
-            group_begin, c["perm"], c["tok2row"] = o.route_pack(c["idx"], c["loc"], c["counts"], seg_tokens, E)
-            c["group_begin"] = group_begin
+        if packed and not dyn:
+            c["group_begin"], c["perm"], c["tok2row"] = o.route_pack(c["idx"], c["loc"], c["counts"], seg_tokens, E)
         # packed ReLU-mask slots (swn_chain_desc.packed_rows) in the no-drop row space: the masks follow the P rows too (and the persistent
         # launch walks P / 256 + groups tiles instead of groups * seg_tokens / 256; an inference forward on another geometry: no masks)
-        pk = P if (dyn and (sv or c["geom"] in (0, 1, 7))) else 0
-        c["packed_rows"] = pk
-        c["rows"], c["ng"] = rows, ng
+        c["packed_rows"] = P if (dyn and (sv or c["geom"] in (0, 1, 7))) else 0
+        c["rows"], c["ng"] = P if packed else n_seg * E * cap, n_seg * E
         c["counts_flat"] = c["counts"].view(-1)
-        c["saves"] = [_b(f"save{l}", (rows, M), dt) if sv else None for l in range(L - 1)]
-        if pk:
+        return owner
+
+    def _expert_forward_layers(self, c):
+        """The expert chain's save / mask / output buffers of the context's row space and its forward layer list (this rank's experts)."""
+        o, dt, sv, L, M = ops, self.dtype, self._saving, self.L, self.M
+        P, n_seg, cap, rows, ng = c["P"], c["n_seg"], c["cap"], c["rows"], c["ng"]
+        c["saves"] = [self._cbuf(c, f"save{l}", (rows, M), dt) if sv else None for l in range(L - 1)]
+        if c["packed_rows"]:
             nw = o.chain_mask_words_packed(dt, P, ng, M)
         else:
-            nw = max(o.chain_mask_words(dt, ng, cap, M), n_seg * o.chain_mask_words(dt, E, cap, M))    # (expert parallel: one launch per segment)
-        c["masks"] = [_b(f"mask{l}", (nw,), torch.int32) if sv else None for l in range(L - 1)]
-        skips = set(self.cfg["skips"])
-        layers = [o.Layer(self._local_experts(self.wf[f"exp{l}"]), self._local_experts(self.p[f"exp{l}.b"]),
-                          relu=1 if l < L - 1 else 0, skip=(l in skips), save=c["saves"][l] if (sv and l < L - 1) else None,
-                          mask=c["masks"][l] if (sv and l < L - 1) else None) for l in range(L)]
-        c["eo"] = None if c["tail_fused"] else _b("eo", (rows, M), dt)
+            nw = max(o.chain_mask_words(dt, ng, cap, M), n_seg * o.chain_mask_words(dt, self.E, cap, M))    # (expert parallel: one launch per segment)
+        c["masks"] = [self._cbuf(c, f"mask{l}", (nw,), torch.int32) if sv else None for l in range(L - 1)]
+        c["eo"] = None if c["tail_fused"] else self._cbuf(c, "eo", (rows, M), dt)
         self._kernel_sel.update(geom=c["geom"], front_geom=c["front_geom"], tail_fused=bool(c["tail_fused"]))
-        if no_batch and not sv and self.ep is not None:
-            # evaluation without token dropping under expert parallelism (tutel_moe_layer_nobatch.py:308-335): the packed rows of a
-            # segment, expert-major = (destination rank, local expert), travel with UNEQUAL splits (the reference's list_all_to_all);
-            # the owner runs its experts on the (source rank, local expert) groups it received and sends the rows back
-            ep = self.ep
-            _gb, perm_p, c["tok2row"] = o.route_pack(c["idx"], c["loc"], c["counts"], seg_tokens, E)
-            c["row_of_tok"] = c["tok2row"]
-            c["eo"] = _b("eo_packed", (P, M), dt)
-            for s_ in range(n_seg):
-                rs = slice(s_ * seg_tokens, (s_ + 1) * seg_tokens)          # every segment holds exactly seg_tokens packed rows
-                recv, rc = ep.all_to_all_ragged(o.gather_rows(c["h0"], perm_p[rs]), c["counts"][s_].contiguous())
-                out = torch.empty_like(recv)
-                if recv.shape[0]:
-                    gb = (torch.cumsum(rc, 0) - rc).to(torch.int32)
-                    o.mlp_chain(recv, layers, out, n_groups=ep.world * ep.El, n_wsets=ep.El, group_stride=seg_tokens, group_rows=rc,
-                                group_rows_clamp=seg_tokens, tag=1, geometry=c["geom"], group_begin=gb)
-                back, _ = ep.all_to_all_ragged(out, rc, recv_counts=c["counts"][s_].contiguous())
-                c["eo"][rs] = back
-        elif self.ep is None and c["tail_fused"]:
-            # ---- experts + tail in ONE launch (chain_big.hip, tag 7): behind the last expert layer a row is scaled by its gate value and
-            # ReLU'd (the decoded MoE output y), runs through layer "1" and layer "2" (+ the per-ray bias below) and the two heads; y, h1
-            # and h2 are saved in TOKEN order for the backward (a training forward), raw is written in token order; the tokens no expert
-            # kept enter at layer "1" as zero rows (swn_route_dropped).  Replaces: the expert output's round trip through memory, the
-            # 64-row tail chain (which re-streams its 192 KiB of weights from L2 for every 64 rows) and its launch.
-            c["row_of_tok"] = c["tok2row"]
-            if ray_feat_ev is not None:
-                self._join_side_outputs(ray_feat_ev, c["ray_feat"], c["c_ray"])
-            else:
-                c["ray_feat"], c["c_ray"] = o.ray_feat_fwd(pe_dir, self.in_dir, self.p["emb"], image_indices.contiguous(), self.p["l2r.w"], self.p["l2.b"])
-            if "dropped" not in c:
-                c["drop_begin"], c["dropped"] = o.route_dropped(c["idx"], c["loc"], c["counts"], seg_tokens, E, cap)
-            if "l2h_pad" not in self.wf:      # (SWN_FUSED_TAIL switched on after the compute copies were made)
-                self.wf["l2h_pad"] = o.pack_weights_padded(self.p["l2h.w"].unsqueeze(0), dt, True, 0, 256)
-            c["y"] = _b("y", (P, M), dt) if sv else None
-            c["h1"] = _b("h1", (P, M), dt) if sv else None
-            c["h2"] = _b("h2", (P, H2), dt) if sv else None
-            c["raw"] = torch.empty(P, 4, dtype=torch.float32, device=dev)
-            heads = (self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"], sigma_noise, c["raw"])
+        return o.expert_fwd_layers([self._local_experts(self.wf[f"exp{l}"]) for l in range(L)],
+                                   [self._local_experts(self.p[f"exp{l}.b"]) for l in range(L)], set(self.cfg["skips"]), c["saves"], c["masks"])
 
-            def run_experts(save=sv):
-                lys = [o.Layer(ly.w, ly.b, relu=ly.relu, skip=ly.skip, save=ly.save if save else None, mask=ly.mask if save else None)
-                       for ly in layers]
-                lys[-1].save = c["y"] if save else None
-                lys += [o.Layer(self.wf["l1"], self.p["l1.b"].view(1, M), save=c["h1"] if save else None),
-                        o.Layer(self.wf["l2h_pad"], None, relu=1, rowbias=c["c_ray"], rows_per_bias=S)]
-                o.mlp_chain(c["h0"], lys, c["h2"] if save else None, n_groups=ng, n_wsets=E, group_stride=cap, group_rows=c["counts_flat"],
-                            group_rows_clamp=cap, x_gather=c["perm"].view(-1), tag=7, geometry=7, heads=heads, group_begin=group_begin,
-                            tail=(L, c["gmax"], c["drop_begin"], c["dropped"], H2), packed_rows=pk)
-            with self._timed("expert_fwd"):
-                run_experts()
-            if self.profile:      # bench.py: the launch again on this step's live buffers, its save-free form, and the expert layers ALONE
-                def expert_gemm():    # (the grouped GEMM without the tail: tag 1, into a scratch output - what round 1-3's figure measured)
-                    o.mlp_chain(c["h0"], [o.Layer(ly.w, ly.b, relu=ly.relu, skip=ly.skip) for ly in layers], _b("eo_probe", (rows, M), dt),
-                                n_groups=ng, n_wsets=E, group_stride=cap, group_rows=c["counts_flat"], group_rows_clamp=cap,
-                                x_gather=c["perm"].view(-1), tag=1, geometry=7, group_begin=group_begin, packed_rows=pk)
-                c["_relaunch"] = {"expert_fwd": run_experts, "expert_fwd_nosave": lambda: run_experts(False), "expert_gemm_nosave": expert_gemm}
-            return c
-        elif self.ep is None:
-            c["row_of_tok"] = c["tok2row"]
+    def _experts_forward_ep_nobatch(self, c, layers):
+        """Expert-parallel evaluation without token dropping, segment by segment, into c["eo"] (packed rows)."""
+        # evaluation without token dropping under expert parallelism (tutel_moe_layer_nobatch.py:308-335): the packed rows of a
+        # segment, expert-major = (destination rank, local expert), travel with UNEQUAL splits (the reference's list_all_to_all);
+        # the owner runs its experts on the (source rank, local expert) groups it received and sends the rows back
+        o, ep, seg_tokens = ops, self.ep, c["seg_tokens"]
+        _gb, perm_p, c["tok2row"] = o.route_pack(c["idx"], c["loc"], c["counts"], seg_tokens, self.E)
+        c["row_of_tok"] = c["tok2row"]
+        c["eo"] = self._buf(c["tag"] + ":eo_packed", (c["P"], self.M), self.dtype)
+        for s_ in range(c["n_seg"]):
+            rs = slice(s_ * seg_tokens, (s_ + 1) * seg_tokens)          # every segment holds exactly seg_tokens packed rows
+            recv, rc = ep.all_to_all_ragged(o.gather_rows(c["h0"], perm_p[rs]), c["counts"][s_].contiguous())
+            out = torch.empty_like(recv)
+            if recv.shape[0]:
+                gb = (torch.cumsum(rc, 0) - rc).to(torch.int32)
+                o.mlp_chain(recv, layers, out, n_groups=ep.world * ep.El, n_wsets=ep.El, group_stride=seg_tokens, group_rows=rc,
+                            group_rows_clamp=seg_tokens, tag=1, geometry=c["geom"], group_begin=gb)
+            back, _ = ep.all_to_all_ragged(out, rc, recv_counts=c["counts"][s_].contiguous())
+            c["eo"][rs] = back
 
-            def run_experts(lys=layers):
-                o.mlp_chain(c["h0"], lys, c["eo"], n_groups=ng, n_wsets=E, group_stride=cap, group_rows=c["counts_flat"],
-                            group_rows_clamp=cap, x_gather=c["perm"].view(-1), tag=1, geometry=c["geom"], group_begin=group_begin,
-                            packed_rows=pk)
-            with self._timed("expert_fwd"):
-                run_experts()
-            if self.profile:      # bench.py: the same launch again, back to back, on this step's live buffers (and its save-free form)
-                c["_relaunch"] = {"expert_fwd": run_experts,
-                                  "expert_fwd_nosave": lambda: run_experts([o.Layer(ly.w, ly.b, relu=ly.relu, skip=ly.skip) for ly in layers])}
-        else:
-            # expert parallel, pipelined per routing segment (parallel.ExpertParallel), KEPT ROWS ONLY: the kept rows of segment s, packed in
-            # (expert, slot) order = payload order (destination rank, local expert, slot) -> unequal-split all-to-all on the side stream ->
-            # the local experts run on the (source rank, local expert) groups (first rows from a device prefix sum) -> all-to-all back into
-            # the packed row space the combine gathers from.  The dispatch of segment s + 1 and the return of segment s - 1 travel while
-            # the experts work on segment s.  One host read of the counts per forward pass (ExpertParallel.plan).
-            if owner:
-                return ep_owner.forward(self, c, pe_dir, image_indices, sigma_noise, sv)
-            ep = self.ep
-            W, El = ep.world, ep.El
-            ngs = W * El
-            recv_counts = ep.exchange_counts(c["counts"], cap, self.side)()            # [n_seg, W * E_local], the expert kernels' group order
-            c["ep_counts"] = recv_counts
-            c["ep_padded"] = ep.use_padded(E * cap * M * c_esz(dt))
-            if c["ep_padded"]:
-                # the reference's layout (tutel_moe_layer_nobatch.py:157): every (expert, capacity slot) of a segment travels - empty slots
-                # as zero rows - with EQUAL splits.  The row spaces are the standard ones (perm / tok2row of swn_route_top1, group g at row
-                # g * cap), nothing is read on the host: the step can be captured into a hipGraph, collectives included.
-                perm_p, c["row_of_tok"] = c["perm"].view(-1), c["tok2row"]
-                seg_rows = E * cap
-                pl = dict(in_splits=[[El * cap] * W] * n_seg, out_splits=[[El * cap] * W] * n_seg,
-                          send_off=[s_ * seg_rows for s_ in range(n_seg + 1)], recv_off=[s_ * seg_rows for s_ in range(n_seg + 1)])
-                key = ("ep_begin_padded", n_seg * ngs, cap)
-                if key not in self._bufs:
-                    self._bufs[key] = (torch.arange(n_seg * ngs, device=dev, dtype=torch.int32) * cap).contiguous()
-                c["ep_begin"] = self._bufs[key]
-            else:
-                kept = c["counts"].clamp(max=cap)
-                idx_kept = torch.where(c["loc"] < cap, c["idx"], torch.full_like(c["idx"], -1))
-                _gb, perm_p, c["row_of_tok"] = o.route_pack(idx_kept, c["loc"], kept, seg_tokens, E)     # packed row space of this rank's rows
-                pl = ep.plan(kept, recv_counts)
-                flat_rc = recv_counts.reshape(-1)
-                c["ep_begin"] = (torch.cumsum(flat_rc, 0, dtype=torch.int32) - flat_rc).contiguous()      # first row of every received group
-            c["ep_perm"], c["ep_plan"] = perm_p, pl
-            so, ro = pl["send_off"], pl["recv_off"]
-            xr = _b("ep_x", (rows, M), dt)                                  # received rows of all segments (also the first layer's
-            send = xr if ep.local else _b("ep_send_x", (rows, M), dt)         # weight-gradient operand)
-            eo_r = c["eo"] if ep.local else _b("ep_eo", (rows, M), dt)        # expert outputs in the received row space
-            wseg = o.chain_mask_words(dt, E, cap, M)
-            c["ep_mask_words"] = wseg
-
-            def issue(s_):
-                o.gather_rows(c["h0"], perm_p[so[s_]:so[s_ + 1]], send[so[s_]:so[s_ + 1]])
-                return ep.all_to_all_v(send[so[s_]:so[s_ + 1]], pl["in_splits"][s_], xr[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], self.side)
-            with self._timed("expert_fwd"):
-                pend = issue(0)
-                returns = []
-                for s_ in range(n_seg):
-                    nxt = issue(s_ + 1) if s_ + 1 < n_seg else None
-                    pend()
-                    layers_s = [o.Layer(ly.w, ly.b, relu=ly.relu, skip=ly.skip, save=ly.save,
-                                        mask=None if ly.mask is None else ly.mask[s_ * wseg:(s_ + 1) * wseg]) for ly in layers]
-                    if ro[s_ + 1] > ro[s_]:
-                        o.mlp_chain(xr, layers_s, eo_r, n_groups=ngs, n_wsets=El, group_stride=cap, group_rows=recv_counts[s_],
-                                    group_rows_clamp=cap, tag=1, geometry=c["geom"], group_begin=c["ep_begin"][s_ * ngs:(s_ + 1) * ngs])
-                    returns.append(ep.all_to_all_v(eo_r[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], c["eo"][so[s_]:so[s_ + 1]],
-                                                   pl["in_splits"][s_], self.side))
-                    pend = nxt
-                for wait in returns:
-                    wait()
-            c["ep_x"] = xr
-        # ---- per-ray part of layer "2": [PE(dir), appearance embedding] @ W2r + b2   (N_rays x 75, host-side torch)
-        # (one launch: swn_ray_feat_fwd - was cat / embedding lookup / addmm in torch)
-        if ray_feat_ev is not None:        # (issued on the side stream above; this branch: the fused tail was not taken after all)
+    def _experts_forward_fused(self, c, layers, pe_dir, image_indices, sigma_noise, ray_feat_ev):
+        """Local experts + tail + heads in ONE launch -> c["raw"]; returns the finished context."""
+        # ---- experts + tail in ONE launch (chain_big.hip, tag 7): behind the last expert layer a row is scaled by its gate value and
+        # ReLU'd (the decoded MoE output y), runs through layer "1" and layer "2" (+ the per-ray bias below) and the two heads; y, h1
+        # and h2 are saved in TOKEN order for the backward (a training forward), raw is written in token order; the tokens no expert
+        # kept enter at layer "1" as zero rows (swn_route_dropped).  Replaces: the expert output's round trip through memory, the
+        # 64-row tail chain (which re-streams its 192 KiB of weights from L2 for every 64 rows) and its launch.
+        o, dt, sv = ops, self.dtype, self._saving
+        P, S, M, H2, L = c["P"], c["S"], self.M, self.H2, self.L
+        c["row_of_tok"] = c["tok2row"]
+        if ray_feat_ev is not None:
             self._join_side_outputs(ray_feat_ev, c["ray_feat"], c["c_ray"])
         else:
-            c["ray_feat"], c["c_ray"] = o.ray_feat_fwd(pe_dir, self.in_dir, self.p["emb"], image_indices.contiguous(), self.p["l2r.w"], self.p["l2.b"])
-        # ---- tail chain.  Its input load IS the combine: rows gathered from the expert output through tok2row, scaled by
+            self._ray_feat(c, pe_dir, image_indices)
+        if "dropped" not in c:
+            c["drop_begin"], c["dropped"] = o.route_dropped(c["idx"], c["loc"], c["counts"], c["seg_tokens"], self.E, c["cap"])
+        w2 = self._l2h_pad(True)
+        c["y"] = self._cbuf(c, "y", (P, M), dt) if sv else None
+        c["h1"] = self._cbuf(c, "h1", (P, M), dt) if sv else None
+        c["h2"] = self._cbuf(c, "h2", (P, H2), dt) if sv else None
+        c["raw"] = torch.empty(P, 4, dtype=torch.float32, device=self.dev)
+        heads = (self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"], sigma_noise, c["raw"])
+        last = layers[-1]
+        full = layers[:-1] + [o.Layer(last.w, last.b, relu=last.relu, skip=last.skip, save=c["y"]),
+                              o.Layer(self.wf["l1"], self.p["l1.b"].view(1, M), save=c["h1"]),
+                              o.Layer(w2, None, relu=1, rowbias=c["c_ray"], rows_per_bias=S)]
+        grp, extra = self._group_args(c), dict(group_begin=c.get("group_begin"), packed_rows=c["packed_rows"])
+
+        def run_experts(save=sv):
+            o.mlp_chain(c["h0"], full if save else [ly.without_saves() for ly in full], c["h2"] if save else None, tag=7, geometry=7,
+                        heads=heads, tail=(L, c["gmax"], c["drop_begin"], c["dropped"], H2), **grp, **extra)
+        with self._timed("expert_fwd"):
+            run_experts()
+        if self.profile:      # bench.py: the launch again on this step's live buffers, its save-free form, and the expert layers ALONE
+            def expert_gemm():    # (the grouped GEMM without the tail: tag 1, into a scratch output - what round 1-3's figure measured)
+                o.mlp_chain(c["h0"], [ly.without_saves() for ly in layers], self._cbuf(c, "eo_probe", (c["rows"], M), dt), tag=1, geometry=7, **grp, **extra)
+            c["_relaunch"] = {"expert_fwd": run_experts, "expert_fwd_nosave": lambda: run_experts(False), "expert_gemm_nosave": expert_gemm}
+        return c
+
+    def _experts_forward_local(self, c, layers):
+        """The local experts as their own launch (tag 1) into c["eo"]; the tail chain follows as a separate launch."""
+        o = ops
+        c["row_of_tok"] = c["tok2row"]
+        grp = self._group_args(c)
+
+        def run_experts(lys=layers):
+            o.mlp_chain(c["h0"], lys, c["eo"], tag=1, geometry=c["geom"], group_begin=c.get("group_begin"), packed_rows=c["packed_rows"], **grp)
+        with self._timed("expert_fwd"):
+            run_experts()
+        if self.profile:      # bench.py: the same launch again, back to back, on this step's live buffers (and its save-free form)
+            c["_relaunch"] = {"expert_fwd": run_experts, "expert_fwd_nosave": lambda: run_experts([ly.without_saves() for ly in layers])}
+
+    def _experts_forward_ep(self, c, layers):
+        """Expert parallel, pipelined per routing segment, kept rows or padded rows, into c["eo"]."""
+        # expert parallel, pipelined per routing segment (parallel.ExpertParallel), KEPT ROWS ONLY: the kept rows of segment s, packed in
+        # (expert, slot) order = payload order (destination rank, local expert, slot) -> unequal-split all-to-all on the side stream ->
+        # the local experts run on the (source rank, local expert) groups (first rows from a device prefix sum) -> all-to-all back into
+        # the packed row space the combine gathers from.  The dispatch of segment s + 1 and the return of segment s - 1 travel while
+        # the experts work on segment s.  One host read of the counts per forward pass (ExpertParallel.plan).
+        o, dt, dev, ep = ops, self.dtype, self.dev, self.ep
+        n_seg, cap, rows, M, E = c["n_seg"], c["cap"], c["rows"], self.M, self.E
+        W, El = ep.world, ep.El
+        ngs = W * El
+        recv_counts = ep.exchange_counts(c["counts"], cap, self.side)()            # [n_seg, W * E_local], the expert kernels' group order
+        c["ep_counts"] = recv_counts
+        c["ep_padded"] = ep.use_padded(E * cap * M * c_esz(dt))
+        if c["ep_padded"]:
+            # the reference's layout (tutel_moe_layer_nobatch.py:157): every (expert, capacity slot) of a segment travels - empty slots
+            # as zero rows - with EQUAL splits.  The row spaces are the standard ones (perm / tok2row of swn_route_top1, group g at row
+            # g * cap), nothing is read on the host: the step can be captured into a hipGraph, collectives included.
+            perm_p, c["row_of_tok"] = c["perm"].view(-1), c["tok2row"]
+            seg_rows = E * cap
+            pl = dict(in_splits=[[El * cap] * W] * n_seg, out_splits=[[El * cap] * W] * n_seg,
+                      send_off=[s_ * seg_rows for s_ in range(n_seg + 1)], recv_off=[s_ * seg_rows for s_ in range(n_seg + 1)])
+            key = ("ep_begin_padded", n_seg * ngs, cap)
+            if key not in self._bufs:
+                self._bufs[key] = (torch.arange(n_seg * ngs, device=dev, dtype=torch.int32) * cap).contiguous()
+            c["ep_begin"] = self._bufs[key]
+        else:
+            kept = c["counts"].clamp(max=cap)
+            idx_kept = torch.where(c["loc"] < cap, c["idx"], torch.full_like(c["idx"], -1))
+            _gb, perm_p, c["row_of_tok"] = o.route_pack(idx_kept, c["loc"], kept, c["seg_tokens"], E)     # packed row space of this rank's rows
+            pl = ep.plan(kept, recv_counts)
+            flat_rc = recv_counts.reshape(-1)
+            c["ep_begin"] = (torch.cumsum(flat_rc, 0, dtype=torch.int32) - flat_rc).contiguous()      # first row of every received group
+        c["ep_perm"], c["ep_plan"] = perm_p, pl
+        so, ro = pl["send_off"], pl["recv_off"]
+        xr = self._cbuf(c, "ep_x", (rows, M), dt)                                  # received rows of all segments (also the first layer's
+        send = xr if ep.local else self._cbuf(c, "ep_send_x", (rows, M), dt)         # weight-gradient operand)
+        eo_r = c["eo"] if ep.local else self._cbuf(c, "ep_eo", (rows, M), dt)        # expert outputs in the received row space
+        wseg = o.chain_mask_words(dt, E, cap, M)
+        c["ep_mask_words"] = wseg
+
+        def issue(s_):
+            o.gather_rows(c["h0"], perm_p[so[s_]:so[s_ + 1]], send[so[s_]:so[s_ + 1]])
+            return ep.all_to_all_v(send[so[s_]:so[s_ + 1]], pl["in_splits"][s_], xr[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], self.side)
+        with self._timed("expert_fwd"):
+            pend = issue(0)
+            returns = []
+            for s_ in range(n_seg):
+                nxt = issue(s_ + 1) if s_ + 1 < n_seg else None
+                pend()
+                if ro[s_ + 1] > ro[s_]:
+                    o.mlp_chain(xr, [ly.with_mask_words(s_ * wseg, (s_ + 1) * wseg) for ly in layers], eo_r, n_groups=ngs, n_wsets=El,
+                                group_stride=cap, group_rows=recv_counts[s_], group_rows_clamp=cap, tag=1, geometry=c["geom"],
+                                group_begin=c["ep_begin"][s_ * ngs:(s_ + 1) * ngs])
+                returns.append(ep.all_to_all_v(eo_r[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], c["eo"][so[s_]:so[s_ + 1]],
+                                               pl["in_splits"][s_], self.side))
+                pend = nxt
+            for wait in returns:
+                wait()
+        c["ep_x"] = xr
+
+    def _tail_forward(self, c, x, sigma_noise, rowbias, rows_per_bias, combine=None):
+        """Layer "1" -> layer "2" (+ per-ray bias) -> heads -> c["raw"] over the rows x; combine = (row_of_tok, gate): MoE form, None: dense."""
+        # ---- tail chain.  (MoE form) Its input load IS the combine: rows gathered from the expert output through tok2row, scaled by
         # the gate value, ReLU'd (dropped tokens -> zero rows) and saved as y;  then layer "1" -> layer "2" (+ per-ray bias)
         # The sigma / colour heads run inside that launch (swn.h: heads_raw): sigma from the staged y tile, colour from the h2 tile.  A
         # training forward still writes y, h1 and h2 (the backward reads them); an inference forward writes nothing but raw.
-        fused = self.sw["fused_heads"] and M in (256, 512) and H2 in (128, 256) and M * c_esz(dt) <= 1024      # (rows of at most 1 KiB)
+        o, dt, sv = ops, self.dtype, self._saving
+        P, M, H2 = c["P"], self.M, self.H2
+        fused = self._heads_fused()
         keep = sv or not fused
-        c["y"] = _b("y", (P, M), dt) if keep else None
-        c["h1"] = _b("h1", (P, M), dt) if sv else None
-        c["h2"] = _b("h2", (P, H2), dt) if keep else None
-        c["raw"] = torch.empty(P, 4, dtype=torch.float32, device=dev) if fused else None
-        rowbias, rpb = c["c_ray"], S
-        if row_range is not None:  # a row range of the point grid: the rows' rays through an explicit per-row gather
-            rowbias, rpb = c["c_ray"].index_select(0, torch.arange(r0, r1, device=dev) // S), 1
-            c["ragged"], c["row0"] = True, r0
-        o.mlp_chain(c["eo"], [o.Layer(self.wf["l1"], self.p["l1.b"].view(1, M), save=c["h1"] if sv else None),
-                              o.Layer(self.wf["l2h"], None, relu=1, rowbias=rowbias, rows_per_bias=rpb)], c["h2"],
-                    group_stride=P, x_gather=c["row_of_tok"], x_save=c["y"], x_scale=c["gmax"], x_relu=True, tag=4,
-                    heads=(self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"], sigma_noise, c["raw"]) if fused else None)
+        kw = {}
+        if combine is not None:
+            c["y"] = self._cbuf(c, "y", (P, M), dt) if keep else None
+            kw = dict(x_gather=combine[0], x_save=c["y"], x_scale=combine[1], x_relu=True)
+        c["h1"] = self._cbuf(c, "h1", (P, M), dt) if sv else None
+        c["h2"] = self._cbuf(c, "h2", (P, H2), dt) if keep else None
+        c["raw"] = torch.empty(P, 4, dtype=torch.float32, device=self.dev) if fused else None
+        o.mlp_chain(x, [o.Layer(self.wf["l1"], self.p["l1.b"].view(1, M), save=c["h1"] if sv else None),
+                        o.Layer(self.wf["l2h"], None, relu=1, rowbias=rowbias, rows_per_bias=rows_per_bias)], c["h2"], group_stride=P, tag=4,
+                    heads=(self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"], sigma_noise, c["raw"]) if fused else None,
+                    **kw)
         if not fused:      # ---- heads as their own launch (SWN_NO_FUSED_HEADS=1: rounds 1-2)
             c["raw"] = o.heads_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                    sigma_noise)
-        return c
 
     # ------------------------------------------------------------------------------------------ backward
     def backward(self, c, d_rgb, d_laux):
@@ -902,27 +956,62 @@ class SwitchNeRF:
         """First half of backward_net (see there); returns the state backward_net_b continues from.  join_side: the launch stream
         waits for the expert weight gradients before returning (they run on the side stream otherwise and are joined at the end of
         the second half)."""
-        o, dt = ops, self.dtype
+        # The driver of the backward phases: _heads_backward (heads + per-ray), _tail_backward, ONE _experts_backward_* (the mode is chosen
+        # here), _expert_wgrads, then the state dict.
         if c.get("no_grad"):
             raise RuntimeError("this context comes from an inference forward (training=False): nothing was saved for the backward")
         assert c.get("parts") is None, "ragged contexts go through backward_net"
         if c.get("ep_owner") is not None:      # expert parallelism with the tail on the expert's rank
             from . import ep_owner
             return ep_owner.backward_a(self, c, d_raw, d_laux)
-        N, S, P, n_seg, cap, seg_tokens = c["N"], c["S"], c["P"], c["n_seg"], c["cap"], c["seg_tokens"]
-        M, E, L, G, H2 = self.M, self.E, self.L, self.G, self.H2
-        g = self.g
-        rows, ng = c["rows"], c["ng"]
-        _b = lambda name, shape, dtype: self._buf(c["tag"] + ":" + name, shape, dtype)
         # the tail's two backward layers and the combine backward in FRONT of the expert backward chain, one launch (chain_big.hip, tag 8):
         # pairs with the fused forward (its list of dropped tokens); SWN_FUSED_TAIL_BWD=0 keeps the two launches
         fused_bwd = bool(c.get("tail_fused")) and self.ep is None and self.sw["fused_tail_bwd"]
         # ... which also forms the sigma head's weight gradient where it reads y anyway (swn_chain_desc.comb_dwsig): the heads' backward
         # launch then runs without y - 512 bytes per point less (SWN_FUSED_DWSIG=0: from y in the heads' launch, as before)
-        fused_dws = fused_bwd and M == 256 and self.sw["fused_dwsig"]
-        y_heads = None if fused_dws else c["y"]
+        fused_dws = fused_bwd and self.M == 256 and self.sw["fused_dwsig"]
         self._kernel_sel.update(fused_backward=fused_bwd, comb_dwsig=fused_dws)
+        b = dict(fused_bwd=fused_bwd, fused_dws=fused_dws)
+        b["dh2"], b["dsig"], b["dc_ray"], side_small = self._heads_backward(c, d_raw, None if fused_dws else c["y"])
+        self._tail_backward(c, b)
+        if self.ep is not None:
+            w = self._experts_backward_ep(c, b)
+        elif fused_bwd:
+            w = self._experts_backward_fused(c, b)
+        else:
+            w = self._experts_backward_local(c, b)
+        side_done = None
+        if self.overlap and self.side is not None and not self.profile and not join_side:
+            # independent of everything that follows (they only read the saved activations / dZ and write their own
+            # gradient slices): run them on the side stream, join before Adam
+            side_done = self._on_side(lambda: self._expert_wgrads(c, w))
+        else:
+            with self._timed("expert_wgrad"):
+                self._expert_wgrads(c, w)
+            if self.profile and "_relaunch" in c:
+                c["_relaunch"]["expert_wgrad"] = lambda: self._expert_wgrads(c, w)        # (accumulates into the gradient buffer again: timing only)
+        if side_small is not None and side_done is None:      # (no expert weight gradients behind it on the side stream: join here)
+            torch.cuda.current_stream().wait_event(side_small)
+        return dict(c=c, d_laux=d_laux, dgmax=b["dgmax"], dx=w["dx"], dout=b["dout"], returns=w["returns"], tail_jobs=b["tail_jobs"],
+                    nsp=b["nsp"], side_done=side_done,
+                    keep=(b["dc_ray"], b["dh2"], b["dsig"]))      # (keep: tensors the side stream reads stay allocated to the join)
+
+    def _ray_level_grads(self, c, dc_ray):
+        """The tiny per-ray GEMM's parameter gradients (layer "2"'s ray half, its bias) and the appearance embedding's, from dc_ray."""
+        o, g = ops, self.g
+        if dc_ray.shape[1] in (64, 128, 256) and c["ray_feat"].shape[1] <= 256:      # split over the rays + ordered reduce (one launch)
+            o.ray_feat_wgrad(c["ray_feat"], dc_ray, g["l2r.w"], g["l2.b"])
+        else:
+            g["l2r.w"].addmm_(c["ray_feat"].t(), dc_ray)
+            g["l2.b"].add_(dc_ray.sum(0))
+        d_feat_emb = dc_ray @ self.p["l2r.w"][self.in_dir:].t()
+        o.emb_grad(d_feat_emb, c["image_indices"].contiguous(), g["emb"])        # (rays added in order: torch's index_add_ uses atomics)
+
+    def _heads_backward(self, c, d_raw, y_heads):
+        """Heads backward and the per-ray gradients; returns (dh2, dsig, dc_ray, the side stream's event or None)."""
         # per-ray bias gradient (the column sums of a ray's dh2 rows: from the heads' launch) and the tiny per-ray GEMM's parameters
+        o, g = ops, self.g
+        N, S, P, H2 = c["N"], c["S"], c["P"], self.H2
         if c.get("ragged"):      # a row range of the point grid: rays may be cut at either end - per-ray sums through the rows' ray index
             dh2, dsig = o.heads_bwd(y_heads, c["h2"], self.p["color.w"], c["raw"], d_raw, g["sigma.w"], g["sigma.b"], g["color.w"],
                                     g["color.b"])
@@ -931,174 +1020,151 @@ class SwitchNeRF:
         else:
             dh2, dsig, dc_ray = o.heads_bwd(y_heads, c["h2"], self.p["color.w"], c["raw"], d_raw, g["sigma.w"], g["sigma.b"], g["color.w"],
                                             g["color.b"], rows_per_group=S)
-        def ray_level():
-            if dc_ray.shape[1] in (64, 128, 256) and c["ray_feat"].shape[1] <= 256:      # split over the rays + ordered reduce (one launch)
-                o.ray_feat_wgrad(c["ray_feat"], dc_ray, g["l2r.w"], g["l2.b"])
-            else:
-                g["l2r.w"].addmm_(c["ray_feat"].t(), dc_ray)
-                g["l2.b"].add_(dc_ray.sum(0))
-            d_feat_emb = dc_ray @ self.p["l2r.w"][self.in_dir:].t()
-            o.emb_grad(d_feat_emb, c["image_indices"].contiguous(), g["emb"])        # (rays added in order: torch's index_add_ uses atomics)
         # The per-ray work (layer "2"'s ray half and the appearance embedding: three small launches + a reduce, ~0.1 ms in which 10-30
         # workgroups hold the chip) goes to the SIDE stream: it only needs dc_ray and writes gradient slices nobody else touches, so it
         # runs under the expert backward launch that follows (whose resident workgroups pick the few late CUs up through the tile queue);
         # joined with the expert weight gradients (same stream) or at the end of this half.  SWN_NO_OVERLAP=1: on the launch stream.
         side_small = None
         if self.overlap and self.side is not None and not self.profile and not c.get("ragged") and self.ep is None:
-            ready_small = torch.cuda.Event()
-            ready_small.record()
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ready_small)
-                ray_level()
-                side_small = torch.cuda.Event()
-                side_small.record()
+            side_small = self._on_side(lambda: self._ray_level_grads(c, dc_ray))
         else:
-            ray_level()
+            self._ray_level_grads(c, dc_ray)
+        return dh2, dsig, dc_ray, side_small
+
+    def _tail_backward(self, c, b):
+        """Tail backward (fused backward: its buffers only); adds dh1, dout, dgmax, nsp and the tail's weight-gradient jobs to b."""
         # tail backward chain: dh2 -> dh1 -> dy
         # ... with the combine backward (the sigma head's rank-1 term, the ReLU mask of y, the gate gradient, the gate scaling) applied
         # in the write-out of the last layer: dy itself never reaches memory
-        dh1 = _b("dh1", (P, M), dt)
-        dout = None if fused_bwd else _b("dy", (P, M), dt)
-        if fused_bwd:
-            dgmax = _b("dgmax", (P,), torch.float32)
-            if "l2h_pad" not in self.wb:
-                self.wb["l2h_pad"] = o.pack_weights_padded(self.p["l2h.w"].unsqueeze(0), dt, False, 0, 256)
+        o, dt = ops, self.dtype
+        P, M, H2, g = c["P"], self.M, self.H2, self.g
+        dh2, dsig = b["dh2"], b["dsig"]
+        dh1 = self._cbuf(c, "dh1", (P, M), dt)
+        dout = None if b["fused_bwd"] else self._cbuf(c, "dy", (P, M), dt)
+        if b["fused_bwd"]:
+            dgmax = self._cbuf(c, "dgmax", (P,), torch.float32)
+            self._l2h_pad(False)
         elif M * dout.element_size() <= 1024:      # (a row's 16-byte chunks must fit one wavefront: everything but fp32 rows of 512)
-            dgmax = _b("dgmax", (P,), torch.float32)
+            dgmax = self._cbuf(c, "dgmax", (P,), torch.float32)
             tg = self.sw["tail_geom"] if self._tail_big() else 0
             o.mlp_chain(dh2, [o.Layer(self.wb["l2h_pad" if tg >= 6 else "l2h"], None, save=dh1), o.Layer(self.wb["l1"], None)], dout, tag=5,
                         combine=(c["y"], dsig, self.p["sigma.w"], c["gmax"], dgmax), geometry=tg, x_features=H2 if tg >= 6 else 0)
         else:
             o.mlp_chain(dh2, [o.Layer(self.wb["l2h"], None, save=dh1), o.Layer(self.wb["l1"], None)], dout, tag=5)
             dout, dgmax = o.combine_bwd(dout, c["y"], dsig, self.p["sigma.w"], c["gmax"])
-        nsp = max(1, min(256, P // 1024))          # row splits of the dense weight-gradient GEMMs: one workgroup per CU also at the
+        b["nsp"] = max(1, min(256, P // 1024))     # row splits of the dense weight-gradient GEMMs: one workgroup per CU also at the
                                                    # per-GPU batch of an 8-GPU run (262144 points)
-        ep = self.ep
-        if ep is not None:      # the rows of the first segment travel to their experts while the tail's weight gradients run
-            pl, perm_p = c["ep_plan"], c["ep_perm"]
-            so, ro = pl["send_off"], pl["recv_off"]
-            dr = _b("ep_d", (rows, M), dt)
-            dsend = dr if ep.local else _b("ep_send_d", (rows, M), dt)
+        b["dh1"], b["dout"], b["dgmax"] = dh1, dout, dgmax
+        b["tail_jobs"] = [(c["h1"], dh2, g["l2h.w"].view(1, M, H2), None), (c["y"], dh1, g["l1.w"].view(1, M, M), g["l1.b"].view(1, M))]
 
-            def issue_b(s_):
-                o.gather_rows(dout, perm_p[so[s_]:so[s_ + 1]], dsend[so[s_]:so[s_ + 1]])
-                return ep.all_to_all_v(dsend[so[s_]:so[s_ + 1]], pl["in_splits"][s_], dr[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], self.side)
-            pend = issue_b(0)
+    def _tail_wgrads_if_large(self, c, b):
+        """The tail layers' weight gradients as their own launch, at the full batch only."""
         # The weight gradients of the two tail layers: at small batches (the per-GPU share of a strong-scaling run) they go out together
         # with the front layers' at the end - one balanced launch + one reduction for all five dense layers (2.39 against 2.42 ms per
         # step at 1024 rays); at the full batch two launches are faster (15.15 against 15.30 ms: the tail operands are the most recently
         # written tensors when their launch follows the tail backward directly).  Measured on one box, scripts/ab_env.sh.
-        tail_jobs = [(c["h1"], dh2, g["l2h.w"].view(1, M, H2), None), (c["y"], dh1, g["l1.w"].view(1, M, M), g["l1.b"].view(1, M))]
-        if P > (1 << 19) and not fused_bwd:      # (fused backward: dh1 comes out of the expert launch - the tail's weight gradients follow it)
-            self._dense_wgrads(tail_jobs, nsp)
-            tail_jobs = []
-        # expert backward chain
-        dz = [_b(f"dz{l}", (rows, M), dt) for l in range(L - 1)]     # dz[L-1] = dout through perm: never materialised
-        dx = _b("dx", (rows, M), dt)
-        skip_l = list(self.cfg["skips"])[0] if len(self.cfg["skips"]) else None
-        bl = []
-        for i in range(L):
-            l = L - 1 - i
-            bl.append(o.Layer(self._local_experts(self.wb[f"exp{l}"]), None, relu=2 if l > 0 else 0,
-                              mask=c["masks"][l - 1] if l > 0 else None, save=dz[l - 1] if l > 0 else None))
-        n_loc = E if ep is None else ep.El
-        grp_rows = c["counts_flat"] if ep is None else c["ep_counts"]
-        if ep is None and fused_bwd:
-            perm = c["perm"].view(-1)
-            x_first, dz_last = c["h0"], _b("dz_last", (rows, M), dt)      # the last expert layer's dZ in the row space (the combine's output)
+        # (fused backward: dh1 comes out of the expert launch - the tail's weight gradients follow it)
+        if c["P"] > (1 << 19):
+            self._dense_wgrads(b["tail_jobs"], b["nsp"])
+            b["tail_jobs"] = []
 
-            dws_dst = [g["sigma.w"].view(-1) if fused_dws else None]
+    def _expert_backward_layers(self, c):
+        """(dz, dx, backward layer list, the skip's y_add) of the expert backward chain in the context's row space."""
+        dt, L, M, rows = self.dtype, self.L, self.M, c["rows"]
+        dz = [self._cbuf(c, f"dz{l}", (rows, M), dt) for l in range(L - 1)]     # dz[L-1] = dout through perm: never materialised
+        dx = self._cbuf(c, "dx", (rows, M), dt)
+        bl = ops.expert_bwd_layers([self._local_experts(self.wb[f"exp{l}"]) for l in range(L)], c["masks"], dz)
+        skips = list(self.cfg["skips"])
+        return dz, dx, bl, dz[skips[0]] if skips else None
 
-            def run_expert_bwd():
-                o.mlp_chain(dh2, [o.Layer(self.wb["l2h_pad"], None, save=dh1), o.Layer(self.wb["l1"], None, save=dz_last)] + bl, dx, n_groups=ng,
-                            n_wsets=n_loc, group_stride=cap, group_rows=grp_rows, group_rows_clamp=cap, x_gather=perm,
-                            y_add=dz[skip_l] if skip_l is not None else None, tag=8, geometry=7, x_features=H2,
-                            combine=(c["y"], dsig, self.p["sigma.w"], c["gmax"], dgmax, dws_dst[0]), head=(2, c["drop_begin"], c["dropped"]),
-                            group_begin=c.get("group_begin"), packed_rows=c.get("packed_rows", 0))
-            with self._timed("expert_bwd"):
-                run_expert_bwd()
-            if self.profile and "_relaunch" in c:
-                if fused_dws:      # (a relaunch for timing adds into a scratch vector, not into the gradient)
-                    dws_dst[0] = torch.zeros(M, dtype=torch.float32, device=self.dev)
-                c["_relaunch"]["expert_bwd"] = run_expert_bwd
-            if P > (1 << 19):
-                self._dense_wgrads(tail_jobs, nsp)
-                tail_jobs = []
-        elif ep is None:
-            perm = c["perm"].view(-1)
-            x_first, dz_last = c["h0"], dout            # read through the routing permutation
-            def run_expert_bwd():
-                o.mlp_chain(dz_last, bl, dx, n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows,
-                            group_rows_clamp=cap, x_gather=perm, y_add=dz[skip_l] if skip_l is not None else None, tag=2,
-                            geometry=c["geom"], group_begin=c.get("group_begin") if c.get("packed_rows") else None,
-                            packed_rows=c.get("packed_rows", 0))
-            with self._timed("expert_bwd"):
-                run_expert_bwd()
-            if self.profile and "_relaunch" in c:
-                c["_relaunch"]["expert_bwd"] = run_expert_bwd
+    def _experts_backward_fused(self, c, b):
+        """Tail backward + combine backward + expert backward in ONE launch (chain_big.hip, tag 8) on the local experts."""
+        o, M = ops, self.M
+        dz, dx, bl, y_add = self._expert_backward_layers(c)
+        dz_last = self._buf(c["tag"] + ":dz_last", (c["rows"], M), self.dtype)      # the last expert layer's dZ in the row space (the combine's output)
+        lys = [o.Layer(self.wb["l2h_pad"], None, save=b["dh1"]), o.Layer(self.wb["l1"], None, save=dz_last)] + bl
+        dws_dst = [self.g["sigma.w"].view(-1) if b["fused_dws"] else None]
+        grp = self._group_args(c)
+
+        def run_expert_bwd():
+            o.mlp_chain(b["dh2"], lys, dx, y_add=y_add, tag=8, geometry=7, x_features=self.H2,
+                        combine=(c["y"], b["dsig"], self.p["sigma.w"], c["gmax"], b["dgmax"], dws_dst[0]), head=(2, c["drop_begin"], c["dropped"]),
+                        group_begin=c.get("group_begin"), packed_rows=c.get("packed_rows", 0), **grp)
+        with self._timed("expert_bwd"):
+            run_expert_bwd()
+        if self.profile and "_relaunch" in c:
+            if b["fused_dws"]:      # (a relaunch for timing adds into a scratch vector, not into the gradient)
+                dws_dst[0] = torch.zeros(M, dtype=torch.float32, device=self.dev)
+            c["_relaunch"]["expert_bwd"] = run_expert_bwd
+        self._tail_wgrads_if_large(c, b)
+        return dict(x_first=c["h0"], dz_last=dz_last, dz=dz, dx=dx, a_gather=grp["x_gather"], b_gather=None, returns=None)
+
+    def _experts_backward_local(self, c, b):
+        """The local experts' backward chain as its own launch (tag 2): dy read through the routing permutation."""
+        o = ops
+        self._tail_wgrads_if_large(c, b)
+        dz, dx, bl, y_add = self._expert_backward_layers(c)
+        grp = self._group_args(c)
+
+        def run_expert_bwd():
+            o.mlp_chain(b["dout"], bl, dx, y_add=y_add, tag=2, geometry=c["geom"], group_begin=c.get("group_begin") if c.get("packed_rows") else None,
+                        packed_rows=c.get("packed_rows", 0), **grp)
+        with self._timed("expert_bwd"):
+            run_expert_bwd()
+        if self.profile and "_relaunch" in c:
+            c["_relaunch"]["expert_bwd"] = run_expert_bwd
+        return dict(x_first=c["h0"], dz_last=b["dout"], dz=dz, dx=dx, a_gather=grp["x_gather"], b_gather=grp["x_gather"], returns=None)
+
+    def _experts_backward_ep(self, c, b):
+        """The expert-parallel backward chain, pipelined per routing segment."""
+        # per segment like the forward pass: dispatch of segment s + 1 and return of segment s - 1 overlap the chain of segment s;
+        # the input gradients come home into the packed row space (dx) that the front backward chain gathers from
+        o, dt, ep = ops, self.dtype, self.ep
+        n_seg, cap, rows, M, dout = c["n_seg"], c["cap"], c["rows"], self.M, b["dout"]
+        pl, perm_p = c["ep_plan"], c["ep_perm"]
+        so, ro = pl["send_off"], pl["recv_off"]
+        dr = self._cbuf(c, "ep_d", (rows, M), dt)
+        dsend = dr if ep.local else self._cbuf(c, "ep_send_d", (rows, M), dt)
+
+        def issue_b(s_):
+            o.gather_rows(dout, perm_p[so[s_]:so[s_ + 1]], dsend[so[s_]:so[s_ + 1]])
+            return ep.all_to_all_v(dsend[so[s_]:so[s_ + 1]], pl["in_splits"][s_], dr[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], self.side)
+        pend = issue_b(0)      # the rows of the first segment travel to their experts while the tail's weight gradients run
+        self._tail_wgrads_if_large(c, b)
+        dz, dx, bl, y_add = self._expert_backward_layers(c)
+        ngs = ep.world * ep.El
+        dx_r = dx if ep.local else self._cbuf(c, "ep_dx", (rows, M), dt)
+        wseg = c["ep_mask_words"]
+        returns = []
+        with self._timed("expert_bwd"):
+            for s_ in range(n_seg):
+                nxt = issue_b(s_ + 1) if s_ + 1 < n_seg else None
+                pend()
+                if ro[s_ + 1] > ro[s_]:
+                    o.mlp_chain(dr, [ly.with_mask_words(s_ * wseg, (s_ + 1) * wseg) for ly in bl], dx_r, n_groups=ngs, n_wsets=ep.El,
+                                group_stride=cap, group_rows=c["ep_counts"][s_], group_rows_clamp=cap, y_add=y_add, tag=2, geometry=c["geom"],
+                                group_begin=c["ep_begin"][s_ * ngs:(s_ + 1) * ngs])
+                returns.append(ep.all_to_all_v(dx_r[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], dx[so[s_]:so[s_ + 1]], pl["in_splits"][s_],
+                                               self.side))
+                pend = nxt
+        # the received rows, already in group order: no gather
+        return dict(x_first=c["ep_x"], dz_last=dr, dz=dz, dx=dx, a_gather=None, b_gather=None, returns=returns)
+
+    def _expert_wgrads(self, c, w):
+        """Expert weight gradients from w, what the mode's _experts_backward_* returned."""
+        # all layers in ONE launch: layer 0 reads its input rows, layer L-1 its dZ rows, through the routing permutation
+        o, g, L, ep = ops, self.g, self.L, self.ep
+        items = o.expert_wgrad_items(w["x_first"], c["saves"], w["dz"], w["dz_last"], [self._local_experts(g[f"exp{l}.w"]) for l in range(L)],
+                                     [self._local_experts(g[f"exp{l}.b"]) for l in range(L)], w["a_gather"], w["b_gather"])
+        grp = self._group_args(c, gather=False)
+        if ep is not None:      # received rows are packed: groups through their first rows (any width: wgrad_multi cuts 512-feature
+            grp.update(n_wsets=ep.El, group_rows=c["ep_counts"].reshape(-1))      # operands into 256-column GEMMs of the same launch)
+            o.wgrad_multi(items, tag=1, group_begin=c["ep_begin"], **grp)
+        elif c.get("packed_rows"):      # the no-drop row space (capacity_factor = 0): the same balanced launch over the packed groups -
+            o.wgrad_multi(items, tag=1, group_begin=c["group_begin"], **grp)      # it cuts the valid rows into equal shares (no row-split heuristic)
         else:
-            # per segment like the forward pass: dispatch of segment s + 1 and return of segment s - 1 overlap the chain of segment s;
-            # the input gradients come home into the packed row space (dx) that the front backward chain gathers from
-            perm = None
-            x_first, dz_last = c["ep_x"], dr                     # the received rows, already in group order
-            grp_rows = c["ep_counts"].reshape(-1)
-            ngs = ep.world * ep.El
-            dx_r = dx if ep.local else _b("ep_dx", (rows, M), dt)
-            wseg = c["ep_mask_words"]
-            returns = []
-            with self._timed("expert_bwd"):
-                for s_ in range(n_seg):
-                    nxt = issue_b(s_ + 1) if s_ + 1 < n_seg else None
-                    pend()
-                    bl_s = [o.Layer(ly.w, None, relu=ly.relu, save=ly.save,
-                                    mask=None if ly.mask is None else ly.mask[s_ * wseg:(s_ + 1) * wseg]) for ly in bl]
-                    if ro[s_ + 1] > ro[s_]:
-                        o.mlp_chain(dr, bl_s, dx_r, n_groups=ngs, n_wsets=n_loc, group_stride=cap, group_rows=c["ep_counts"][s_],
-                                    group_rows_clamp=cap, y_add=dz[skip_l] if skip_l is not None else None, tag=2, geometry=c["geom"],
-                                    group_begin=c["ep_begin"][s_ * ngs:(s_ + 1) * ngs])
-                    returns.append(ep.all_to_all_v(dx_r[ro[s_]:ro[s_ + 1]], pl["out_splits"][s_], dx[so[s_]:so[s_ + 1]], pl["in_splits"][s_],
-                                                   self.side))
-                    pend = nxt
-
-        def expert_wgrads():
-            # all layers in ONE launch: layer 0 reads its input rows, layer L-1 its dZ rows, through the routing permutation
-            items = []
-            for l in range(L):
-                a = x_first if l == 0 else c["saves"][l - 1]
-                bz = dz_last if l == L - 1 else dz[l]
-                items.append((a, bz, self._local_experts(g[f"exp{l}.w"]), self._local_experts(g[f"exp{l}.b"]),
-                              perm if l == 0 else None, perm if (l == L - 1 and not fused_bwd) else None))
-            if ep is not None:      # received rows are packed: groups through their first rows (any width: wgrad_multi cuts 512-feature
-                o.wgrad_multi(items, n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows, group_rows_clamp=cap, tag=1,
-                              group_begin=c["ep_begin"])      # operands into 256-column GEMMs of the same launch)
-                return
-            if c.get("packed_rows"):      # the no-drop row space (capacity_factor = 0): the same balanced launch over the packed groups -
-                o.wgrad_multi(items, n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows, group_rows_clamp=cap, tag=1,
-                              group_begin=c["group_begin"])      # it cuts the valid rows into equal shares (no row-split heuristic)
-                return
             for i0 in range(0, L, 8):
-                o.wgrad_batched(items[i0:i0 + 8], n_groups=ng, n_wsets=n_loc, group_stride=cap, group_rows=grp_rows,
-                                group_rows_clamp=cap, n_splits=self.expert_wgrad_splits or max(1, min(256 // ng, cap // 2048)), tag=1)
-        side_done = None
-        if self.overlap and self.side is not None and not self.profile and not join_side:
-            # independent of everything that follows (they only read the saved activations / dZ and write their own
-            # gradient slices): run them on the side stream, join before Adam
-            ready = torch.cuda.Event()
-            ready.record()
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ready)
-                expert_wgrads()
-                side_done = torch.cuda.Event()
-                side_done.record()
-        else:
-            with self._timed("expert_wgrad"):
-                expert_wgrads()
-            if self.profile and "_relaunch" in c:
-                c["_relaunch"]["expert_wgrad"] = expert_wgrads        # (accumulates into the gradient buffer again: timing only)
-        if side_small is not None and side_done is None:      # (no expert weight gradients behind it on the side stream: join here)
-            torch.cuda.current_stream().wait_event(side_small)
-        return dict(c=c, d_laux=d_laux, dgmax=dgmax, dx=dx, dout=dout, returns=returns if ep is not None else None, tail_jobs=tail_jobs,
-                    nsp=nsp, side_done=side_done, keep=(dc_ray, dh2, dsig))      # (keep: tensors the side stream reads stay allocated to the join)
+                o.wgrad_batched(items[i0:i0 + 8], n_splits=self.expert_wgrad_splits or max(1, min(256 // c["ng"], c["cap"] // 2048)), tag=1, **grp)
 
     def backward_net_b(self, st):
         """Second half of backward_net: router backward, front backward chain, dense weight gradients (+ the hash table's)."""
@@ -1108,14 +1174,13 @@ class SwitchNeRF:
         P, seg_tokens = c["P"], c["seg_tokens"]
         M, E, G = self.M, self.E, self.G
         g, ep = self.g, self.ep
-        _b = lambda name, shape, dtype: self._buf(c["tag"] + ":" + name, shape, dtype)
         # gate backward (softmax / router / LayerNorm) including the l_aux term
         coef = (d_laux * (E / float(seg_tokens * seg_tokens))).to(torch.float32).contiguous()
         dg = o.gate_bwd(c["g"], self.p["ln.w"], self.p["ln.b"], self.p["wg"], c["gates"], c["idx"], dgmax, c["stats"],
                         c["counts"], coef, seg_tokens, g["wg"], g["ln.w"], g["ln.b"])
         # front backward chain: dg -> d(a1) -> d(h0), adding the expert path's input gradient through tok2row
-        dza1 = _b("dza1", (P, G), dt)
-        dh0 = _b("dh0", (P, M), dt)
+        dza1 = self._cbuf(c, "dza1", (P, G), dt)
+        dh0 = self._cbuf(c, "dh0", (P, M), dt)
         if ep is not None:      # (the input gradients travelled home under the expert weight gradients / the router backward)
             for wait in returns:
                 wait()
@@ -1128,7 +1193,7 @@ class SwitchNeRF:
             d_enc = c.get("d_enc_out")     # (a part of a ragged batch: its rows of the batch's buffer - backward_net scatters them)
             part = d_enc is not None
             if not part:
-                d_enc = _b("d_enc", (P, self.KP), dt)
+                d_enc = self._cbuf(c, "d_enc", (P, self.KP), dt)
             o.mlp_chain(dh0, [o.Layer(self.wb["xyz"], None)], d_enc, tag=0)
             if not part:
                 o.hash_encode_bwd(c["rays"], c["z"], d_enc, self.hash, g["hash.table"])

@@ -77,6 +77,40 @@ class _Gate(nn.Module):
         self.wg = nn.Linear(gate_dim, n_experts, bias=False)       # tutel_moe_layer_nobatch.py:73 (fp32 router)
 
 
+def _expert_fwd_setup(layer, wb, E, stride, need_grad):
+    """(forward layer list, saves, masks) of an expert MLP over E groups of `stride` rows from the parameters wb = (*weights, *biases);
+    the save / mask buffers only when something needs a gradient."""
+    o, dt, L, M, dev = ops, layer.dtype, layer.layer_num, layer.model_dim, wb[0].device
+    wf = [o.pack_weights(w.detach().float().contiguous(), dt, True) for w in wb[:L]]
+    bias = [b.detach().float().reshape(E, M).contiguous() for b in wb[L:]]
+    saves = [torch.empty(E * stride, M, dtype=dt, device=dev) if need_grad else None for _ in range(L - 1)]
+    nw = o.chain_mask_words(dt, E, stride, M)
+    masks = [torch.empty(nw, dtype=torch.int32, device=dev) if need_grad else None for _ in range(L - 1)]
+    return o.expert_fwd_layers(wf, bias, layer.skips, saves, masks), saves, masks
+
+
+def _expert_bwd_setup(layer, ws, rows, masks):
+    """(backward layer list, dz, the input-gradient buffer, the skip's y_add) of an expert MLP over a row space of `rows` rows."""
+    o, dt, M, dev = ops, layer.dtype, layer.model_dim, ws[0].device
+    wbk = [o.pack_weights(w.detach().float().contiguous(), dt, False) for w in ws]
+    dz = [torch.empty(rows, M, dtype=dt, device=dev) for _ in range(len(ws) - 1)]
+    dxr = torch.empty(rows, M, dtype=dt, device=dev)
+    return o.expert_bwd_layers(wbk, masks, dz), dz, dxr, dz[layer.skips[0]] if layer.skips else None
+
+
+def _expert_wgrads(xs, saves, dz, dout, E, stride, group_rows, n_splits, a_gather=None):
+    """(dW [E, M, M], db [E, M]) of every expert layer, zero-initialised, 8 layers per launch: layer 0 reads its input rows xs (through
+    a_gather, the routing permutation, where they are in token order)."""
+    M, L = xs.shape[1], len(dz) + 1
+    dws = [torch.zeros(E, M, M, dtype=torch.float32, device=xs.device) for _ in range(L)]
+    dbs = [torch.zeros(E, M, dtype=torch.float32, device=xs.device) for _ in range(L)]
+    items = ops.expert_wgrad_items(xs, saves, dz, dout, dws, dbs, a_gather=a_gather)
+    for i0 in range(0, L, 8):
+        ops.wgrad_batched(items[i0:i0 + 8], n_groups=E, n_wsets=E, group_stride=stride, group_rows=group_rows, group_rows_clamp=stride,
+                          n_splits=n_splits, tag=1)
+    return dws, dbs
+
+
 class _MoEFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layer, x, gate_in, wg, gate_noise, *wb):
@@ -97,16 +131,10 @@ class _MoEFunction(torch.autograd.Function):
         loc, counts, perm, tok2row, l_aux = o.route_top1(idx, gmax, gates, P, E, cap, layer.bpr)
         need_grad = any(ctx.needs_input_grad[1:])
         rows = E * cap
-        wf = [o.pack_weights(w.detach().float().contiguous(), dt, True) for w in wb[:L]]
-        bias = [b.detach().float().reshape(E, M).contiguous() for b in wb[L:]]
-        saves = [torch.empty(rows, M, dtype=dt, device=xs.device) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
-        nw = o.chain_mask_words(dt, E, cap, M)
-        masks = [torch.empty(nw, dtype=torch.int32, device=xs.device) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
-        layers = [o.Layer(wf[l], bias[l], relu=1 if l < L - 1 else 0, skip=(l in layer.skips), save=saves[l] if l < L - 1 else None,
-                          mask=masks[l] if l < L - 1 else None) for l in range(L)]
+        layers, saves, masks = _expert_fwd_setup(layer, wb, E, cap, need_grad)
         eo = torch.empty(rows, M, dtype=dt, device=xs.device)
         cnt = counts.view(-1)
-        geom = 7 if (M == 256 and dt != torch.float32 and cap >= 256) else 1       # persistent 256-row geometry (forward and backward alike)
+        geom = o.expert_geometry(M, dt, cap)       # persistent 256-row geometry (forward and backward alike)
         o.mlp_chain(xs, layers, eo, n_groups=E, n_wsets=E, group_stride=cap, group_rows=cnt, group_rows_clamp=cap,
                     x_gather=perm.view(-1), tag=1, geometry=geom)
         y = o.combine_fwd(gmax, idx, loc, eo, cap, P, E, False)                                # decode: gate * row, 0 if dropped
@@ -134,25 +162,12 @@ class _MoEFunction(torch.autograd.Function):
         dgmax = o.dispatch_bwd_gate(idx, loc, dy, eo, cap)
         dout = o.dispatch_fwd(gmax, idx, loc, dy, E, cap)
         cnt = counts.view(-1)
-        wbk = [o.pack_weights(w.detach().float().contiguous(), dt, False) for w in ws]
-        dz = [torch.empty(E * cap, M, dtype=dt, device=dev) for _ in range(L - 1)]
-        dxr = torch.empty(E * cap, M, dtype=dt, device=dev)
-        skip_l = layer.skips[0] if layer.skips else None
-        bl = [o.Layer(wbk[l], None, relu=2 if l > 0 else 0, mask=masks[l - 1] if l > 0 else None, save=dz[l - 1] if l > 0 else None)
-              for l in range(L - 1, -1, -1)]
+        bl, dz, dxr, y_add = _expert_bwd_setup(layer, ws, E * cap, masks)
         o.mlp_chain(dout, bl, dxr, n_groups=E, n_wsets=E, group_stride=cap, group_rows=cnt, group_rows_clamp=cap,
-                    y_add=dz[skip_l] if skip_l is not None else None, tag=2,
-                    geometry=7 if (M == 256 and dt != torch.float32 and cap >= 256) else 1)
+                    y_add=y_add, tag=2, geometry=o.expert_geometry(M, dt, cap))
         dx = o.dispatch_bwd_data(None, idx, loc, dxr, cap)                                     # encode backward (no score)
         # expert weight / bias gradients, all layers in one launch (layer 0 reads its input rows through the permutation)
-        dws = [torch.zeros(E, M, M, dtype=torch.float32, device=dev) for _ in range(L)]
-        dbs = [torch.zeros(E, M, dtype=torch.float32, device=dev) for _ in range(L)]
-        pv = perm.view(-1)
-        items = [(xs if l == 0 else saves[l - 1], dout if l == L - 1 else dz[l], dws[l], dbs[l], pv if l == 0 else None, None)
-                 for l in range(L)]
-        for i0 in range(0, L, 8):
-            o.wgrad_batched(items[i0:i0 + 8], n_groups=E, n_wsets=E, group_stride=cap, group_rows=cnt, group_rows_clamp=cap,
-                            n_splits=max(1, min(256 // E, cap // 2048)), tag=1)
+        dws, dbs = _expert_wgrads(xs, saves, dz, dout, E, cap, cnt, max(1, min(256 // E, cap // 2048)), perm.view(-1))
         # gate backward: softmax / fp32 router, including the load-balance loss term (tutel_fast_dispatch.py:141-150)
         d_wg = torch.zeros_like(wg32)
         coef = (d_laux.reshape(1).float() * (E / float(P * P))).contiguous()
@@ -198,15 +213,9 @@ class _MoETopKFunction(torch.autograd.Function):
             li = (scores, logits_w, coef_li)
         need_grad = any(ctx.needs_input_grad[1:])
         rows = E * cap
-        wf = [o.pack_weights(w.detach().float().contiguous(), dt, True) for w in wb[:L]]
-        bias = [b.detach().float().reshape(E, M).contiguous() for b in wb[L:]]
-        saves = [torch.empty(rows, M, dtype=dt, device=xs.device) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
-        nw = o.chain_mask_words(dt, E, cap, M)
-        masks = [torch.empty(nw, dtype=torch.int32, device=xs.device) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
-        layers = [o.Layer(wf[l], bias[l], relu=1 if l < L - 1 else 0, skip=(l in layer.skips), save=saves[l] if l < L - 1 else None,
-                          mask=masks[l] if l < L - 1 else None) for l in range(L)]
+        layers, saves, masks = _expert_fwd_setup(layer, wb, E, cap, need_grad)
         eo = torch.empty(rows, M, dtype=dt, device=xs.device)
-        geom = 7 if (M == 256 and dt != torch.float32 and cap >= 256) else 1
+        geom = o.expert_geometry(M, dt, cap)
         o.mlp_chain(xs, layers, eo, n_groups=E, n_wsets=E, group_stride=cap, group_rows=group_rows, group_rows_clamp=cap,
                     x_gather=perm.view(-1), tag=1, geometry=geom)
         y = o.combine_fwd(gn[0], idx[0], loc[0], eo, cap, P, E, False)                         # decode, first choice (:59-62)
@@ -247,26 +256,13 @@ class _MoETopKFunction(torch.autograd.Function):
         dout = o.dispatch_fwd(gn[0], idx[0], loc[0], dy, E, cap)
         for j in range(1, K):
             o.dispatch_fwd_more(gn[j], idx[j], loc[j], dy, dout, E, cap)
-        wbk = [o.pack_weights(w.detach().float().contiguous(), dt, False) for w in ws]
-        dz = [torch.empty(E * cap, M, dtype=dt, device=dev) for _ in range(L - 1)]
-        dxr = torch.empty(E * cap, M, dtype=dt, device=dev)
-        skip_l = layer.skips[0] if layer.skips else None
-        bl = [o.Layer(wbk[l], None, relu=2 if l > 0 else 0, mask=masks[l - 1] if l > 0 else None, save=dz[l - 1] if l > 0 else None)
-              for l in range(L - 1, -1, -1)]
+        bl, dz, dxr, y_add = _expert_bwd_setup(layer, ws, E * cap, masks)
         o.mlp_chain(dout, bl, dxr, n_groups=E, n_wsets=E, group_stride=cap, group_rows=group_rows, group_rows_clamp=cap,
-                    y_add=dz[skip_l] if skip_l is not None else None, tag=2,
-                    geometry=7 if (M == 256 and dt != torch.float32 and cap >= 256) else 1)
+                    y_add=y_add, tag=2, geometry=o.expert_geometry(M, dt, cap))
         dx = o.dispatch_bwd_data(None, idx[0], loc[0], dxr, cap)                               # encode backward (:34-37), summed over the choices
         for j in range(1, K):
             o.dispatch_bwd_data_more(None, idx[j], loc[j], dx, dxr, cap)
-        dws = [torch.zeros(E, M, M, dtype=torch.float32, device=dev) for _ in range(L)]
-        dbs = [torch.zeros(E, M, dtype=torch.float32, device=dev) for _ in range(L)]
-        pv = perm.view(-1)
-        items = [(xs if l == 0 else saves[l - 1], dout if l == L - 1 else dz[l], dws[l], dbs[l], pv if l == 0 else None, None)
-                 for l in range(L)]
-        for i0 in range(0, L, 8):
-            o.wgrad_batched(items[i0:i0 + 8], n_groups=E, n_wsets=E, group_stride=cap, group_rows=group_rows, group_rows_clamp=cap,
-                            n_splits=max(1, min(256 // E, cap // 2048)), tag=1)
+        dws, dbs = _expert_wgrads(xs, saves, dz, dout, E, cap, group_rows, max(1, min(256 // E, cap // 2048)), perm.view(-1))
         # gate backward: the normalisation (:204-206), the softmax / fp32 router, the load-balance term of the FIRST choice's mask (:184)
         d_probs = o.topk_gate_bwd(gates, idx, dgn)
         d_wg = torch.zeros_like(wg32)
@@ -274,10 +270,6 @@ class _MoETopKFunction(torch.autograd.Function):
         dg = o.gate_bwd_dense(gs, None, None, wg32, gates, idx[0].contiguous(), None, d_probs, stats, counts[0].contiguous(), coef, P, d_wg,
                               None, None, d_logits_add=d_logits_add)
         return (None, dx.to(ctx.x_dtype), dg.to(ctx.g_dtype), d_wg, None, None, *dws, *[b.view(E, 1, M) for b in dbs])
-
-
-def _residual_geometry(M, dt, P):
-    return 7 if (M == 256 and dt != torch.float32 and P >= 256) else 1      # (the experts' choice, with all P rows as one group)
 
 
 class _ResidualExpertFunction(torch.autograd.Function):
@@ -292,17 +284,11 @@ class _ResidualExpertFunction(torch.autograd.Function):
         dev = xs.device
         xs = xs.detach().contiguous()
         need_grad = any(ctx.needs_input_grad[1:])
-        wf = [o.pack_weights(w.detach().float().contiguous(), dt, True) for w in wb[:L]]
-        bias = [b.detach().float().reshape(1, M).contiguous() for b in wb[L:]]
-        saves = [torch.empty(P, M, dtype=dt, device=dev) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
-        nw = o.chain_mask_words(dt, 1, P, M)
-        masks = [torch.empty(nw, dtype=torch.int32, device=dev) for _ in range(L - 1)] if need_grad else [None] * (L - 1)
-        layers = [o.Layer(wf[l], bias[l], relu=1 if l < L - 1 else 0, skip=(l in layer.skips), save=saves[l] if l < L - 1 else None,
-                          mask=masks[l] if l < L - 1 else None) for l in range(L)]
+        layers, saves, masks = _expert_fwd_setup(layer, wb, 1, P, need_grad)
         rows = torch.full((1,), P, dtype=torch.int32, device=dev)
         y = torch.empty(P, M, dtype=dt, device=dev)
         o.mlp_chain(xs, layers, y, n_groups=1, n_wsets=1, group_stride=P, group_rows=rows, group_rows_clamp=P, tag=1,
-                    geometry=_residual_geometry(M, dt, P))
+                    geometry=o.expert_geometry(M, dt, P))      # (the experts' choice, with all P rows as one group)
         ctx.layer = layer
         ctx.save_for_backward(xs, rows, *wb[:L], *[s for s in saves if s is not None], *[m for m in masks if m is not None])
         return y
@@ -317,22 +303,11 @@ class _ResidualExpertFunction(torch.autograd.Function):
         saves = list(sv[2 + L:2 + L + (L - 1)])
         masks = list(sv[2 + L + (L - 1):])
         P = xs.shape[0]
-        dev = xs.device
         dout = dy.to(dt).contiguous()
-        wbk = [o.pack_weights(w.detach().float().contiguous(), dt, False) for w in ws]
-        dz = [torch.empty(P, M, dtype=dt, device=dev) for _ in range(L - 1)]
-        dx = torch.empty(P, M, dtype=dt, device=dev)
-        skip_l = layer.skips[0] if layer.skips else None
-        bl = [o.Layer(wbk[l], None, relu=2 if l > 0 else 0, mask=masks[l - 1] if l > 0 else None, save=dz[l - 1] if l > 0 else None)
-              for l in range(L - 1, -1, -1)]
+        bl, dz, dx, y_add = _expert_bwd_setup(layer, ws, P, masks)
         o.mlp_chain(dout, bl, dx, n_groups=1, n_wsets=1, group_stride=P, group_rows=rows, group_rows_clamp=P,
-                    y_add=dz[skip_l] if skip_l is not None else None, tag=2, geometry=_residual_geometry(M, dt, P))
-        dws = [torch.zeros(1, M, M, dtype=torch.float32, device=dev) for _ in range(L)]
-        dbs = [torch.zeros(1, M, dtype=torch.float32, device=dev) for _ in range(L)]
-        items = [(xs if l == 0 else saves[l - 1], dout if l == L - 1 else dz[l], dws[l], dbs[l], None, None) for l in range(L)]
-        for i0 in range(0, L, 8):
-            # (one group: the balanced launch; n_splits only sizes the fallback's workspace)
-            o.wgrad_batched(items[i0:i0 + 8], n_groups=1, n_wsets=1, group_stride=P, group_rows=rows, group_rows_clamp=P, n_splits=1, tag=1)
+                    y_add=y_add, tag=2, geometry=o.expert_geometry(M, dt, P))      # (the experts' choice, with all P rows as one group)
+        dws, dbs = _expert_wgrads(xs, saves, dz, dout, 1, P, rows, 1)      # (one group: the balanced launch; n_splits only sizes the fallback's workspace)
         return (None, dx, *dws, *[b.view(1, 1, M) for b in dbs])
 
 

@@ -859,6 +859,46 @@ class Layer:
         self.w, self.b, self.relu, self.skip, self.save, self.mask = w, b, int(relu), int(skip), save, mask      # skip: 0 / 1 residual / 2 concat half
         self.rowbias, self.rows_per_bias = rowbias, int(rows_per_bias)
 
+    def without_saves(self):
+        """The layer as an inference launch runs it: no activation save, no ReLU mask."""
+        return Layer(self.w, self.b, self.relu, self.skip, None, None, self.rowbias, self.rows_per_bias)
+
+    def with_mask_words(self, w0, w1):
+        """The layer with words [w0, w1) of its ReLU mask (one routing segment of a mask buffer that holds every segment's)."""
+        return Layer(self.w, self.b, self.relu, self.skip, self.save, None if self.mask is None else self.mask[w0:w1], self.rowbias,
+                     self.rows_per_bias)
+
+
+# ---- the expert chain's rules, each written once (SwitchNeRF, ep_owner.py and the autograd functions of moe.py build their launches from
+# these; pure Python over Layer and tensors)
+def expert_fwd_layers(w, b, skips, saves, masks):
+    """Forward layers of an expert MLP from packed weights w[l] and biases b[l]: ReLU on all but the last layer, the residual skip on the
+    layers in `skips`; layer l < L - 1 saves its output in saves[l] and its ReLU mask in masks[l] (length L - 1, None = nothing saved)."""
+    L = len(w)
+    return [Layer(w[l], b[l], relu=1 if l < L - 1 else 0, skip=(l in skips), save=saves[l] if l < L - 1 else None,
+                  mask=masks[l] if l < L - 1 else None) for l in range(L)]
+
+
+def expert_bwd_layers(wb, masks, dz):
+    """Backward-data layers in launch order (layer L - 1 first) from the backward copies wb[l]: above layer 0 the layer's input gradient
+    goes through the ReLU mask of the layer below (relu = 2, masks[l - 1]) and is saved as dz[l - 1], the next weight-gradient operand."""
+    return [Layer(wb[l], None, relu=2 if l > 0 else 0, mask=masks[l - 1] if l > 0 else None, save=dz[l - 1] if l > 0 else None)
+            for l in range(len(wb) - 1, -1, -1)]
+
+
+def expert_wgrad_items(x_first, saves, dz, dz_last, dw, db, a_gather=None, b_gather=None):
+    """(a, dz, dw, db, a_gather, b_gather) per layer for wgrad_multi / wgrad_batched: layer 0 reads the chain's input rows x_first (through
+    a_gather), layer l > 0 the saved output of layer l - 1; layer L - 1 reads dz_last (through b_gather), layer l < L - 1 the saved dz[l]."""
+    L = len(dw)
+    return [(x_first if l == 0 else saves[l - 1], dz_last if l == L - 1 else dz[l], dw[l], db[l], a_gather if l == 0 else None,
+             b_gather if l == L - 1 else None) for l in range(L)]
+
+
+def expert_geometry(M, dt, rows, preferred=7):
+    """Geometry of an expert chain, forward and backward alike (the pair shares its ReLU mask layout): `preferred` for 256-feature experts
+    in a 16-bit compute dtype once a group holds at least one full 256-row tile, else the 64-row kernels (1)."""
+    return preferred if (M == 256 and dt != torch.float32 and rows >= 256) else 1
+
 
 def chain_tile_rows(dtype) -> int:
     return _lib.load().swn_chain_tile_rows(_code(dtype))

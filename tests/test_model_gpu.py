@@ -895,3 +895,41 @@ def test_fused_tail_inference_on_packed_rows_equals_separate_launches_bf16(monke
         d_rgb = (outs[0][2] - outs[1][2]).abs().max().item()
         print(f"fused inference (no_batch={no_batch}, {outs[0][3]} dropped): raw {d_raw:.2e}, rgb {d_rgb:.2e}")
         assert d_raw < 5e-3 and d_rgb < 2e-3
+
+
+def test_profile_relaunch_hooks_rerun_on_live_buffers_without_side_effects():
+    """The relaunch hooks of a profiled step (SwitchNeRF.profile; bench.py times the expert kernels through them): the smallest shape
+    that takes geometry 7 and the fused tail (two segments, capacity 256).  The three forward hooks and the backward hook re-run on the
+    step's live buffers and leave raw, y, h2 and the gradient bit-identical (the backward relaunch adds the sigma head's weight gradient
+    into a scratch vector); the weight-gradient hook accumulates into the expert block only.  With the tail as its own launches the
+    hooks are the same set without the expert-layers-alone one."""
+    N, S, chunk = 64, 64, 2048
+    rays, img, rgbs = synth.make_rays(181, N)
+    for fused in (True, False):
+        m = _model(torch.bfloat16, 180, 1.0, capacity_factor=1.0)
+        if not fused:
+            m.set_kernel_switches(fused_tail=False)
+        m.profile = True
+        st = m.grad_step(_dev(rgbs), _dev(rays), _dev(img), S, chunk, perturb=0.0)
+        m.profile = False
+        c = st["ctx"]
+        assert c["n_seg"] == 2 and c["cap"] == 256 and c["geom"] == 7 and c["tail_fused"] == fused
+        hooks = c["_relaunch"]
+        names = {"expert_fwd", "expert_fwd_nosave", "expert_gemm_nosave", "expert_bwd", "expert_wgrad"}
+        assert set(hooks) == (names if fused else names - {"expert_gemm_nosave"})
+        torch.cuda.synchronize()
+        keep = {k: c[k].clone() for k in ("raw", "y", "h2")}
+        grad = m.grad.clone()
+        assert grad.abs().sum().item() > 0
+        for name in ("expert_fwd", "expert_fwd_nosave", "expert_gemm_nosave", "expert_bwd"):
+            if name not in hooks:
+                continue
+            hooks[name]()
+            torch.cuda.synchronize()
+            for k, v in keep.items():
+                assert torch.equal(c[k], v), (name, k)
+            assert torch.equal(m.grad, grad), name
+        hooks["expert_wgrad"]()
+        torch.cuda.synchronize()
+        assert torch.equal(m.grad[:m.n_dense], grad[:m.n_dense])
+        assert not torch.equal(m.grad[m.n_dense:], grad[m.n_dense:])
