@@ -50,6 +50,25 @@ int swn_sample_pe(const float* rays, const float* t_steps, const float* perturb_
                   int n_rays, int n_samples, int l_xyz, int l_dir, int dtype,
                   float* z_out, void* pe_xyz, int pe_stride, void* pe_dir, int dir_stride, void* stream);
 
+/* ---- seeded device-side noise (csrc/philox.hpp, csrc/rng.hip) ---------------------------------------------------
+ * Philox4x32-10 keyed by (seed, step, stream id, GLOBAL element index): element e is word (e & 3) of block e >> 2,
+ * counter = {block_lo, block_hi, step, stream id}, key = {seed_lo, seed_hi}.  The step (< 2^32, checked where the host sets
+ * it) is read from DEVICE memory (step_dev: int64[1]) by the kernels, so a launch captured into a hipGraph follows it.
+ * Stream ids: 0 coarse jitter, 1 coarse sigma noise, 2 fine u, 3 fine sigma noise, 4 gate noise, 5 router normal noise.
+ * swn_rng_fill: out[i] = the draw of element base + i (base need not be a multiple of 4); kind 0: uniform
+ *   (x >> 8) 2^-24 in [0, 1); kind 1: standard normal (Box-Muller over the word pairs (0,1), (2,3)) times scale.
+ * swn_rng_advance: *step_dev += 1, one thread - the last launch of a training step.
+ * swn_sample_pe_rng: swn_sample_pe with the jitter (stream 0, element (ray_base + ray) * n_samples + s) drawn inside the
+ *   kernel: z_out / pe_xyz / pe_dir equal swn_rng_fill(stream 0, base = ray_base * n_samples) + swn_sample_pe bit for bit. */
+#define SWN_RNG_UNIFORM 0
+#define SWN_RNG_NORMAL 1
+int swn_rng_fill(float* out, int64_t n, int64_t base, int kind, float scale, uint64_t seed, const int64_t* step_dev,
+                 int stream_id, void* stream);
+int swn_rng_advance(int64_t* step_dev, void* stream);
+int swn_sample_pe_rng(const float* rays, const float* t_steps, uint64_t seed, const int64_t* step_dev, int64_t ray_base,
+                      float perturb, int n_rays, int n_samples, int l_xyz, int l_dir, int dtype, float* z_out, void* pe_xyz,
+                      int pe_stride, void* pe_dir, int dir_stride, void* stream);
+
 /* same encoding for caller-supplied depths z[N,S] (fine pass: xyz_fine_fn, rendering.py:246) */
 int swn_pe_from_z(const float* rays, const float* z, int n_rays, int n_samples, int l_xyz, int dtype, void* pe_xyz,
                   int pe_stride, void* stream);

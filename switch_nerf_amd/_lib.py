@@ -25,7 +25,7 @@ def source_hash() -> str:
             h.update(open(f, "rb").read())
     return h.hexdigest()
 
-vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
+vp, i32, i64, f32, sz, u64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_uint64
 
 
 class ChainLayer(C.Structure):
@@ -67,6 +67,9 @@ SIGNATURES = {
     "swn_version": [],
     "swn_mfma_probe": [vp, vp],
     "swn_sample_pe": [vp, vp, vp, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp],
+    "swn_sample_pe_rng": [vp, vp, u64, vp, i64, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp],
+    "swn_rng_fill": [vp, i64, i64, i32, f32, u64, vp, i32, vp],
+    "swn_rng_advance": [vp, vp],
     "swn_pe_from_z": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
     "swn_sample_pdf": [vp, vp, vp, i32, i32, i32, vp, vp],
     "swn_merge_samples": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],

@@ -21,17 +21,27 @@ class RenderRaysFunction(torch.autograd.Function):
     """(flat_param, nerf, rays, image_indices, S, F, chunk, perturb, perturb_rand, sigma_noise, sigma_noise_fine)
     -> (rgb [N,3], gate_loss_coarse [n_seg], gate_loss_fine [n_seg_f] or empty, depth [N], depth_variance [N]).
     perturb_rand = "graph" (with sigma_noise = the noise std): the forward and the backward are replayed from the captured graphs of
-    graph.GraphedRenderTrain (`nerf.graph_train = True`), which draw the jitter and the noise on the device themselves."""
+    graph.GraphedRenderTrain (`nerf.graph_train = True`), which draw the jitter and the noise on the device themselves.
+    sigma_noise = a float with perturb_rand = None (the model's device noise on): the passes draw jitter and noise from the seeded
+    generator, sigma noise with that std; the forward ends in the step counter's advance."""
 
     @staticmethod
     def forward(ctx, flat_param, nerf, rays, image_indices, S, F, chunk, perturb, perturb_rand, sigma_noise, sigma_noise_fine):
         nerf._sync_compute_copies()
         ctx.nerf, ctx.fine = nerf, F > 0
         ctx.graph = None
+        std = 0.0
+        if isinstance(sigma_noise, float) and perturb_rand is None:      # the model's seeded device noise is on (set_device_noise): the std
+            if not getattr(nerf, "device_noise", False):                 # of the sigma noise the passes draw themselves
+                raise ValueError("RenderRaysFunction: sigma_noise given as a std (float) needs the model's device noise on "
+                                 "(set_device_noise); pass a noise tensor or None otherwise")
+            std, sigma_noise = sigma_noise, None
         if isinstance(perturb_rand, str) and perturb_rand == "graph":
             from .graph import GraphedRenderTrain, cached_graph
             cache = nerf.__dict__.setdefault("_train_graphs", {})
-            key = (rays.shape[0], S, F, int(chunk), float(perturb), float(sigma_noise or 0.0), bool(nerf.moe_no_batch), nerf.dtype)
+            dn = nerf._noise or {}                           # (a captured graph holds the seed and ray_base it was captured with)
+            key = (rays.shape[0], S, F, int(chunk), float(perturb), float(sigma_noise or 0.0), bool(nerf.moe_no_batch), nerf.dtype,
+                   dn.get("seed"), dn.get("ray_base"))
             g = cached_graph(cache, key, lambda: GraphedRenderTrain(nerf, rays, image_indices, S, F, chunk, float(perturb),
                                                                     float(sigma_noise or 0.0)))
             state, outs = g.forward(rays, image_indices)
@@ -39,11 +49,14 @@ class RenderRaysFunction(torch.autograd.Function):
             res = (outs[0].clone(), outs[1].clone(), outs[2].clone(), outs[3].clone(), outs[4].clone())
         elif F > 0:
             c, cf, out = nerf.forward_hier(rays, image_indices, S, F, chunk, perturb, perturb_rand, None, sigma_noise, sigma_noise_fine,
-                                           no_batch=nerf.moe_no_batch, training=True)
+                                           no_batch=nerf.moe_no_batch, training=True, sigma_noise_std=std)
+            nerf._noise_advance()
             ctx.state = (c, cf, out, S, F)
             res = (out["rgb"], c["l_aux"], cf["l_aux"], out["depth"], out["depth_variance"])
         else:
-            c = nerf.forward_rays(rays, image_indices, S, chunk, perturb, perturb_rand, sigma_noise, training=True, no_batch=nerf.moe_no_batch)
+            c = nerf.forward_rays(rays, image_indices, S, chunk, perturb, perturb_rand, sigma_noise, training=True, no_batch=nerf.moe_no_batch,
+                                  sigma_noise_std=std)
+            nerf._noise_advance()
             ctx.state = (c,)
             res = (c["rgb"], c["l_aux"], torch.zeros(0, device=rays.device), c["depth"], c["depth_variance"])
         ctx.mark_non_differentiable(res[3], res[4])

@@ -64,6 +64,10 @@ class BackgroundScene:
         """sigma_noise_bg / sigma_noise_bg_fine: [Nb * samples] tensors, or the string "randn" to draw noise_std * N(0,1)
         here (the number of background rays is only known inside)."""
         o, nerf, bg = ops, self.nerf, self.bg
+        if getattr(nerf, "device_noise", False) or getattr(bg, "device_noise", False):
+            # the background's rays are a data-dependent subset: no global index to key its noise by - never mix the two sources silently
+            raise NotImplementedError("seeded device noise (set_device_noise / device_noise_seed) with a background model is not "
+                                      "implemented: turn it off (set_device_noise(None)) for scenes with a bg_nerf")
         N, S, Fn = rays.shape[0], n_samples, int(fine_samples)
         rays_fg, fg_far, last0, has_bg, n_out = o.fg_bounds(rays, self.center, self.radius)
         idx_bg = has_bg.nonzero().view(-1)                      # rays_with_bg, rendering.py:36 (host sync, like the reference)

@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include "common.hpp"
 #include "pe_store.hpp"
+#include "philox.hpp"
 
 namespace swn {
 
@@ -60,11 +61,14 @@ __device__ __forceinline__ float z_of(float near, float far, float t) {
   return a + b;
 }
 
-template <typename T, int LMAX>
+// The jitter's third source (swn_sample_pe_rng): stream 0 of the seeded generator drawn in place, element (ray_base + ray) * S + s.
+struct JitterRng { uint64_t seed; const int64_t* step_dev; int64_t elem_base; };
+
+template <typename T, int LMAX, bool RNG = false>
 __global__ __launch_bounds__(128) void sample_pe_kernel(const float* __restrict__ rays, const float* __restrict__ tsteps,
                                                         const float* __restrict__ prand, float perturb, int n_rays,
                                                         int S, int L, float* __restrict__ z_out, T* __restrict__ pe,
-                                                        int pe_stride, const float* __restrict__ z_in) {
+                                                        int pe_stride, const float* __restrict__ z_in, JitterRng rng = JitterRng{}) {
 #pragma clang fp contract(off)
   const long p_raw = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = p_raw < (long)n_rays * S;
@@ -73,12 +77,15 @@ __global__ __launch_bounds__(128) void sample_pe_kernel(const float* __restrict_
   const float* r = rays + (long)ray * 8;
   const float near = r[6], far = r[7];
   float z = z_in ? z_in[p] : z_of(near, far, tsteps[s]);      // z_in: depths supplied by the caller (fine pass)
-  if (!z_in && perturb > 0.f && prand) {  // rendering.py:573-584
+  if (!z_in && perturb > 0.f && (RNG || prand)) {  // rendering.py:573-584
     const float zp = s > 0 ? z_of(near, far, tsteps[s - 1]) : z;
     const float zn = s < S - 1 ? z_of(near, far, tsteps[s + 1]) : z;
     const float lower = s > 0 ? 0.5f * (zp + z) : z;
     const float upper = s < S - 1 ? 0.5f * (z + zn) : z;
-    const float pr = perturb * prand[p];
+    float u;
+    if constexpr (RNG) u = philox_uniform_at(rng.seed, (uint32_t)*rng.step_dev, RNG_STREAM_JITTER, rng.elem_base + p);
+    else u = prand[p];
+    const float pr = perturb * u;
     const float span = (upper - lower) * pr;
     z = lower + span;
   }
@@ -1114,24 +1121,26 @@ static inline int ew_blocks(long waves_needed) {
   return (int)b;
 }
 
-extern "C" int swn_sample_pe(const float* rays, const float* t_steps, const float* perturb_rand, float perturb,
-                             int n_rays, int n_samples, int l_xyz, int l_dir, int dtype, float* z_out, void* pe_xyz,
-                             int pe_stride, void* pe_dir, int dir_stride, void* stream) {
-  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "swn_sample_pe: bad dtype");
-  SWN_CHECK(rays && t_steps && z_out && pe_xyz, "swn_sample_pe: null pointer");
-  SWN_CHECK(l_xyz >= 0 && l_xyz <= 12 && l_dir >= 0 && l_dir <= 12, "swn_sample_pe: frequencies must be <= 12");
+// swn_sample_pe / swn_sample_pe_rng: the checks and the two launches (points, directions); RNG selects the jitter's source
+template <bool RNG>
+static int sample_pe_launch(const char* who, const float* rays, const float* t_steps, const float* perturb_rand, JitterRng rng, float perturb,
+                            int n_rays, int n_samples, int l_xyz, int l_dir, int dtype, float* z_out, void* pe_xyz, int pe_stride,
+                            void* pe_dir, int dir_stride, void* stream) {
+  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "%s: bad dtype", who);
+  SWN_CHECK(rays && t_steps && z_out && pe_xyz, "%s: null pointer", who);
+  SWN_CHECK(l_xyz >= 0 && l_xyz <= 12 && l_dir >= 0 && l_dir <= 12, "%s: frequencies must be <= 12", who);
   const int epc = dtype == SWN_HALF ? 8 : 4;
-  SWN_CHECK(pe_stride >= 3 + 6 * l_xyz && pe_stride % epc == 0, "swn_sample_pe: pe_stride %d too small / unaligned", pe_stride);
+  SWN_CHECK(pe_stride >= 3 + 6 * l_xyz && pe_stride % epc == 0, "%s: pe_stride %d too small / unaligned", who, pe_stride);
   const long P = (long)n_rays * n_samples;
   if (dtype == SWN_HALF)
-    hipLaunchKernelGGL((sample_pe_kernel<bf16_t, 12>), dim3(cdiv(P, 128)), dim3(128), 0, as_stream(stream), rays, t_steps,
-                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_out, (bf16_t*)pe_xyz, pe_stride, (const float*)nullptr);
+    hipLaunchKernelGGL((sample_pe_kernel<bf16_t, 12, RNG>), dim3(cdiv(P, 128)), dim3(128), 0, as_stream(stream), rays, t_steps,
+                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_out, (bf16_t*)pe_xyz, pe_stride, (const float*)nullptr, rng);
   else
-    hipLaunchKernelGGL((sample_pe_kernel<float, 12>), dim3(cdiv(P, 64)), dim3(64), 0, as_stream(stream), rays, t_steps,
-                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_out, (float*)pe_xyz, pe_stride, (const float*)nullptr);
+    hipLaunchKernelGGL((sample_pe_kernel<float, 12, RNG>), dim3(cdiv(P, 64)), dim3(64), 0, as_stream(stream), rays, t_steps,
+                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_out, (float*)pe_xyz, pe_stride, (const float*)nullptr, rng);
   SWN_LAUNCH_CHECK();
   if (pe_dir) {
-    SWN_CHECK(dir_stride >= 3 + 6 * l_dir, "swn_sample_pe: dir_stride too small");
+    SWN_CHECK(dir_stride >= 3 + 6 * l_dir, "%s: dir_stride too small", who);
     if (dtype == SWN_HALF)
       hipLaunchKernelGGL((dir_pe_kernel<bf16_t, 12>), dim3(cdiv(n_rays, 256)), dim3(256), 0, as_stream(stream), rays,
                          n_rays, l_dir, (bf16_t*)pe_dir, dir_stride);
@@ -1141,6 +1150,26 @@ extern "C" int swn_sample_pe(const float* rays, const float* t_steps, const floa
     SWN_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int swn_sample_pe(const float* rays, const float* t_steps, const float* perturb_rand, float perturb,
+                             int n_rays, int n_samples, int l_xyz, int l_dir, int dtype, float* z_out, void* pe_xyz,
+                             int pe_stride, void* pe_dir, int dir_stride, void* stream) {
+  return sample_pe_launch<false>("swn_sample_pe", rays, t_steps, perturb_rand, JitterRng{}, perturb, n_rays, n_samples, l_xyz, l_dir, dtype,
+                                 z_out, pe_xyz, pe_stride, pe_dir, dir_stride, stream);
+}
+
+/* swn_sample_pe with the jitter drawn in the kernel (philox.hpp, stream 0) instead of read from perturb_rand[N,S]: z and pe equal, bit
+ * for bit, swn_rng_fill(stream 0, base = ray_base * S) followed by swn_sample_pe */
+extern "C" int swn_sample_pe_rng(const float* rays, const float* t_steps, uint64_t seed, const int64_t* step_dev, int64_t ray_base,
+                                 float perturb, int n_rays, int n_samples, int l_xyz, int l_dir, int dtype, float* z_out, void* pe_xyz,
+                                 int pe_stride, void* pe_dir, int dir_stride, void* stream) {
+  SWN_CHECK(step_dev, "swn_sample_pe_rng: null pointer");
+  SWN_CHECK(n_rays >= 0 && n_samples >= 1, "swn_sample_pe_rng: bad sizes");
+  SWN_CHECK(ray_base >= 0 && ray_base <= (INT64_MAX / n_samples) - n_rays, "swn_sample_pe_rng: ray_base out of range");
+  if (n_rays == 0) return 0;
+  return sample_pe_launch<true>("swn_sample_pe_rng", rays, t_steps, nullptr, JitterRng{seed, step_dev, ray_base * (int64_t)n_samples}, perturb,
+                                n_rays, n_samples, l_xyz, l_dir, dtype, z_out, pe_xyz, pe_stride, pe_dir, dir_stride, stream);
 }
 
 /* positional encoding of xyz = o + d * z for caller-supplied depths z[N,S] (the fine pass: rendering.py:246 xyz_fine_fn) */
@@ -1154,10 +1183,10 @@ extern "C" int swn_pe_from_z(const float* rays, const float* z, int n_rays, int 
   const long P = (long)n_rays * n_samples;
   if (dtype == SWN_HALF)
     hipLaunchKernelGGL((sample_pe_kernel<bf16_t, 12>), dim3(cdiv(P, 128)), dim3(128), 0, as_stream(stream), rays, (const float*)nullptr,
-                       (const float*)nullptr, 0.f, n_rays, n_samples, l_xyz, (float*)nullptr, (bf16_t*)pe_xyz, pe_stride, z);
+                       (const float*)nullptr, 0.f, n_rays, n_samples, l_xyz, (float*)nullptr, (bf16_t*)pe_xyz, pe_stride, z, JitterRng{});
   else
     hipLaunchKernelGGL((sample_pe_kernel<float, 12>), dim3(cdiv(P, 64)), dim3(64), 0, as_stream(stream), rays, (const float*)nullptr,
-                       (const float*)nullptr, 0.f, n_rays, n_samples, l_xyz, (float*)nullptr, (float*)pe_xyz, pe_stride, z);
+                       (const float*)nullptr, 0.f, n_rays, n_samples, l_xyz, (float*)nullptr, (float*)pe_xyz, pe_stride, z, JitterRng{});
   SWN_LAUNCH_CHECK();
   return 0;
 }

@@ -32,7 +32,8 @@ class GraphedTrainStep:
 
     Same result dict as SwitchNeRF.train_step (tensors live in static graph memory: read them before the next call).  The inputs
     are copied into static buffers; stratified jitter (perturb > 0) and the sigma noise (noise_std > 0) are drawn inside the
-    graph from the device generator, like rendering.py:582 / :366.  Only the plain (non-hierarchical, non-mip) step is graphed.
+    graph from the device generator, like rendering.py:582 / :366 - or, with the model's device noise on (set_device_noise), from the
+    seeded generator: the replays then equal the eager steps bit for bit.  Only the plain (non-hierarchical, non-mip) step is graphed.
 
     split_backward (default: on when torch.distributed runs more than one rank): the step is captured as TWO graphs cut behind the
     expert weight gradients (SwitchNeRF.backward_net_a / _b).  Between the replays the all-reduce of the expert block of the flat
@@ -61,13 +62,18 @@ class GraphedTrainStep:
             model._loss_scale_tensor()                     # exists before the capture (it is read, not created, inside the graph)
         ro = None if routing_override is None else routing_override.to(dev).int().contiguous()
 
+        # device noise on (SwitchNeRF.set_device_noise): no noise tensors are passed - the step draws from the seeded generator and its
+        # last launch advances the step counter, so the captured step holds the draws AND the advance
+        dn = model.device_noise
+
         def run():
-            pr = torch.rand(N, S, device=dev) if perturb > 0 else None
-            noise = torch.randn(P, device=dev) * noise_std if noise_std > 0 else None
+            pr = torch.rand(N, S, device=dev) if perturb > 0 and not dn else None
+            noise = torch.randn(P, device=dev) * noise_std if noise_std > 0 and not dn else None
             return model.grad_step(self.rgbs, self.rays, self.idx, S, min(int(seg_tokens), P), perturb=perturb, perturb_rand=pr,
-                                   sigma_noise=noise, routing_override=ro, split=self.split)
+                                   sigma_noise=noise, routing_override=ro, split=self.split, sigma_noise_std=noise_std if dn else 0.0)
 
         was_profile, model.profile = model.profile, False
+        step0 = model.noise_state_dict()["step"]           # the warm-up steps advance the noise counter like real ones: put it back
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up on a side stream: allocates every cached buffer / workspace
@@ -77,6 +83,9 @@ class GraphedTrainStep:
                     model.backward_net_b(r_["bwd_b"])
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if dn:
+            model._noise_step.fill_(step0)
+            torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=side):
             self.res = run()
@@ -192,15 +201,21 @@ class GraphedRenderTrain:
         self.d_rgb = torch.zeros(N, 3, dtype=torch.float32, device=dev)
         chunk = min(int(seg_tokens), N * S)
 
+        dn = model.device_noise          # seeded device noise: the passes draw it themselves; the forward graph ends in the counter's advance
+        std = noise_std if dn else 0.0
+
         def fwd():
-            pr = torch.rand(N, S, device=dev) if perturb > 0 else None                                   # rendering.py:582
-            noise = torch.randn(N * S, device=dev) * noise_std if noise_std > 0 else None                # rendering.py:366
+            pr = torch.rand(N, S, device=dev) if perturb > 0 and not dn else None                        # rendering.py:582
+            noise = torch.randn(N * S, device=dev) * noise_std if noise_std > 0 and not dn else None     # rendering.py:366
             if F > 0:
-                noise_f = torch.randn(N * F, device=dev) * noise_std if noise_std > 0 else None
+                noise_f = torch.randn(N * F, device=dev) * noise_std if noise_std > 0 and not dn else None
                 c, cf, out = model.forward_hier(self.rays, self.idx, S, F, chunk, perturb, pr, None, noise, noise_f,
-                                                no_batch=model.moe_no_batch, training=True)
+                                                no_batch=model.moe_no_batch, training=True, sigma_noise_std=std)
+                model._noise_advance()
                 return (c, cf, out), (out["rgb"], c["l_aux"], cf["l_aux"], out["depth"], out["depth_variance"])
-            c = model.forward_rays(self.rays, self.idx, S, chunk, perturb, pr, noise, training=True, no_batch=model.moe_no_batch)
+            c = model.forward_rays(self.rays, self.idx, S, chunk, perturb, pr, noise, training=True, no_batch=model.moe_no_batch,
+                                   sigma_noise_std=std)
+            model._noise_advance()
             return (c,), (c["rgb"], c["l_aux"], torch.zeros(0, device=dev), c["depth"], c["depth_variance"])
 
         def bwd(state):
@@ -215,6 +230,7 @@ class GraphedRenderTrain:
                 model.backward(state[0], self.d_rgb, self.d_laux_c)
 
         was_profile, model.profile = model.profile, False
+        step0 = model.noise_state_dict()["step"]           # the warm-up passes advance the noise counter: put it back before the capture
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up on the capture stream: allocates every cached buffer / workspace
@@ -225,6 +241,9 @@ class GraphedRenderTrain:
                 bwd(st)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if dn:
+            model._noise_step.fill_(step0)
+            torch.cuda.synchronize()
         self.fwd_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.fwd_graph, stream=side):
             self.state, self.outs = fwd()

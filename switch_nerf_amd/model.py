@@ -509,13 +509,23 @@ class SwitchNeRF:
     # ------------------------------------------------------------------------------------------ forward
     def forward_rays(self, rays, image_indices, n_samples, seg_tokens, perturb=0.0, perturb_rand=None, sigma_noise=None,
                      training=True, routing_override=None, no_batch=False, z_in=None, pe_dir=None, tag="c",
-                     want_weights=False, composite=True):
+                     want_weights=False, composite=True, sigma_noise_std=0.0):
         """One pass of render_rays' _inference (rendering.py:277-494) over N rays x n_samples points: sampling (or the
         caller's depths z_in for the fine pass), positional encoding, the network, and (optionally) compositing.
-        Returns a context dict holding every tensor the backward needs and the rendered results."""
+        Returns a context dict holding every tensor the backward needs and the rendered results.
+        Device noise on (set_device_noise) and a training pass: the jitter (perturb > 0, no perturb_rand) and the sigma noise
+        (sigma_noise_std > 0, no sigma_noise) are drawn from the seeded generator; supplied tensors win."""
         o, dt, dev = ops, self.dtype, self.dev
         N, S = rays.shape[0], n_samples
         self._sync_compute_copies()       # (an optimizer outside this class may have stepped flat_param since the last forward)
+        dn = self._noise if training else None
+        jitter_rng = dn is not None and perturb > 0 and perturb_rand is None and z_in is None
+        drawn = None
+        if dn is not None and sigma_noise is None and sigma_noise_std > 0:
+            sigma_noise = drawn = self._draw(o.RNG_SIGMA if tag == "c" else o.RNG_SIGMA_FINE, N * S, dn["ray_base"] * S, o.RNG_NORMAL,
+                                             float(sigma_noise_std))
+        if jitter_rng and self.hash is not None:      # (the plain path draws it inside swn_sample_pe_rng)
+            perturb_rand = self._draw(o.RNG_JITTER, N * S, dn["ray_base"] * S, o.RNG_UNIFORM).view(N, S)
         if self.hash is not None:         # hash-grid encoding of the sample positions (BASELINE configs[4])
             z = z_in if z_in is not None else o.sample_z(rays, self._linspace(S), perturb_rand,
                                                          perturb, S)
@@ -524,8 +534,12 @@ class SwitchNeRF:
                 pe_dir = self._dir_pe(rays)
         elif z_in is None:
             t_steps = self._linspace(S)
-            z, pe, pe_dir = o.sample_pe(rays, t_steps, perturb_rand, perturb, S, self.cfg["pos_xyz_dim"],
-                                        self.cfg["pos_dir_dim"], dt, self.KP, self.DP)
+            if jitter_rng:
+                z, pe, pe_dir = o.sample_pe_rng(rays, t_steps, dn["seed"], self._noise_step, dn["ray_base"], perturb, S,
+                                                self.cfg["pos_xyz_dim"], self.cfg["pos_dir_dim"], dt, self.KP, self.DP)
+            else:
+                z, pe, pe_dir = o.sample_pe(rays, t_steps, perturb_rand, perturb, S, self.cfg["pos_xyz_dim"],
+                                            self.cfg["pos_dir_dim"], dt, self.KP, self.DP)
         else:
             z = z_in
             pe = o.pe_from_z(rays, z_in, self.cfg["pos_xyz_dim"], dt, self.KP)      # xyz_fine_fn, rendering.py:103
@@ -537,9 +551,73 @@ class SwitchNeRF:
         finally:
             self._saving = True
         c["z"], c["rays"] = z, rays
+        if drawn is not None:
+            c["sigma_noise"] = drawn          # (the draw of this pass, for inspection; a supplied tensor is the caller's)
         if composite:
             c["rgb"], c["depth"], c["depth_variance"], c["weights"] = o.composite_fwd(c["raw"], c["z"], want_weights=want_weights)
         return c
+
+    # ------------------------------------------------------------------------------------------ seeded device noise
+    _noise = None            # {"seed", "ray_base"} while device noise is on
+    _ray_base_pending = 0    # set_ray_base() ahead of a switch-on by rendering.render_rays (hparams.device_noise_seed)
+    _noise_step = None       # the step counter: a device int64[1] owned by the model (the kernels read it, swn_rng_advance bumps it)
+
+    def set_device_noise(self, seed, step: int = 0, ray_base: int = 0):
+        """Seeded device-side noise (csrc/philox.hpp): seed = None turns it off (the default - nothing differs from a model that never
+        called this).  On: a TRAINING forward draws what the caller does not supply - the stratified jitter (perturb > 0), the sigma
+        noise (sigma_noise_std > 0), the fine pass's u and the gate noise - from Philox4x32-10 keyed by (seed, step, stream, global
+        element index), ray i of this call being global ray ray_base + i.  The draw is a pure function of those four: identical in eager
+        mode and in a captured graph, on one GPU and on W GPUs (ray_base = the rank's first global ray), and after a resume
+        (noise_state_dict).  The step lives on the device and is advanced by the last launch of every training step.
+        (A graph captured earlier keeps the seed and ray_base it was captured with; the step it reads from the device.)"""
+        if seed is None:
+            self._noise = None
+            return
+        seed, ray_base = int(seed), int(ray_base)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"device noise: seed {seed} outside [0, 2^64)")
+        if ray_base < 0:
+            raise ValueError(f"device noise: ray_base {ray_base} < 0")
+        step = ops.rng_check_step(step)
+        if self._noise_step is None:
+            self._noise_step = ops.rng_step_tensor(step, self.dev)
+        else:
+            self._noise_step.fill_(step)          # (the same tensor: captured launches hold its address)
+        self._noise = dict(seed=seed, ray_base=ray_base)
+        self._ray_base_pending = ray_base
+
+    @property
+    def device_noise(self) -> bool:
+        return self._noise is not None
+
+    def set_ray_base(self, ray_base: int):
+        """The global index of this model's first ray (data parallel: the rank's slice of the batch, parallel.shard_rays).  Set before
+        the noise is switched on through hparams.device_noise_seed (rendering.render_rays), it is what that switch-on starts with."""
+        if int(ray_base) < 0:
+            raise ValueError(f"device noise: ray_base {ray_base} < 0")
+        self._ray_base_pending = int(ray_base)
+        if self._noise is not None:
+            self._noise["ray_base"] = int(ray_base)
+
+    def noise_state_dict(self) -> dict:
+        """{"seed", "step", "ray_base"} - what a resume needs besides the parameters (seed None: device noise off).  Reads the step
+        back from the device.  Store it next to a checkpoint, e.g. torch.save({**ckpt, "noise_state": model.noise_state_dict()})."""
+        if self._noise is None:
+            return dict(seed=None, step=0, ray_base=0)
+        return dict(seed=self._noise["seed"], step=int(self._noise_step.item()), ray_base=self._noise["ray_base"])
+
+    def load_noise_state_dict(self, sd: dict):
+        self.set_device_noise(sd.get("seed"), int(sd.get("step", 0)), int(sd.get("ray_base", 0)))
+
+    def _draw(self, stream_id: int, n: int, elem_base: int, kind: int, scale: float = 1.0):
+        """n draws of a stream from global element elem_base on -> f32 [n] (swn_rng_fill; consumed through the supplied-noise arguments)."""
+        return ops.rng_fill(n, elem_base, kind, self._noise["seed"], self._noise_step, stream_id, scale)
+
+    def _noise_advance(self):
+        """The step counter's advance: the LAST launch of a training step (inside a captured step).  Nothing with device noise off."""
+        if self._noise is not None:
+            step = self._noise_step
+            ops.rng_advance(step)
 
     def _dir_pe(self, rays):
         """PE of the ray directions only (per ray)."""
@@ -691,6 +769,9 @@ class SwitchNeRF:
                     x_features=self.KP if big else 0)
         if not (sv and self.gate_noise > 0):       # (training only, like `self.training and self.gate_noise > 0`)
             return None
+        if self.gate_noise_draw is None and self._noise is not None:     # stream 4, element (ray_base * S + point) * E + expert
+            r0 = 0 if row_range is None else row_range[0]
+            return self._draw(o.RNG_GATE, P * E, (self._noise["ray_base"] * S + r0) * E, o.RNG_NORMAL).view(P, E)
         if self.gate_noise_draw is None:
             return torch.randn(P, E, device=dev, dtype=torch.float32)
         # a supplied draw (tests): [N * S, E] of this pass's point grid; a row range takes its rows
@@ -1212,15 +1293,16 @@ class SwitchNeRF:
     # ------------------------------------------------------------------------------------------ training step
     def train_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, perturb_rand=None,
                    sigma_noise=None, optimizer_step=True, routing_override=None, grad_allreduce=None, fine_samples=0,
-                   fine_u=None, sigma_noise_fine=None):
-        """Runner._training_step + loss assembly + backward + Adam (runner.py:1077-1123, 646-686) = grad_step + apply_step."""
+                   fine_u=None, sigma_noise_fine=None, sigma_noise_std=0.0):
+        """Runner._training_step + loss assembly + backward + Adam (runner.py:1077-1123, 646-686) = grad_step + apply_step.
+        sigma_noise_std: with device noise on (set_device_noise) the std of the sigma noise the step draws itself where none is supplied."""
         res = self.grad_step(rgbs, rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise, routing_override,
-                             fine_samples, fine_u, sigma_noise_fine)
+                             fine_samples, fine_u, sigma_noise_fine, sigma_noise_std=sigma_noise_std)
         self.apply_step(grad_allreduce, optimizer_step)
         return res
 
     def grad_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, perturb_rand=None, sigma_noise=None,
-                  routing_override=None, fine_samples=0, fine_u=None, sigma_noise_fine=None, split=False):
+                  routing_override=None, fine_samples=0, fine_u=None, sigma_noise_fine=None, split=False, sigma_noise_std=0.0):
         """Forward + loss + backward of one training step: fills self.grad (zeroed first) and returns the metrics.  Nothing here
         depends on host state that changes from step to step, so the whole launch sequence can be captured into a hipGraph
         (graph.GraphedTrainStep).  split=True (plain step only) stops after backward_net_a - the expert block of the gradient is final,
@@ -1233,10 +1315,10 @@ class SwitchNeRF:
         fine = fine_samples > 0
         if not fine:
             c = out = self.forward_rays(rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise, True,
-                                        routing_override)
+                                        routing_override, sigma_noise_std=sigma_noise_std)
         else:
             c, cf, out = self.forward_hier(rays, image_indices, n_samples, fine_samples, seg_tokens, perturb, perturb_rand,
-                                           fine_u, sigma_noise, sigma_noise_fine, routing_override)
+                                           fine_u, sigma_noise, sigma_noise_fine, routing_override, sigma_noise_std=sigma_noise_std)
         # loss (F.mse_loss runner.py:1099, + wt * gate loss :646-651, :1104-1111), psnr and the gradient seeds in ONE launch
         # (swn_step_loss); scaler.scale(loss).backward() (runner.py:679): the scale is read from a DEVICE scalar (kept equal to
         # loss_scaler.scale by _unscale_ok), so a captured step (graph.GraphedTrainStep) follows the scale as it adapts between replays
@@ -1262,6 +1344,7 @@ class SwitchNeRF:
             res["ctx_fine"] = cf
         if split:
             res["bwd_b"] = bwd_b
+        self._noise_advance()              # device noise: the next step draws at step + 1 (the last launch of the captured step)
         return res
 
     def apply_step(self, grad_allreduce=None, optimizer_step=True, refresh=None):
@@ -1321,21 +1404,26 @@ class SwitchNeRF:
         return self.grad
 
     def forward_hier(self, rays, image_indices, n_samples, fine_samples, seg_tokens, perturb=0.0, perturb_rand=None,
-                     fine_u=None, sigma_noise=None, sigma_noise_fine=None, routing_override=None, no_batch=False, training=True):
+                     fine_u=None, sigma_noise=None, sigma_noise_fine=None, routing_override=None, no_batch=False, training=True,
+                     sigma_noise_std=0.0):
         """_get_results with fine_samples > 0 and no cascade (rendering.py:199-274): coarse pass (weights only, its raw
         outputs kept), importance sampling of the fine depths from the detached coarse weights, fine pass on those
         depths, sort-merge of both sample sets (:419-433) and compositing of the union.
         Returns (coarse ctx, fine ctx, merged results {raw, z, order, rgb, depth, depth_variance})."""
         N = rays.shape[0]
         c = self.forward_rays(rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise, training,
-                              routing_override, no_batch=no_batch, want_weights=True)
+                              routing_override, no_batch=no_batch, want_weights=True, sigma_noise_std=sigma_noise_std)
+        if fine_u is None and perturb != 0 and training and self._noise is not None:      # device noise: stream 2
+            fine_u = self._draw(ops.RNG_FINE_U, N * fine_samples, self._noise["ray_base"] * fine_samples,
+                                ops.RNG_UNIFORM).view(N, fine_samples)
         if fine_u is None:                                                # det = (perturb == 0): linspace, else rand (:605-609)
             fine_u = (self._linspace(fine_samples).expand(N, fine_samples).contiguous() if perturb == 0
                       else torch.rand(N, fine_samples, device=self.dev))
         z_fine = ops.sample_pdf(c["z"], c["weights"], fine_u, fine_samples)
         seg_f = min(seg_tokens, N * fine_samples)
         cf = self.forward_rays(rays, image_indices, fine_samples, seg_f, 0.0, None, sigma_noise_fine, training, None,
-                               no_batch=no_batch, z_in=z_fine, pe_dir=c["pe_dir"], tag="f", composite=False)
+                               no_batch=no_batch, z_in=z_fine, pe_dir=c["pe_dir"], tag="f", composite=False,
+                               sigma_noise_std=sigma_noise_std)
         zm, order, raw_m = ops.merge_samples(z_fine, c["z"], cf["raw"], c["raw"])
         out = dict(raw=raw_m, z=zm, order=order, z_fine=z_fine)
         out["rgb"], out["depth"], out["depth_variance"], _ = ops.composite_fwd(raw_m, zm)
@@ -1343,7 +1431,7 @@ class SwitchNeRF:
 
     # ------------------------------------------------------------------------------------------ mip path
     def forward_level_mip(self, rays, radii, image_indices, z, seg_tokens, sigma_noise=None, no_batch=False, tag="c",
-                          want_weights=False, rgb_padding=0.001, pe_dir=None, training=True):
+                          want_weights=False, rgb_padding=0.001, pe_dir=None, training=True, sigma_noise_std=0.0):
         """One level of rendering_mip._get_results (rendering_mip.py:195-215 / :236-253): the S edges `z` of every ray give
         S - 1 conical frustums; integrated positional encoding (swn_mip_encode) -> the same network (MipNeRFMoE.forward is
         NeRFMoE.forward behind MipEmbedder, nerf_moe.py:675-810) -> compositing at the frustum mid points with the colour
@@ -1354,12 +1442,18 @@ class SwitchNeRF:
         if pe_dir is None:
             pe_dir = self._dir_pe(rays)
         seg = min(seg_tokens, N * S1)
+        drawn = None
+        if training and self._noise is not None and sigma_noise is None and sigma_noise_std > 0:      # one value per interval
+            sigma_noise = drawn = self._draw(ops.RNG_SIGMA if tag == "c" else ops.RNG_SIGMA_FINE, N * S1, self._noise["ray_base"] * S1,
+                                     ops.RNG_NORMAL, float(sigma_noise_std))
         self._saving = bool(training)      # inference: no activation saves / ReLU masks (like forward_rays)
         try:
             c = self._net_forward(pe, pe_dir, image_indices, N, S1, seg, sigma_noise, None, no_batch, tag)
         finally:
             self._saving = True
         c["z_edges"] = z
+        if drawn is not None:
+            c["sigma_noise"] = drawn
         c["z"] = (0.5 * (z[:, 1:] + z[:, :-1])).contiguous()
         c["rgb_padding"] = float(rgb_padding)
         c["rgb"], c["depth"], c["depth_variance"], c["weights"] = ops.composite_fwd(c["raw"], c["z"], want_weights=want_weights,
@@ -1368,7 +1462,7 @@ class SwitchNeRF:
 
     def forward_mip(self, rays, radii, image_indices, n_samples, n_fine, seg_tokens, perturb=0.0, perturb_rand=None, fine_u=None,
                     sigma_noise=None, sigma_noise_fine=None, no_batch=False, rgb_padding=0.001, resample_padding=0.01,
-                    training=True, fine_randomized=None):
+                    training=True, fine_randomized=None, sigma_noise_std=0.0):
         """rendering_mip.render_rays (rendering_mip.py:133-172): coarse level on n_samples edges, then (n_fine > 0) the fine
         level on n_fine edges resampled from the blurred coarse weights (stop_level_grad: no gradient through the edges).
         fine_u: the U[0,1) tensor [N, n_fine] of sorted_piecewise_constant_pdf1's randomized branch (drawn here if perturb > 0
@@ -1380,26 +1474,31 @@ class SwitchNeRF:
             fine_randomized = perturb > 0
         t_steps = self._linspace(n_samples)
         radii = radii.reshape(-1).contiguous()
+        dn = self._noise if training else None
+        if dn is not None and perturb > 0 and perturb_rand is None:       # device noise: stream 0 through the fill
+            perturb_rand = self._draw(ops.RNG_JITTER, N * n_samples, dn["ray_base"] * n_samples, ops.RNG_UNIFORM).view(N, n_samples)
         z = ops.sample_z(rays, t_steps, perturb_rand, perturb, n_samples)
         c = self.forward_level_mip(rays, radii, image_indices, z, seg_tokens, sigma_noise, no_batch, "c", n_fine > 0, rgb_padding,
-                                   training=training)
+                                   training=training, sigma_noise_std=sigma_noise_std)
         if n_fine <= 0:
             return c, None
+        if fine_u is None and fine_randomized and dn is not None:          # stream 2
+            fine_u = self._draw(ops.RNG_FINE_U, N * n_fine, dn["ray_base"] * n_fine, ops.RNG_UNIFORM).view(N, n_fine)
         if fine_u is None and fine_randomized:
             fine_u = torch.rand(N, n_fine, device=self.dev)
         z_f = ops.mip_resample(z, c["weights"], fine_u if fine_randomized else None, n_fine, resample_padding)
         cf = self.forward_level_mip(rays, radii, image_indices, z_f, seg_tokens, sigma_noise_fine, no_batch, "f", False, rgb_padding,
-                                    pe_dir=c["pe_dir"], training=training)
+                                    pe_dir=c["pe_dir"], training=training, sigma_noise_std=sigma_noise_std)
         return c, cf
 
     def train_step_mip(self, rgbs, rays, radii, image_indices, n_samples, n_fine, seg_tokens, perturb=1.0, perturb_rand=None,
                        fine_u=None, sigma_noise=None, sigma_noise_fine=None, optimizer_step=True, grad_allreduce=None,
-                       rgb_padding=0.001, resample_padding=0.01):
+                       rgb_padding=0.001, resample_padding=0.01, sigma_noise_std=0.0):
         """Runner._training_step_mip (runner.py:1126-1167): loss = (mse(rgb_fine) + mse(rgb_coarse)) / 2
         + wt * (mean(gate_loss_fine) + mean(gate_loss_coarse)) / 2, backward through both levels, Adam."""
         self.grad.zero_()
         c, cf = self.forward_mip(rays, radii, image_indices, n_samples, n_fine, seg_tokens, perturb, perturb_rand, fine_u,
-                                 sigma_noise, sigma_noise_fine, False, rgb_padding, resample_padding)
+                                 sigma_noise, sigma_noise_fine, False, rgb_padding, resample_padding, sigma_noise_std=sigma_noise_std)
         levels = [c] if cf is None else [cf, c]
         share = 1.0 / len(levels)
         photo, gate_loss = 0.0, 0.0
@@ -1414,6 +1513,7 @@ class SwitchNeRF:
             d_raw = ops.composite_bwd(lv["raw"], lv["z"], lv["_d_rgb"], rgb_padding=lv["rgb_padding"])
             d_laux = torch.full((lv["n_seg"],), share * self.wt / lv["n_seg"], dtype=torch.float32, device=self.dev) * ls
             self.backward_net(lv, d_raw, d_laux)
+        self._noise_advance()
         self.apply_step(grad_allreduce, optimizer_step)
         top = levels[0]
         return dict(loss=loss, photo_loss=photo, gate_loss=gate_loss, psnr=-10.0 * torch.log10(((top["rgb"] - rgbs) ** 2).mean()),

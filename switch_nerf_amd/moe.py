@@ -401,16 +401,26 @@ class MoELayer(nn.Module):
         ex = self.experts[0]
         noise = clean = None
         E = self.n_experts
-        draw = lambda given: (given.to(x.device, torch.float32).reshape(-1, E).contiguous() if given is not None
-                              else torch.randn(x.shape[0], E, device=x.device, dtype=torch.float32))
+        dn, drew = self._noise, []
+
+        def draw(given, stream_id):
+            if given is not None:
+                return given.to(x.device, torch.float32).reshape(-1, E).contiguous()
+            if dn is not None:                 # seeded device noise (set_device_noise): element (row_base + p) * E + e of the stream
+                drew.append(stream_id)
+                return ops.rng_fill(x.shape[0] * E, dn["row_base"] * E, ops.RNG_NORMAL, dn["seed"], self._noise_step,
+                                    stream_id).view(-1, E)
+            return torch.randn(x.shape[0], E, device=x.device, dtype=torch.float32)
         if self.training and self.use_normal_noise:            # logits + n1 / E (+ gate_noise * n2 / E) = logits + (n1 + gate_noise * n2) / E
-            noise = clean = draw(normal_noise_draw)    # (clean: the part that belongs to `logits` in the load / importance loss, :116-117)
+            noise = clean = draw(normal_noise_draw, ops.RNG_ROUTER_NORMAL)    # (clean: the part that belongs to `logits` in the load / importance loss, :116-117)
             if self.gate_noise > 0:
-                noise = noise + self.gate_noise * draw(gate_noise_draw)
+                noise = noise + self.gate_noise * draw(gate_noise_draw, ops.RNG_GATE)
             self._noise_scale = 1.0 / E
         elif self.training and self.gate_noise > 0:
-            noise = draw(gate_noise_draw)
+            noise = draw(gate_noise_draw, ops.RNG_GATE)
             self._noise_scale = self.gate_noise / E
+        if drew:
+            ops.rng_advance(self._noise_step)      # the next training forward draws at step + 1
         l_bal = None
         if self.top_k == 1 and not self.use_load_importance_loss:
             y, l_aux, idx = _MoEFunction.apply(self, x, g, self.gates[0].wg.weight, noise, *ex.weights, *ex.bias)
@@ -428,6 +438,34 @@ class MoELayer(nn.Module):
         if extras:
             y.gate_extras = extras
         return y
+
+    _noise = None            # {"seed", "row_base"} while seeded device noise is on
+    _noise_step = None       # its step counter: a device int64[1] owned by the layer
+
+    def set_device_noise(self, seed, step: int = 0, row_base: int = 0, device="cuda"):
+        """The switch of SwitchNeRF.set_device_noise for this layer's router noise: seed = None (default) draws with torch.randn as
+        before; a seed draws the gate noise (and the use_normal_noise draw, a stream of its own) of a TRAINING forward from the library's
+        Philox generator keyed by (seed, step, stream, (row_base + token) * E + expert); the counter advances once per forward that drew.
+        Supplied draws (gate_noise_draw / normal_noise_draw) still win."""
+        if seed is None:
+            self._noise = None
+            return
+        if not 0 <= int(seed) < 1 << 64 or int(row_base) < 0:
+            raise ValueError("device noise: seed outside [0, 2^64) or row_base < 0")
+        step = ops.rng_check_step(step)
+        if self._noise_step is None:
+            self._noise_step = ops.rng_step_tensor(step, device)
+        else:
+            self._noise_step.fill_(step)
+        self._noise = dict(seed=int(seed), row_base=int(row_base))
+
+    def noise_state_dict(self) -> dict:
+        if self._noise is None:
+            return dict(seed=None, step=0, row_base=0)
+        return dict(seed=self._noise["seed"], step=int(self._noise_step.item()), row_base=self._noise["row_base"])
+
+    def load_noise_state_dict(self, sd: dict):
+        self.set_device_noise(sd.get("seed"), int(sd.get("step", 0)), int(sd.get("row_base", 0)))
 
     def _residual(self, x, y_moe):
         """y_moe * c0 + residual_expert(x) * c1, c = softmax(coefficient(x)) (tutel_moe_layer_nobatch.py:777-788), on x in the layer

@@ -68,6 +68,61 @@ def sample_pe(rays, t_steps, perturb_rand, perturb: float, n_samples: int, l_xyz
     return z, pe, pd
 
 
+# ---- seeded device-side noise (csrc/philox.hpp, csrc/rng.hip): Philox4x32-10 keyed by (seed, step, stream id, global element index).
+# The stream ids are fixed (the same table as philox.hpp); element index e of each:
+RNG_JITTER = 0          # coarse stratified jitter     (ray_base + n) * S + s
+RNG_SIGMA = 1           # coarse sigma noise           (ray_base + n) * R + r, R rows per ray (S; S - 1 intervals for mip)
+RNG_FINE_U = 2          # fine-pass u                  (ray_base + n) * F + f
+RNG_SIGMA_FINE = 3      # fine sigma noise             as RNG_SIGMA with the fine row count
+RNG_GATE = 4            # gate noise                   (ray_base * R + p) * E + e
+RNG_ROUTER_NORMAL = 5   # moe.MoELayer's use_normal_noise draw, addressed like RNG_GATE
+RNG_UNIFORM, RNG_NORMAL = 0, 1
+
+
+def rng_check_step(step: int) -> int:
+    """The step is the third counter word of the generator: it must fit 32 bits (checked where the host sets it)."""
+    step = int(step)
+    if not 0 <= step < 1 << 32:
+        raise ValueError(f"device noise: step {step} outside [0, 2^32)")
+    return step
+
+
+def rng_step_tensor(step: int, device) -> torch.Tensor:
+    """The device int64[1] the kernels read the step from (a captured launch follows it from replay to replay)."""
+    return torch.full((1,), rng_check_step(step), dtype=torch.int64, device=device)
+
+
+def rng_fill(n: int, base: int, kind: int, seed: int, step_dev, stream_id: int, scale: float = 1.0, out=None):
+    """-> out [n] f32: out[i] = the draw of element base + i of (seed, step_dev[0], stream_id); RNG_UNIFORM in [0, 1) or
+    RNG_NORMAL * scale."""
+    assert step_dev.dtype == torch.int64 and step_dev.numel() == 1
+    if out is None:
+        out = torch.empty(int(n), dtype=torch.float32, device=step_dev.device)
+    assert out.dtype == torch.float32 and out.numel() == int(n)
+    call("swn_rng_fill", _p(out), int(n), int(base), int(kind), float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev), int(stream_id),
+         _stream())
+    return out
+
+
+def rng_advance(step_dev):
+    """step_dev[0] += 1 on the device (one launch: the last one of a training step, inside a captured step)."""
+    assert step_dev.dtype == torch.int64 and step_dev.numel() == 1
+    call("swn_rng_advance", _p(step_dev), _stream())
+
+
+def sample_pe_rng(rays, t_steps, seed: int, step_dev, ray_base: int, perturb: float, n_samples: int, l_xyz: int, l_dir: int, dtype,
+                  pe_stride: int, dir_stride: int):
+    """sample_pe with the jitter (stream RNG_JITTER) drawn inside the kernel: no [N,S] noise buffer.
+    -> z [N,S] f32, pe_xyz [N*S, pe_stride] dtype, pe_dir [N, dir_stride] dtype"""
+    n = rays.shape[0]
+    z = torch.empty(n, n_samples, dtype=torch.float32, device=rays.device)
+    pe = torch.empty(n * n_samples, pe_stride, dtype=dtype, device=rays.device)
+    pd = torch.empty(n, dir_stride, dtype=dtype, device=rays.device)
+    call("swn_sample_pe_rng", _p(rays), _p(t_steps), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev), int(ray_base), float(perturb), n,
+         n_samples, l_xyz, l_dir, _dt(pe), _p(z), _p(pe), pe_stride, _p(pd), dir_stride, _stream())
+    return z, pe, pd
+
+
 def pe_from_z(rays, z, l_xyz: int, dtype, pe_stride: int):
     n, S = z.shape
     pe = torch.empty(n * S, pe_stride, dtype=dtype, device=rays.device)

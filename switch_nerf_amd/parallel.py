@@ -55,10 +55,13 @@ def shutdown(timeout_s: float = 20.0, exit_code: int = 0):
     dog.cancel()
 
 
-def shard_rays(n_rays: int, rank: int, world: int) -> Tuple[int, int]:
+def shard_rays(n_rays: int, rank: int, world: int, model=None) -> Tuple[int, int]:
     """Contiguous per-rank slice [begin, end) of a global ray batch (runner.py:575: batch_size // world_size each;
-    the remainder, if any, is dropped like DataLoader(drop_last) would)."""
+    the remainder, if any, is dropped like DataLoader(drop_last) would).  model: its seeded device noise (SwitchNeRF.set_device_noise)
+    is told the slice's first global ray, so that ray i of the global batch draws the same noise at every world size."""
     per = n_rays // world
+    if model is not None and hasattr(model, "set_ray_base"):
+        model.set_ray_base(rank * per)
     return rank * per, (rank + 1) * per
 
 

@@ -50,6 +50,30 @@ def _point_keys(res, hparams, typ, rays, raw_pass, z, raw, last_delta=1e10, z_pt
 
 
 
+def _device_noise(nerf, bg_nerf, hparams) -> bool:
+    """hparams.device_noise_seed (absent / None: off): seeded device-side noise (SwitchNeRF.set_device_noise), switched on ONCE per model
+    with the seed - the step counter then runs on.  An optional hparams.ray_base (the global index of this process's first ray) is
+    honoured on every call; absent (or None), the model keeps the ray_base it has (parallel.shard_rays(..., model=nerf), set_ray_base).
+    Returns whether the model draws its own noise."""
+    seed = getattr(hparams, "device_noise_seed", None)
+    if seed is None and not getattr(nerf, "device_noise", False):
+        return False
+    if bg_nerf is not None:
+        raise NotImplementedError("device_noise_seed with a background model (bg_nerf): the background's rays are a data-dependent "
+                                  "subset without a global index; its noise is not seeded - turn one of the two off")
+    if not hasattr(nerf, "set_device_noise"):
+        raise NotImplementedError("device_noise_seed: the model has no seeded device noise")
+    if seed is None:                      # (switched on by the caller: SwitchNeRF.set_device_noise)
+        return True
+    ray_base = getattr(hparams, "ray_base", None)
+    if not nerf.device_noise or nerf._noise["seed"] != int(seed):
+        keep = nerf._noise["ray_base"] if nerf.device_noise else getattr(nerf, "_ray_base_pending", 0)
+        nerf.set_device_noise(int(seed), 0, keep if ray_base is None else int(ray_base))
+    elif ray_base is not None:
+        nerf.set_ray_base(int(ray_base))
+    return True
+
+
 def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch.Tensor], hparams, sphere_center=None,
                 sphere_radius=None, get_depth: bool = True, get_depth_variance: bool = True,
                 get_bg_fg_rgb: bool = False) -> Tuple[Dict[str, torch.Tensor], bool]:
@@ -58,6 +82,7 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
     F = int(getattr(hparams, "fine_samples", 0))
     N = rays.shape[0]
     S = hparams.coarse_samples
+    dn = _device_noise(nerf, bg_nerf, hparams) and nerf.training
     if bg_nerf is not None:
         return _render_rays_bg(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, sphere_radius, get_depth,
                                get_depth_variance, get_bg_fg_rgb)
@@ -73,6 +98,8 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
     if under_autograd and getattr(nerf, "graph_train", False) and getattr(nerf, "ep", None) is None:
         # forward / backward replayed from captured graphs (graph.GraphedRenderTrain); jitter and sigma noise are drawn inside them
         pr, noise, noise_f = "graph", (float(hparams.sigma_noise_std) if use_noise else 0.0), None
+    elif dn:       # seeded device noise: the passes draw jitter / sigma noise / fine u themselves (noise = the std), then advance the step
+        pr, noise, noise_f = None, (float(hparams.sigma_noise_std) if use_noise else 0.0), None
     else:
         pr = torch.rand(N, S, device=rays.device) if perturb > 0 else None
         noise = torch.randn(P, device=rays.device) * hparams.sigma_noise_std if use_noise else None      # rendering.py:366
@@ -107,9 +134,14 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
         return res, False
     if not nerf.training and getattr(nerf, "graph_eval", False) and getattr(nerf, "ep", None) is None and not _want_points(hparams):
         return _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get_depth, get_depth_variance), False
+    std = 0.0
+    if dn:
+        std, noise = noise, None
     if F > 0:
         c, cf, out = nerf.forward_hier(rays.contiguous(), image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
-                                       no_batch=nerf.moe_no_batch, training=nerf.training)
+                                       no_batch=nerf.moe_no_batch, training=nerf.training, sigma_noise_std=std)
+        if dn:
+            nerf._noise_advance()
         res = {"rgb_fine": out["rgb"], "gate_loss_coarse": c["l_aux"], "gate_loss_fine": cf["l_aux"]}
         if get_depth:
             res["depth_fine"] = out["depth"]
@@ -125,7 +157,9 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
         _point_keys(res, hparams, "fine", rays, cf["raw"], out["z"], out["raw"], z_pts=out["z_fine"], order=out["order"])
         return res, False
     c = nerf.forward_rays(rays.contiguous(), image_indices, S, chunk, float(perturb), pr, noise, training=nerf.training,
-                          no_batch=nerf.moe_no_batch)
+                          no_batch=nerf.moe_no_batch, sigma_noise_std=std)
+    if dn:
+        nerf._noise_advance()
     res = {"rgb_coarse": c["rgb"], "gate_loss_coarse": c["l_aux"]}
     if get_depth:
         res["depth_coarse"] = c["depth"]
@@ -227,10 +261,14 @@ def render_rays_mip(nerf, rays: torch.Tensor, radii: torch.Tensor, image_indices
     N = rays.shape[0]
     S, F = hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
     perturb = hparams.perturb if nerf.training else 0
-    pr = torch.rand(N, S, device=rays.device) if perturb > 0 else None
+    dn = _device_noise(nerf, None, hparams) and nerf.training      # seeded device noise: forward_mip draws what is not supplied
+    pr = torch.rand(N, S, device=rays.device) if perturb > 0 and not dn else None
     chunk = hparams.model_chunk_size
     noise = noise_f = None
-    if getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and nerf.training:
+    std = 0.0
+    if dn and getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0:
+        std = float(hparams.sigma_noise_std)
+    elif getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and nerf.training:
         noise = torch.randn(N * (S - 1), device=rays.device) * hparams.sigma_noise_std
         noise_f = torch.randn(N * max(F - 1, 0), device=rays.device) * hparams.sigma_noise_std if F > 0 else None
     if image_indices is None:
@@ -238,7 +276,10 @@ def render_rays_mip(nerf, rays: torch.Tensor, radii: torch.Tensor, image_indices
     c, cf = nerf.forward_mip(rays.contiguous(), radii, image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
                              no_batch=nerf.moe_no_batch, rgb_padding=float(getattr(hparams, "rgb_padding", 0.001) or 0.0),
                              resample_padding=float(getattr(hparams, "weights_resample_padding", 0.01)), training=nerf.training,
-                             fine_randomized=bool(hparams.perturb))      # rendering_mip.py:227: randomized=hparams.perturb, also in eval
+                             fine_randomized=bool(hparams.perturb),      # rendering_mip.py:227: randomized=hparams.perturb, also in eval
+                             sigma_noise_std=std)
+    if dn:
+        nerf._noise_advance()
     res = {"rgb_coarse": c["rgb"], "gate_loss_coarse": c["l_aux"]}
     top, typ = (c, "coarse") if cf is None else (cf, "fine")
     if cf is not None:
