@@ -52,18 +52,31 @@ int swn_sample_pe(const float* rays, const float* t_steps, const float* perturb_
 
 /* ---- seeded device-side noise (csrc/philox.hpp, csrc/rng.hip) ---------------------------------------------------
  * Philox4x32-10 keyed by (seed, step, stream id, GLOBAL element index): element e is word (e & 3) of block e >> 2,
- * counter = {block_lo, block_hi, step, stream id}, key = {seed_lo, seed_hi}.  The step (< 2^32, checked where the host sets
- * it) is read from DEVICE memory (step_dev: int64[1]) by the kernels, so a launch captured into a hipGraph follows it.
+ * counter = {block_lo, block_hi, step, stream id | (domain << 8)}, key = {seed_lo, seed_hi}.  The step (< 2^32, checked where the
+ * host sets it) is read from DEVICE memory (step_dev: int64[1]) by the kernels, so a launch captured into a hipGraph follows it.
  * Stream ids: 0 coarse jitter, 1 coarse sigma noise, 2 fine u, 3 fine sigma noise, 4 gate noise, 5 router normal noise.
+ * Domains: 0 every draw of a model of its own (swn_rng_fill, swn_sample_pe_rng); 1 the background model of a scene, whose rays are
+ *   addressed through their position in the batch (streams 0-3; csrc/philox.hpp has the element index of each).
  * swn_rng_fill: out[i] = the draw of element base + i (base need not be a multiple of 4); kind 0: uniform
  *   (x >> 8) 2^-24 in [0, 1); kind 1: standard normal (Box-Muller over the word pairs (0,1), (2,3)) times scale.
  * swn_rng_advance: *step_dev += 1, one thread - the last launch of a training step.
  * swn_sample_pe_rng: swn_sample_pe with the jitter (stream 0, element (ray_base + ray) * n_samples + s) drawn inside the
- *   kernel: z_out / pe_xyz / pe_dir equal swn_rng_fill(stream 0, base = ray_base * n_samples) + swn_sample_pe bit for bit. */
+ *   kernel: z_out / pe_xyz / pe_dir equal swn_rng_fill(stream 0, base = ray_base * n_samples) + swn_sample_pe bit for bit.
+ * swn_rng_fill_rows: the generator addressed through a row index: out[j * per_row + s] = the draw of element
+ *   (row_base + row_index[j]) * per_row + s of (seed, *step_dev, stream_id, domain), j < n_rows.  row_index: int64[n_rows] on the
+ *   device, unsorted and with repeats allowed, every entry in [0, index_limit); NULL = the identity (the limit is then at least
+ *   n_rows).  index_limit only bounds the element index for the overflow check ((row_base + index_limit) * per_row must fit int64);
+ *   row_index is never used as a memory offset.  A normal draw keeps the pairing of the GLOBAL element (an odd per_row makes rows
+ *   share a Box-Muller pair; each takes its own half).  row_index NULL and domain 0 equal
+ *   swn_rng_fill(n_rows * per_row, row_base * per_row, ...) bit for bit. */
 #define SWN_RNG_UNIFORM 0
 #define SWN_RNG_NORMAL 1
+#define SWN_RNG_DOMAIN_FG 0
+#define SWN_RNG_DOMAIN_BG 1
 int swn_rng_fill(float* out, int64_t n, int64_t base, int kind, float scale, uint64_t seed, const int64_t* step_dev,
                  int stream_id, void* stream);
+int swn_rng_fill_rows(float* out, int64_t n_rows, int64_t per_row, int64_t row_base, const int64_t* row_index, int64_t index_limit,
+                      int kind, float scale, uint64_t seed, const int64_t* step_dev, int stream_id, int domain, void* stream);
 int swn_rng_advance(int64_t* step_dev, void* stream);
 int swn_sample_pe_rng(const float* rays, const float* t_steps, uint64_t seed, const int64_t* step_dev, int64_t ray_base,
                       float perturb, int n_rays, int n_samples, int l_xyz, int l_dir, int dtype, float* z_out, void* pe_xyz,
@@ -408,6 +421,10 @@ int swn_hash_encode_bwd_binned(const float* rays, const float* z, int n_rays, in
  *   z_in != NULL: the caller's depths (hierarchical pass :246), everything in the order of z_in.
  *   Points: _depth2pts_outside (:521-570, include_xyz_real False): unit-sphere point rotated by Rodrigues' formula + the
  *   inverse distance -> 4-D, encoded with l_xyz octaves (4 + 8 l_xyz columns, zero-padded to pe_stride elements of `dtype`).
+ * swn_bg_sample_pe_rng: the coarse pass of swn_bg_sample_pe with the jitter drawn inside the kernel from the seeded generator
+ *   (domain 1, stream 0): ray r of this call is global ray ray_base + row_index[r] (row_index: int64[n_rays] on the device, entries
+ *   in [0, index_limit), NULL = the identity) and its ascending sample a draws element (ray_base + row_index[r]) * n_samples + a.
+ *   Equals swn_rng_fill_rows(uniform, domain 1, stream 0, per_row = n_samples) + swn_bg_sample_pe bit for bit.
  * swn_composite_bounded_fwd / _bwd: volumetric compositing (:435-494) with a per-ray last delta (last_delta [n_rays] or
  *   NULL = 1e10), flip != 0 for descending depths (:436-437), depth_real [n_rays, n_samples] or NULL as the depth map's
  *   source (:483-484) and bg_lambda [n_rays] or NULL = the transmittance behind the last sample (:456-457); the backward
@@ -417,6 +434,10 @@ int swn_fg_bounds(const float* rays, const float* center_host, const float* radi
 int swn_bg_sample_pe(const float* rays, const float* center_host, const float* radius_host, const float* t_steps,
                      const float* perturb_rand, float perturb, int n_rays, int n_samples, int l_xyz, int dtype,
                      const float* z_in, float* z_out, float* depth_real, void* pe, int pe_stride, void* stream);
+int swn_bg_sample_pe_rng(const float* rays, const float* center_host, const float* radius_host, const float* t_steps, uint64_t seed,
+                         const int64_t* step_dev, int64_t ray_base, const int64_t* row_index, int64_t index_limit, float perturb,
+                         int n_rays, int n_samples, int l_xyz, int dtype, float* z_out, float* depth_real, void* pe, int pe_stride,
+                         void* stream);
 int swn_composite_bounded_fwd(const float* raw, const float* z, const float* last_delta, int flip, const float* depth_real,
                               int n_rays, int n_samples, float* rgb, float* depth, float* depth_var, float* weights,
                               float* bg_lambda, void* stream);

@@ -69,6 +69,7 @@ SIGNATURES = {
     "swn_sample_pe": [vp, vp, vp, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp],
     "swn_sample_pe_rng": [vp, vp, u64, vp, i64, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp],
     "swn_rng_fill": [vp, i64, i64, i32, f32, u64, vp, i32, vp],
+    "swn_rng_fill_rows": [vp, i64, i64, i64, vp, i64, i32, f32, u64, vp, i32, i32, vp],
     "swn_rng_advance": [vp, vp],
     "swn_pe_from_z": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
     "swn_sample_pdf": [vp, vp, vp, i32, i32, i32, vp, vp],
@@ -110,6 +111,7 @@ SIGNATURES = {
     "swn_mip_resample": [vp, vp, vp, f32, i32, i32, i32, vp, vp],
     "swn_fg_bounds": [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp],
     "swn_bg_sample_pe": [vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp],
+    "swn_bg_sample_pe_rng": [vp, vp, vp, vp, u64, vp, i64, vp, i64, f32, i32, i32, i32, i32, vp, vp, vp, i32, vp],
     "swn_composite_bounded_fwd": [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp],
     "swn_composite_bounded_bwd": [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp],
     "swn_point_fields": [vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp],

@@ -14,6 +14,11 @@ With fine_samples > 0 both models run the hierarchical pass (fine_samples // 2 f
 quirk is mirrored deliberately: the background's importance sampling pairs the ASCENDING bin mid points (:238 uses
 _get_results' own un-flipped z_vals) with the coarse weights in FLIPPED order (computed by _inference on its flipped
 copy, :302-304), and its depth map reads the un-flipped depth_real (:483-484); tests/golden/bg_train_*.npz pin both.
+
+Seeded device noise (BackgroundScene.set_device_noise; csrc/philox.hpp): the scene owns the state and ONE device step counter for both
+models.  The foreground model draws its own streams through that counter exactly as it does without a background; the background's
+draws live in the generator's second domain and are addressed through each background ray's position in the batch (idx_bg), so a
+background ray's noise depends on (seed, step, global ray) only - not on which other rays of the batch leave the bound.
 """
 from __future__ import annotations
 
@@ -49,7 +54,8 @@ class BackgroundScene:
 
     def detach(self):
         """Undo the scaler sharing: each model gets back the LossScaler (or None) it had before the scene was built; a model that owned
-        one continues from the shared scale."""
+        one continues from the shared scale.  The foreground model gets back the noise state it had before set_device_noise."""
+        self.set_device_noise(None)
         for m, own in zip((self.nerf, self.bg), self._own_scalers):
             if own is not None and self.loss_scaler is not None and own is not self.loss_scaler:
                 own.load_state_dict(self.loss_scaler.state_dict())
@@ -57,17 +63,98 @@ class BackgroundScene:
             if own is None:
                 m._ls_dev = None
 
+    # ------------------------------------------------------------------------------------------ seeded device noise
+    _noise = None            # {"seed", "ray_base"} while the scene's device noise is on
+    _noise_step = None       # the ONE step counter of both models: a device int64[1] (the foreground model holds the same tensor)
+    _fg_own_noise = None     # the foreground model's (_noise, _noise_step, _ray_base_pending) from before the switch-on
+
+    def set_device_noise(self, seed, step: int = 0, ray_base: int = 0):
+        """Seeded device-side noise for both models (SwitchNeRF.set_device_noise has the contract); seed = None switches it off and hands
+        the foreground model back the noise state it had.  On: the foreground model is switched on with the same seed and the SAME counter
+        tensor, so it draws its streams as it does without a background; a TRAINING forward draws what the caller does not supply for the
+        background model - jitter, coarse / fine sigma noise (noise_std > 0), fine u - from the generator's background domain, background
+        row j being global ray ray_base + idx_bg[j].  train_step ends in one advance of the counter."""
+        nerf = self.nerf
+        if seed is None:
+            if self._noise is not None:
+                nerf._noise, nerf._noise_step, nerf._ray_base_pending = self._fg_own_noise
+                nerf._noise_scene = None
+            self._noise = self._fg_own_noise = None
+            return
+        seed, ray_base = int(seed), int(ray_base)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"device noise: seed {seed} outside [0, 2^64)")
+        if ray_base < 0:
+            raise ValueError(f"device noise: ray_base {ray_base} < 0")
+        step = ops.rng_check_step(step)
+        if self._noise_step is None:
+            self._noise_step = ops.rng_step_tensor(step, self.dev)
+        else:
+            self._noise_step.fill_(step)
+        if self._noise is None:
+            self._fg_own_noise = (nerf._noise, nerf._noise_step, nerf._ray_base_pending)
+        self._noise = dict(seed=seed, ray_base=ray_base)
+        nerf._noise, nerf._noise_step, nerf._ray_base_pending = dict(seed=seed, ray_base=ray_base), self._noise_step, ray_base
+        nerf._noise_scene = self             # (rendering._device_noise: this model's noise is the scene's business)
+
+    @property
+    def device_noise(self) -> bool:
+        return self._noise is not None
+
+    def set_ray_base(self, ray_base: int):
+        """The global index of this process's first ray (parallel.shard_rays(..., model=scene)), for both models.  Nothing to set while
+        the noise is off: set_device_noise takes the ray_base it starts with."""
+        if int(ray_base) < 0:
+            raise ValueError(f"device noise: ray_base {ray_base} < 0")
+        if self._noise is not None:
+            self._noise["ray_base"] = int(ray_base)
+            self.nerf.set_ray_base(ray_base)
+
+    def noise_state_dict(self) -> dict:
+        """{"seed", "step", "ray_base"} of the scene (both models): what a resume needs besides the parameters.  Reads the step back."""
+        if self._noise is None:
+            return dict(seed=None, step=0, ray_base=0)
+        return dict(seed=self._noise["seed"], step=int(self._noise_step.item()), ray_base=self._noise["ray_base"])
+
+    def load_noise_state_dict(self, sd: dict):
+        self.set_device_noise(sd.get("seed"), int(sd.get("step", 0)), int(sd.get("ray_base", 0)))
+
+    def _noise_advance(self):
+        """The one advance of the shared step counter that ends a training step.  Nothing with the noise off."""
+        if self._noise is not None:
+            ops.rng_advance(self._noise_step)
+
+    def _check_noise_sources(self):
+        """Never mix the two noise sources silently: a model drawing seeded noise of its own inside a scene that draws the background's
+        from the framework generator (or from another counter) is an error."""
+        nerf, bg = self.nerf, self.bg
+        if getattr(bg, "device_noise", False):
+            raise RuntimeError("BackgroundScene: the background model's own device noise is on (bg_nerf.set_device_noise): the scene "
+                               "carries the noise of both models - turn it off there and call BackgroundScene.set_device_noise(seed)")
+        if self._noise is None and getattr(nerf, "device_noise", False):
+            raise RuntimeError("BackgroundScene: the foreground model's device noise is on but the scene's is not, so the background "
+                               "would draw from the framework generator - call BackgroundScene.set_device_noise(seed) instead of "
+                               "the model's set_device_noise (or turn the model's off)")
+        if self._noise is not None and (nerf._noise_step is not self._noise_step or nerf._noise is None
+                                        or nerf._noise["seed"] != self._noise["seed"]):
+            raise RuntimeError("BackgroundScene: the foreground model's device noise was changed behind the scene's back "
+                               "(SwitchNeRF.set_device_noise after BackgroundScene.set_device_noise): set it on the scene")
+
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, rays, image_indices, n_samples, seg_tokens, perturb=0.0, perturb_rand=None, perturb_rand_bg=None,
                 sigma_noise=None, sigma_noise_bg=None, fine_samples=0, fine_u=None, fine_u_bg=None, sigma_noise_fine=None,
-                sigma_noise_bg_fine=None, no_batch=False, noise_std=0.0, training=True):
+                sigma_noise_bg_fine=None, no_batch=False, noise_std=0.0, training=True, ray_index=None):
         """sigma_noise_bg / sigma_noise_bg_fine: [Nb * samples] tensors, or the string "randn" to draw noise_std * N(0,1)
-        here (the number of background rays is only known inside)."""
+        here (the number of background rays is only known inside).
+        The scene's device noise on (set_device_noise) and a training pass: what is not supplied is drawn from the seeded generator -
+        the foreground's as SwitchNeRF does it (sigma noise of std noise_std), the background's jitter inside swn_bg_sample_pe_rng, its
+        sigma noise (noise_std > 0; "randn" or None) and fine u through swn_rng_fill_rows; the drawn tensors are kept in ctx["bg"]
+        ("sigma_noise", "fine_u", "sigma_noise_fine").  Supplied tensors win.
+        ray_index (int64 [N], optional): the position in the full batch of each ray of this call - the BACKGROUND's draws are addressed
+        by ray_base + ray_index[i] instead of ray_base + i (a call on a subset of a batch reproduces that batch's background draws)."""
         o, nerf, bg = ops, self.nerf, self.bg
-        if getattr(nerf, "device_noise", False) or getattr(bg, "device_noise", False):
-            # the background's rays are a data-dependent subset: no global index to key its noise by - never mix the two sources silently
-            raise NotImplementedError("seeded device noise (set_device_noise / device_noise_seed) with a background model is not "
-                                      "implemented: turn it off (set_device_noise(None)) for scenes with a bg_nerf")
+        self._check_noise_sources()
+        dn = self._noise if training else None
         N, S, Fn = rays.shape[0], n_samples, int(fine_samples)
         rays_fg, fg_far, last0, has_bg, n_out = o.fg_bounds(rays, self.center, self.radius)
         idx_bg = has_bg.nonzero().view(-1)                      # rays_with_bg, rendering.py:36 (host sync, like the reference)
@@ -82,11 +169,23 @@ class BackgroundScene:
             Sb = S // 2
             rays_b = rays.index_select(0, idx_bg).contiguous()
             img_b = image_indices.index_select(0, idx_bg).contiguous()
-            if perturb > 0 and perturb_rand_bg is None:
-                perturb_rand_bg = torch.rand(Nb, Sb, device=self.dev)
-            z_b, dreal_b, pe_b = o.bg_sample_pe(rays_b, self.center, self.radius, Sb, bg.cfg["pos_xyz_dim"], bg.dtype, bg.KP,
-                                                perturb_rand_bg, float(perturb), pe_out=bg._buf("c:pe", (Nb * Sb, bg.KP), bg.dtype))
+            drawn = {}
+            if dn is not None:               # background row j is global ray ray_base + rows[j]; every entry < lim
+                rows, lim = (idx_bg, N) if ray_index is None else (ray_index.index_select(0, idx_bg), int(ray_index.max().item()) + 1)
+                draw = lambda stream, per_row, kind, scale=1.0: o.rng_fill_rows(
+                    Nb, per_row, dn["ray_base"], rows, kind, dn["seed"], self._noise_step, stream, o.RNG_DOMAIN_BG, scale, lim)
+            if dn is not None and perturb > 0 and perturb_rand_bg is None:
+                z_b, dreal_b, pe_b = o.bg_sample_pe_rng(rays_b, self.center, self.radius, Sb, bg.cfg["pos_xyz_dim"], bg.dtype, bg.KP,
+                                                        dn["seed"], self._noise_step, dn["ray_base"], rows, lim, float(perturb),
+                                                        pe_out=bg._buf("c:pe", (Nb * Sb, bg.KP), bg.dtype))
+            else:
+                if perturb > 0 and perturb_rand_bg is None:
+                    perturb_rand_bg = torch.rand(Nb, Sb, device=self.dev)
+                z_b, dreal_b, pe_b = o.bg_sample_pe(rays_b, self.center, self.radius, Sb, bg.cfg["pos_xyz_dim"], bg.dtype, bg.KP,
+                                                    perturb_rand_bg, float(perturb), pe_out=bg._buf("c:pe", (Nb * Sb, bg.KP), bg.dtype))
             pe_dir_b = bg._dir_pe(rays_b)
+            if dn is not None and noise_std > 0 and (sigma_noise_bg is None or isinstance(sigma_noise_bg, str)):
+                sigma_noise_bg = drawn["sigma_noise"] = draw(o.RNG_SIGMA, Sb, o.RNG_NORMAL, float(noise_std)).view(-1)
             if isinstance(sigma_noise_bg, str):
                 sigma_noise_bg = torch.randn(Nb * Sb, device=self.dev) * noise_std
             cb = bg._net_forward(pe_b, pe_dir_b, img_b, Nb, Sb, Nb * Sb, sigma_noise_bg, None, False, "c")
@@ -95,8 +194,12 @@ class BackgroundScene:
             b = dict(c=cb, raw=cb["raw"], z=z_b)
             if Fn > 0:
                 Fb = Fn // 2
+                if dn is not None and fine_u_bg is None and perturb != 0:
+                    fine_u_bg = drawn["fine_u"] = draw(o.RNG_FINE_U, Fb, o.RNG_UNIFORM)
                 if fine_u_bg is None:
                     fine_u_bg = det_u(Nb, Fb)
+                if dn is not None and noise_std > 0 and (sigma_noise_bg_fine is None or isinstance(sigma_noise_bg_fine, str)):
+                    sigma_noise_bg_fine = drawn["sigma_noise_fine"] = draw(o.RNG_SIGMA_FINE, Fb, o.RNG_NORMAL, float(noise_std)).view(-1)
                 if isinstance(sigma_noise_bg_fine, str):
                     sigma_noise_bg_fine = torch.randn(Nb * Fb, device=self.dev) * noise_std
                 z_f = o.sample_pdf(z_b.flip(-1).contiguous(), w_b, fine_u_bg, Fb)        # ascending bins x flipped weights (see module doc)
@@ -109,21 +212,24 @@ class BackgroundScene:
                 dreal_m = torch.gather(torch.cat([dreal_f, dreal_b], 1), 1, order.long())    # :432-433
                 rgb_b, depth_b, _, _, _ = o.composite_bounded_fwd(raw_m, z_m, None, True, dreal_m)
                 b.update(cf=cfb, raw=raw_m, z=z_m, order=order, z_fine=z_f)
-            b.update(rgb=rgb_b, depth=depth_b)
+            b.update(rgb=rgb_b, depth=depth_b, **drawn)       # (the draws of this pass, for inspection; a supplied tensor is the caller's)
             ctx["bg"] = b
         # ---- foreground on the clipped rays
         bg._saving = True
+        std_fg = float(noise_std) if dn is not None else 0.0       # device noise: the foreground draws its own sigma noise (streams 1 / 3)
         c = nerf.forward_rays(rays_fg, image_indices, S, seg_tokens, perturb, perturb_rand, sigma_noise, training, None,
-                              no_batch=no_batch, want_weights=Fn > 0, composite=Fn > 0)
+                              no_batch=no_batch, want_weights=Fn > 0, composite=Fn > 0, sigma_noise_std=std_fg)
         ctx["c"] = c
         if Fn == 0:
             raw, z, z_last = c["raw"], c["z"], c["z"][:, -1]              # stratified depths ascend: the last one is the maximum (:217)
         else:
+            if dn is not None and fine_u is None and perturb != 0:          # stream 2, as SwitchNeRF.forward_hier draws it
+                fine_u = nerf._draw(o.RNG_FINE_U, N * Fn, dn["ray_base"] * Fn, o.RNG_UNIFORM).view(N, Fn)
             if fine_u is None:
                 fine_u = det_u(N, Fn)
             z_fine = o.sample_pdf(c["z"], c["weights"], fine_u, Fn)
             cf = nerf.forward_rays(rays_fg, image_indices, Fn, min(seg_tokens, N * Fn), 0.0, None, sigma_noise_fine, training, None,
-                                   no_batch=no_batch, z_in=z_fine, pe_dir=c["pe_dir"], tag="f", composite=False)
+                                   no_batch=no_batch, z_in=z_fine, pe_dir=c["pe_dir"], tag="f", composite=False, sigma_noise_std=std_fg)
             z, order, raw = o.merge_samples(z_fine, c["z"], cf["raw"], c["raw"])
             z_last = z_fine.max(dim=-1)[0]                               # the FINE depths' maximum (:249-250)
             ctx.update(cf=cf, order=order, z_fine=z_fine)
@@ -220,5 +326,6 @@ class BackgroundScene:
                 m.step_count += 1
                 ops.adam_step(m.flat, m.grad, m.m, m.v, None, m.step_count, m.lr, grad_scale=sc)
                 m.refresh_compute_copies()
+        self._noise_advance()              # device noise: ONE advance per step, with or without background rays / a background Adam step
         return dict(loss=loss, photo_loss=photo, gate_loss=gate_loss, psnr=-10.0 * torch.log10(photo), rgb=ctx["rgb"],
                     depth=ctx["depth"], depth_variance=ctx["depth_variance"].mean(), ctx=ctx, bg_nerf_rays_present=bg_present)

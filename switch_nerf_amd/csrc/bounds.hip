@@ -2,10 +2,12 @@
 //   fg_bounds_kernel     where a ray leaves the (ellipsoidal) foreground bound, which rays continue into the background
 //                        model, the clipped far plane and the last sample's delta
 //   bg_sample_pe_kernel  the background's inverse-distance samples (stratified, flipped), their NeRF++ inverted-sphere
-//                        points (unit-sphere point + 1/r), metric depths, and the 4-D positional encoding
+//                        points (unit-sphere point + 1/r), metric depths, and the 4-D positional encoding; its RNG instantiation
+//                        (swn_bg_sample_pe_rng) draws the jitter in place from the seeded generator's background domain
 // fp32 arithmetic in the reference's operation order (fma contraction off), one thread per ray / per sample.
 #include "common.hpp"
 #include "pe_store.hpp"
+#include "philox.hpp"
 
 namespace swn {
 
@@ -69,11 +71,16 @@ __global__ __launch_bounds__(256) void fg_bounds_kernel(const float* __restrict_
 //   sequence (:302-304), so z_out / pe are written in descending-depth order j, while depth_real stays in ascending order
 //   a (the reference never flips it, :483-484 reads it as is).
 // z_in != nullptr: depths supplied (hierarchical pass, :246 xyz_fine_fn): no flip, everything in the order of z_in.
-template <typename T, int LMAX>
+// RNG (swn_bg_sample_pe_rng): the jitter of (ray, a) is not read from prand but drawn in place - philox.hpp domain 1, stream 0, element
+//   (ray_base + row_index[ray]) * S + a, row_index[ray] = the (gathered) ray's position in the batch (nullptr: the identity).
+struct BgJitterRng { uint64_t seed; const int64_t* step_dev; int64_t ray_base; const int64_t* row_index; };
+
+template <typename T, int LMAX, bool RNG = false>
 __global__ __launch_bounds__(128) void bg_sample_pe_kernel(const float* __restrict__ rays, Bound bd, const float* __restrict__ tsteps,
                                                            const float* __restrict__ prand, float perturb, int n_rays, int S, int L,
                                                            const float* __restrict__ z_in, float* __restrict__ z_out,
-                                                           float* __restrict__ depth_real, T* __restrict__ pe, int pe_stride) {
+                                                           float* __restrict__ depth_real, T* __restrict__ pe, int pe_stride,
+                                                           BgJitterRng rng = BgJitterRng{}) {
 #pragma clang fp contract(off)
   const long total = (long)n_rays * S;
   const long p_raw = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,10 +93,17 @@ __global__ __launch_bounds__(128) void bg_sample_pe_kernel(const float* __restri
     z = z_in[p];
   } else {
     z = tsteps[a];                                                                        // linspace(0, 1, S), :46
-    if (perturb > 0.f && prand) {                                                         // :573-584
+    if (perturb > 0.f && (RNG || prand)) {                                                // :573-584
       const float lower = a > 0 ? 0.5f * (tsteps[a - 1] + z) : z;
       const float upper = a < S - 1 ? 0.5f * (z + tsteps[a + 1]) : z;
-      const float pr = perturb * prand[(long)ray * S + a];
+      float u;
+      if constexpr (RNG) {
+        const int64_t g = rng.ray_base + (rng.row_index ? rng.row_index[ray] : (int64_t)ray);
+        u = philox_uniform_at(rng.seed, (uint32_t)*rng.step_dev, RNG_STREAM_JITTER, g * S + a, RNG_DOMAIN_BG);
+      } else {
+        u = prand[(long)ray * S + a];
+      }
+      const float pr = perturb * u;
       z = lower + (upper - lower) * pr;
     }
   }
@@ -197,24 +211,54 @@ extern "C" int swn_fg_bounds(const float* rays, const float* center_host, const 
   return 0;
 }
 
-extern "C" int swn_bg_sample_pe(const float* rays, const float* center_host, const float* radius_host, const float* t_steps,
-                                const float* perturb_rand, float perturb, int n_rays, int n_samples, int l_xyz, int dtype,
-                                const float* z_in, float* z_out, float* depth_real, void* pe, int pe_stride, void* stream) {
-  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "swn_bg_sample_pe: bad dtype");
-  SWN_CHECK(rays && pe && (z_in || t_steps), "swn_bg_sample_pe: null pointer");
-  SWN_CHECK((center_host == nullptr) == (radius_host == nullptr), "swn_bg_sample_pe: center / radius must both be given or both NULL");
-  SWN_CHECK(l_xyz >= 0 && l_xyz <= 12, "swn_bg_sample_pe: frequencies must be <= 12");
+// swn_bg_sample_pe / swn_bg_sample_pe_rng: the checks and the launch; RNG selects the jitter's source
+template <bool RNG>
+static int bg_sample_pe_launch(const char* who, const float* rays, const float* center_host, const float* radius_host, const float* t_steps,
+                               const float* perturb_rand, BgJitterRng rng, float perturb, int n_rays, int n_samples, int l_xyz, int dtype,
+                               const float* z_in, float* z_out, float* depth_real, void* pe, int pe_stride, void* stream) {
+  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "%s: bad dtype", who);
+  SWN_CHECK(rays && pe && (z_in || t_steps), "%s: null pointer", who);
+  SWN_CHECK((center_host == nullptr) == (radius_host == nullptr), "%s: center / radius must both be given or both NULL", who);
+  SWN_CHECK(l_xyz >= 0 && l_xyz <= 12, "%s: frequencies must be <= 12", who);
   const int epc = dtype == SWN_HALF ? 8 : 4;
-  SWN_CHECK(pe_stride >= 4 + 8 * l_xyz && pe_stride % epc == 0, "swn_bg_sample_pe: pe_stride %d too small / unaligned", pe_stride);
+  SWN_CHECK(pe_stride >= 4 + 8 * l_xyz && pe_stride % epc == 0, "%s: pe_stride %d too small / unaligned", who, pe_stride);
   if (n_rays <= 0) return 0;
   const long P = (long)n_rays * n_samples;
   const Bound b = make_bound(center_host, radius_host);
   if (dtype == SWN_HALF)
-    hipLaunchKernelGGL((bg_sample_pe_kernel<bf16_t, 12>), dim3(cdiv(P, 128)), dim3(128), 0, as_stream(stream), rays, b, t_steps,
-                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_in, z_out, depth_real, (bf16_t*)pe, pe_stride);
+    hipLaunchKernelGGL((bg_sample_pe_kernel<bf16_t, 12, RNG>), dim3(cdiv(P, 128)), dim3(128), 0, as_stream(stream), rays, b, t_steps,
+                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_in, z_out, depth_real, (bf16_t*)pe, pe_stride, rng);
   else
-    hipLaunchKernelGGL((bg_sample_pe_kernel<float, 12>), dim3(cdiv(P, 64)), dim3(64), 0, as_stream(stream), rays, b, t_steps,
-                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_in, z_out, depth_real, (float*)pe, pe_stride);
+    hipLaunchKernelGGL((bg_sample_pe_kernel<float, 12, RNG>), dim3(cdiv(P, 64)), dim3(64), 0, as_stream(stream), rays, b, t_steps,
+                       perturb_rand, perturb, n_rays, n_samples, l_xyz, z_in, z_out, depth_real, (float*)pe, pe_stride, rng);
   SWN_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int swn_bg_sample_pe(const float* rays, const float* center_host, const float* radius_host, const float* t_steps,
+                                const float* perturb_rand, float perturb, int n_rays, int n_samples, int l_xyz, int dtype,
+                                const float* z_in, float* z_out, float* depth_real, void* pe, int pe_stride, void* stream) {
+  return bg_sample_pe_launch<false>("swn_bg_sample_pe", rays, center_host, radius_host, t_steps, perturb_rand, BgJitterRng{}, perturb,
+                                    n_rays, n_samples, l_xyz, dtype, z_in, z_out, depth_real, pe, pe_stride, stream);
+}
+
+/* swn_bg_sample_pe's coarse pass with the jitter drawn in the kernel (philox.hpp: domain 1, stream 0) instead of read from
+ * perturb_rand[n_rays, n_samples]: z_out / depth_real / pe equal, bit for bit, swn_rng_fill_rows(uniform, domain 1, stream 0, per_row =
+ * n_samples, the same row_base / row_index) followed by swn_bg_sample_pe */
+extern "C" int swn_bg_sample_pe_rng(const float* rays, const float* center_host, const float* radius_host, const float* t_steps,
+                                    uint64_t seed, const int64_t* step_dev, int64_t ray_base, const int64_t* row_index,
+                                    int64_t index_limit, float perturb, int n_rays, int n_samples, int l_xyz, int dtype, float* z_out,
+                                    float* depth_real, void* pe, int pe_stride, void* stream) {
+  SWN_CHECK(step_dev, "swn_bg_sample_pe_rng: step_dev is NULL");
+  SWN_CHECK(t_steps, "swn_bg_sample_pe_rng: t_steps is NULL");
+  SWN_CHECK(n_rays >= 0 && n_samples >= 1, "swn_bg_sample_pe_rng: bad sizes (n_rays %d, n_samples %d)", n_rays, n_samples);
+  SWN_CHECK(ray_base >= 0, "swn_bg_sample_pe_rng: ray_base must be >= 0");
+  SWN_CHECK(index_limit >= 0, "swn_bg_sample_pe_rng: index_limit must be >= 0");
+  const int64_t limit = row_index ? index_limit : (index_limit > n_rays ? index_limit : (int64_t)n_rays);
+  SWN_CHECK(ray_base <= INT64_MAX - limit && ray_base + limit <= INT64_MAX / n_samples,
+            "swn_bg_sample_pe_rng: n_samples %d overflows the element index ((ray_base + index_limit) * n_samples)", n_samples);
+  if (n_rays == 0) return 0;
+  return bg_sample_pe_launch<true>("swn_bg_sample_pe_rng", rays, center_host, radius_host, t_steps, nullptr,
+                                   BgJitterRng{seed, step_dev, ray_base, row_index}, perturb, n_rays, n_samples, l_xyz, dtype, nullptr,
+                                   z_out, depth_real, pe, pe_stride, stream);
 }

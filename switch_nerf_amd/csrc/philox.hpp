@@ -3,7 +3,16 @@
 // generator's history.  Header only; the integer part compiles for the host too (known-answer checks).
 //
 // Addressing: element e (int64, global) is word (e & 3) of block b = e >> 2;
-//   counter = {b_lo, b_hi, step (u32), stream id}, key = {seed_lo, seed_hi}.
+//   counter = {b_lo, b_hi, step (u32), stream id | (domain << 8)}, key = {seed_lo, seed_hi}.
+// Domains: 0 = the foreground model (and every consumer without a background model: the counter word is the bare stream id);
+//   1 = the background model of a scene (background.BackgroundScene).  Its draws reuse the stream ids 0-3, and its rays - a
+//   data-dependent subset of the batch - are addressed through their position in the batch: background row j is global ray
+//   g = ray_base + idx_bg[j], so a background ray's noise depends on (seed, step, global ray) only, not on which other rays leave
+//   the bound.  With Sb / Fb the background's coarse / fine sample counts:
+//     stream 0 jitter      e = g * Sb + a   (a: the ASCENDING sample index, the order of swn_bg_sample_pe's perturb_rand)
+//     stream 1 sigma noise e = g * Sb + j   (j: the row order the network evaluates = descending depth)
+//     stream 2 fine u      e = g * Fb + f        stream 3 fine sigma noise  e = g * Fb + f
+//   swn_rng_fill_rows (rng.hip) is the generator addressed through such a row index.
 // Uniform: u = (x >> 8) * 2^-24 in [0, 1) (torch.rand's range).
 // Normal (Box-Muller over the word pairs (0,1) and (2,3)): u1 = ((x_a >> 8) + 1) * 2^-24 in (0, 1] (never inf),
 //   r = sqrtf(-2 logf(u1)), theta = 2 pi (x_b >> 8) 2^-24; the even word gets r cos(theta), the odd word r sin(theta).
@@ -24,6 +33,7 @@ enum : int {
   RNG_STREAM_ROUTER_NORMAL = 5, // moe.MoELayer's use_normal_noise draw, addressed like stream 4
   RNG_STREAMS = 6
 };
+enum : int { RNG_DOMAIN_FG = 0, RNG_DOMAIN_BG = 1, RNG_DOMAINS = 2 };
 
 struct PhiloxWords { uint32_t w[4]; };
 
@@ -48,17 +58,18 @@ __host__ __device__ __forceinline__ PhiloxWords philox4x32_10(uint32_t c0, uint3
   return PhiloxWords{{c0, c1, c2, c3}};
 }
 
-// the four words of block `block` of (seed, step, stream)
-__host__ __device__ __forceinline__ PhiloxWords philox_block(uint64_t seed, uint32_t step, int stream_id, int64_t block) {
+// the four words of block `block` of (seed, step, stream, domain); domain 0 leaves the counter word the bare stream id
+__host__ __device__ __forceinline__ PhiloxWords philox_block(uint64_t seed, uint32_t step, int stream_id, int64_t block, int domain = 0) {
   const uint64_t b = (uint64_t)block;
-  return philox4x32_10((uint32_t)b, (uint32_t)(b >> 32), step, (uint32_t)stream_id, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return philox4x32_10((uint32_t)b, (uint32_t)(b >> 32), step, (uint32_t)stream_id | ((uint32_t)domain << 8), (uint32_t)seed,
+                       (uint32_t)(seed >> 32));
 }
 
 __host__ __device__ __forceinline__ float philox_uniform(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }   // 2^-24
 
-// the uniform draw of ONE element (a consumer kernel drawing in place: sample_pe_kernel's jitter)
-__device__ __forceinline__ float philox_uniform_at(uint64_t seed, uint32_t step, int stream_id, int64_t e) {
-  const PhiloxWords v = philox_block(seed, step, stream_id, e >> 2);
+// the uniform draw of ONE element (a consumer kernel drawing in place: the jitter of sample_pe_kernel / bg_sample_pe_kernel)
+__device__ __forceinline__ float philox_uniform_at(uint64_t seed, uint32_t step, int stream_id, int64_t e, int domain = 0) {
+  const PhiloxWords v = philox_block(seed, step, stream_id, e >> 2, domain);
   return philox_uniform(v.w[e & 3]);
 }
 

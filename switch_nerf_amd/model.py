@@ -561,6 +561,7 @@ class SwitchNeRF:
     _noise = None            # {"seed", "ray_base"} while device noise is on
     _ray_base_pending = 0    # set_ray_base() ahead of a switch-on by rendering.render_rays (hparams.device_noise_seed)
     _noise_step = None       # the step counter: a device int64[1] owned by the model (the kernels read it, swn_rng_advance bumps it)
+    _noise_scene = None      # the background.BackgroundScene that carries this model's noise (its seed, ITS counter tensor), if any
 
     def set_device_noise(self, seed, step: int = 0, ray_base: int = 0):
         """Seeded device-side noise (csrc/philox.hpp): seed = None turns it off (the default - nothing differs from a model that never

@@ -77,6 +77,12 @@ RNG_SIGMA_FINE = 3      # fine sigma noise             as RNG_SIGMA with the fin
 RNG_GATE = 4            # gate noise                   (ray_base * R + p) * E + e
 RNG_ROUTER_NORMAL = 5   # moe.MoELayer's use_normal_noise draw, addressed like RNG_GATE
 RNG_UNIFORM, RNG_NORMAL = 0, 1
+# Domains (counter word 3 = stream id | (domain << 8)): the draws above are domain 0.  Domain 1 is the background model of a scene
+# (background.BackgroundScene): the stream ids 0-3 again, background row j being global ray g = ray_base + idx_bg[j] (its position in the
+# batch), Sb / Fb the background's coarse / fine sample counts:
+#   RNG_JITTER g * Sb + a (a: ascending sample)   RNG_SIGMA g * Sb + j (j: evaluated row, descending depth)
+#   RNG_FINE_U g * Fb + f                          RNG_SIGMA_FINE g * Fb + f
+RNG_DOMAIN_FG, RNG_DOMAIN_BG = 0, 1
 
 
 def rng_check_step(step: int) -> int:
@@ -101,6 +107,32 @@ def rng_fill(n: int, base: int, kind: int, seed: int, step_dev, stream_id: int, 
     assert out.dtype == torch.float32 and out.numel() == int(n)
     call("swn_rng_fill", _p(out), int(n), int(base), int(kind), float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev), int(stream_id),
          _stream())
+    return out
+
+
+def _row_index_arg(row_index, n_rows: int, index_limit):
+    """row_index (int64 [n_rows] device tensor or None = identity) and the exclusive bound of its entries the library checks the element
+    index's overflow with (the entries address the generator only, never memory)."""
+    if row_index is None:
+        return None, max(int(index_limit or 0), int(n_rows))
+    assert row_index.dtype == torch.int64 and row_index.numel() == int(n_rows)
+    if index_limit is None:
+        raise ValueError("row_index needs index_limit (an exclusive upper bound of its entries, e.g. the rays of the batch)")
+    return row_index, int(index_limit)
+
+
+def rng_fill_rows(n_rows: int, per_row: int, row_base: int, row_index, kind: int, seed: int, step_dev, stream_id: int,
+                  domain: int = RNG_DOMAIN_FG, scale: float = 1.0, index_limit=None, out=None):
+    """-> out [n_rows, per_row] f32: out[j, s] = the draw of element (row_base + row_index[j]) * per_row + s of (seed, step_dev[0],
+    stream_id, domain).  row_index: int64 [n_rows] (unsorted, repeats allowed, entries in [0, index_limit)) or None = the identity."""
+    assert step_dev.dtype == torch.int64 and step_dev.numel() == 1
+    n_rows, per_row = int(n_rows), int(per_row)
+    row_index, limit = _row_index_arg(row_index, n_rows, index_limit)
+    if out is None:
+        out = torch.empty(max(n_rows, 0), max(per_row, 0), dtype=torch.float32, device=step_dev.device)
+    assert out.dtype == torch.float32 and out.numel() == n_rows * per_row
+    call("swn_rng_fill_rows", _p(out), n_rows, per_row, int(row_base), _p(row_index), limit, int(kind), float(scale),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev), int(stream_id), int(domain), _stream())
     return out
 
 
@@ -776,6 +808,24 @@ def bg_sample_pe(rays, center, radius, n_samples, l_xyz, dtype, pe_stride, pertu
     t_steps = torch.linspace(0, 1, S, dtype=torch.float32).to(dev) if z_in is None else None
     call("swn_bg_sample_pe", _p(rays), _host3(center), _host3(radius), _p(t_steps), _p(perturb_rand), float(perturb), N, S, int(l_xyz),
          _code(dtype), _p(z_in), _p(z) if z_in is None else None, _p(dreal), _p(pe), int(pe_stride), _stream())
+    return z, dreal, pe
+
+
+def bg_sample_pe_rng(rays, center, radius, n_samples, l_xyz, dtype, pe_stride, seed: int, step_dev, ray_base: int, row_index=None,
+                     index_limit=None, perturb=1.0, pe_out=None):
+    """bg_sample_pe's coarse pass with the jitter (domain RNG_DOMAIN_BG, stream RNG_JITTER) drawn inside the kernel: no [N,S] noise buffer.
+    Ray r is global ray ray_base + row_index[r] (None: r).  -> z [N,S], depth_real [N,S], pe."""
+    assert step_dev.dtype == torch.int64 and step_dev.numel() == 1
+    N, S = rays.shape[0], int(n_samples)
+    dev = rays.device
+    row_index, limit = _row_index_arg(row_index, N, index_limit)
+    z = torch.empty(N, S, dtype=torch.float32, device=dev)
+    dreal = torch.empty(N, S, dtype=torch.float32, device=dev)
+    pe = pe_out if pe_out is not None else torch.empty(N * S, pe_stride, dtype=dtype, device=dev)
+    t_steps = torch.linspace(0, 1, S, dtype=torch.float32).to(dev)
+    call("swn_bg_sample_pe_rng", _p(rays), _host3(center), _host3(radius), _p(t_steps), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev),
+         int(ray_base), _p(row_index), limit, float(perturb), N, S, int(l_xyz), _code(dtype), _p(z), _p(dreal), _p(pe), int(pe_stride),
+         _stream())
     return z, dreal, pe
 
 

@@ -54,13 +54,20 @@ def _device_noise(nerf, bg_nerf, hparams) -> bool:
     """hparams.device_noise_seed (absent / None: off): seeded device-side noise (SwitchNeRF.set_device_noise), switched on ONCE per model
     with the seed - the step counter then runs on.  An optional hparams.ray_base (the global index of this process's first ray) is
     honoured on every call; absent (or None), the model keeps the ray_base it has (parallel.shard_rays(..., model=nerf), set_ray_base).
-    Returns whether the model draws its own noise."""
+    Returns whether the model draws its own noise.  A model whose noise is carried by a BackgroundScene (BackgroundScene.set_device_noise
+    marks it) does not: the scene draws for both models and advances the one counter (_render_rays_bg)."""
     seed = getattr(hparams, "device_noise_seed", None)
-    if seed is None and not getattr(nerf, "device_noise", False):
+    by_scene = getattr(nerf, "_noise_scene", None) is not None
+    if seed is None and (by_scene or not getattr(nerf, "device_noise", False)):
         return False
+    if by_scene:
+        raise RuntimeError("device_noise_seed: this model's noise is carried by a BackgroundScene (BackgroundScene.set_device_noise); "
+                           "switch that off (set_device_noise(None) / detach()) before seeding the model on its own")
     if bg_nerf is not None:
-        raise NotImplementedError("device_noise_seed with a background model (bg_nerf): the background's rays are a data-dependent "
-                                  "subset without a global index; its noise is not seeded - turn one of the two off")
+        raise NotImplementedError("device_noise_seed with a background model (bg_nerf) is not switched on through hparams: the scene "
+                                  "owns the noise state of both models - call rendering.background_scene(nerf, bg_nerf, sphere_center, "
+                                  "sphere_radius).set_device_noise(seed) (BackgroundScene.set_device_noise) and leave "
+                                  "device_noise_seed unset")
     if not hasattr(nerf, "set_device_noise"):
         raise NotImplementedError("device_noise_seed: the model has no seeded device noise")
     if seed is None:                      # (switched on by the caller: SwitchNeRF.set_device_noise)
@@ -202,26 +209,39 @@ def _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get
     return res
 
 
+def background_scene(nerf, bg_nerf, sphere_center=None, sphere_radius=None):
+    """The BackgroundScene render_rays uses for (nerf, bg_nerf): built on first use and cached on the foreground model.  Seeded device
+    noise for a scene with a background model is switched on here: background_scene(...).set_device_noise(seed) - a training
+    render_rays then passes no framework-drawn noise and advances the scene's step counter after its forward."""
+    from .background import BackgroundScene
+    scene = getattr(nerf, "_bg_scene", None)
+    if scene is None or scene.bg is not bg_nerf:
+        if scene is not None:
+            scene.set_device_noise(None)       # (the replaced scene hands the foreground model its own noise state back)
+        scene = nerf._bg_scene = BackgroundScene(nerf, bg_nerf, sphere_center, sphere_radius)
+    scene.center, scene.radius = sphere_center, sphere_radius
+    return scene
+
+
 def _render_rays_bg(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, sphere_radius, get_depth, get_depth_variance,
                     get_bg_fg_rgb):
     """The bg_nerf branch (rendering.py:32-159) through background.BackgroundScene."""
-    from .background import BackgroundScene
     N, S, F = rays.shape[0], hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
     perturb = hparams.perturb if nerf.training else 0
     use_noise = getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and nerf.training
     std = hparams.sigma_noise_std if use_noise else 0.0
     if image_indices is None:
         image_indices = torch.zeros(N, dtype=torch.long, device=rays.device)
-    scene = getattr(nerf, "_bg_scene", None)
-    if scene is None or scene.bg is not bg_nerf:
-        scene = nerf._bg_scene = BackgroundScene(nerf, bg_nerf, sphere_center, sphere_radius)
-    scene.center, scene.radius = sphere_center, sphere_radius
+    scene = background_scene(nerf, bg_nerf, sphere_center, sphere_radius)
+    dn = scene.device_noise and nerf.training      # seeded device noise: the scene draws what is not supplied (std = the sigma noise's)
     kw = {}
-    if use_noise:        # rendering.py:366: randn per evaluated chunk, for either model
+    if use_noise and not dn:        # rendering.py:366: randn per evaluated chunk, for either model
         kw = dict(sigma_noise=torch.randn(N * S, device=rays.device) * std, sigma_noise_bg="randn", sigma_noise_bg_fine="randn",
                   sigma_noise_fine=torch.randn(N * F, device=rays.device) * std if F else None)
     ctx = scene.forward(rays.contiguous(), image_indices, S, min(hparams.model_chunk_size, N * S), float(perturb), fine_samples=F,
                         no_batch=nerf.moe_no_batch, noise_std=std, training=nerf.training, **kw)
+    if dn:
+        scene._noise_advance()
     typ = "fine" if F > 0 else "coarse"
     res = {f"rgb_{typ}": ctx["rgb"], "gate_loss_coarse": ctx["c"]["l_aux"]}
     if F > 0:
