@@ -736,6 +736,37 @@ size_t swn_ray_feat_wgrad_workspace_bytes(int n_rays, int n_feat, int h2);
 int swn_ray_feat_wgrad(const float* feat, const float* dc_ray, int n_rays, int n_feat, int h2, float* d_w2r, float* d_b2,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the per-image affine colour transform (--affine_appearance; affine.hip) ------------------------------------------------------
+ * models/nerf_moe.py:153-161 (self.affine = nn.Linear(appearance_dim, 12)) and :436-438:
+ *     affine_transform = self.affine(self.embedding_a(x[:, -1].long())).view(-1, 3, 4)
+ *     rgb = (affine_transform[:, :, :3] @ rgb.unsqueeze(-1) + affine_transform[:, :, 3:]).squeeze(-1)
+ * applied to the colour head's linear output before the sigmoid.  A ray belongs to one image: the matrix is per RAY.  All fp32.
+ *
+ * swn_affine_ray_fwd (:437): T[n_rays, 12] = emb[image_indices[n]] @ w_affine^T + b_affine  (w_affine [12, app_dim], nn.Linear's layout;
+ * row n of T = the 3 x 4 matrix [A | t] row-major). */
+int swn_affine_ray_fwd(const float* emb, int app_dim, const void* image_indices, int indices_are_int64, const float* w_affine,
+                       const float* b_affine, int n_rays, float* T, void* stream);
+/* Its backward: d_w_affine[12, app_dim] += dT^T emb[image_indices], d_b_affine[12] += column sums of dT (block partial sums in `workspace`
+ * added in a fixed order), d_feat[n_rays, app_dim] = dT @ w_affine - the per-ray embedding gradient, for swn_emb_grad. */
+int swn_affine_ray_bwd_workspace_bytes(int n_rays, int app_dim, size_t* bytes);
+int swn_affine_ray_bwd(const float* dT, const float* emb, int app_dim, const void* image_indices, int indices_are_int64,
+                       const float* w_affine, int n_rays, float* d_w_affine, float* d_b_affine, float* d_feat, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* swn_heads_fwd with the transform (:431-441): raw[i] = (sigmoid(A (h2[i] Wc^T + bc) + t), softplus(..)), [A | t] = T[i / rows_per_group]
+ * (rows_per_group = the samples of a ray; it divides n_points).  The colour head's linear output is not stored. */
+int swn_heads_affine_fwd(const void* y, const void* h2, int dtype, const float* w_sigma, const float* b_sigma, const float* w_color,
+                         const float* b_color, const float* sigma_noise, const float* T, int rows_per_group, int n_points,
+                         int model_dim, int h2_dim, float* raw, void* stream);
+/* swn_heads_bwd with the transform: dh2, dsig, the four parameter gradients (accumulated, block partial sums added in a fixed order),
+ * group_colsum (per-ray column sums of the stored dh2 rows; may be NULL) and y == NULL as there.  The colour part recomputes
+ * lin = h2 Wc^T + bc; d_pre = d_raw_c rgb (1 - rgb); d_lin = A^T d_pre feeds dh2, d_w_color and d_b_color; the new output
+ * dT[n_points / rows_per_group, 12] = sum over the ray's samples of [d_pre (x) lin | d_pre] (written, fixed order).  No atomics. */
+int swn_heads_affine_bwd_workspace_bytes(int n_points, int model_dim, int h2_dim, int rows_per_group, size_t* bytes);
+int swn_heads_affine_bwd(const void* y, const void* h2, int dtype, const float* w_color, const float* b_color, const float* T,
+                         const float* raw, const float* d_raw, int n_points, int model_dim, int h2_dim, int rows_per_group, void* dh2,
+                         float* dsig, float* d_w_sigma, float* d_b_sigma, float* d_w_color, float* d_b_color, float* group_colsum,
+                         float* dT, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser -------------------------------------------------------------------------------------------------
  * torch.optim.Adam (runner.py:486) over one flat fp32 parameter buffer; grad_scale multiplies the gradient
  * (1/world_size after a sum all-reduce).  Also refreshes the compute copies: shadow (dtype) same layout.         */

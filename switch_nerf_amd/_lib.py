@@ -143,6 +143,12 @@ SIGNATURES = {
     "swn_step_loss": [vp, vp, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, vp, vp],
     "swn_emb_grad": [vp, i32, vp, i32, i32, i32, i32, vp, vp],
     "swn_ray_feat_wgrad": [vp, vp, i32, i32, i32, vp, vp, vp, sz, vp],
+    "swn_affine_ray_fwd": [vp, i32, vp, i32, vp, vp, i32, vp, vp],
+    "swn_affine_ray_bwd_workspace_bytes": [i32, i32, C.POINTER(sz)],
+    "swn_affine_ray_bwd": [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, sz, vp],
+    "swn_heads_affine_fwd": [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp],
+    "swn_heads_affine_bwd_workspace_bytes": [i32, i32, i32, i32, C.POINTER(sz)],
+    "swn_heads_affine_bwd": [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "swn_adam_step": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, f32, vp],
     "swn_cast": [vp, vp, i32, i64, vp],
     "swn_cast_transpose": [vp, vp, i32, i32, i32, i32, vp],

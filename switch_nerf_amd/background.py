@@ -33,6 +33,9 @@ class BackgroundScene:
 
     def __init__(self, nerf, bg_nerf, sphere_center=None, sphere_radius=None):
         assert getattr(bg_nerf, "xyz_dim", 3) == 4, "the background model takes the 4-D inverted-sphere points (get_bg_nerf: xyz_dim 4)"
+        if getattr(nerf, "affine", False):      # (the reference builds BOTH models from hparams.affine_appearance: model_utils.py:90-120)
+            raise NotImplementedError("affine_appearance is not built for scenes with a background model: the dense background NeRF "
+                                      "(models/nerf.py:117) has no affine branch")
         self.nerf, self.bg = nerf, bg_nerf
         self.center, self.radius = sphere_center, sphere_radius
         bg_nerf._grow_bufs = True           # the number of background rays changes every batch

@@ -106,6 +106,8 @@ def _rank(key: str, dense: bool):
         return (7, 0, wb)
     if k == "embedding_a.weight":
         return (8, 0, 0)
+    if k.startswith("affine."):                 # --affine_appearance: nn.Linear(appearance_dim, 12), registered behind embedding_a
+        return (8, 1, wb)                       # (models/nerf_moe.py:148-157)
     if k.startswith("embedding_xyz."):          # hash-grid table (no reference counterpart): after everything else
         return (9, 0, 0)
     raise KeyError(f"unknown parameter key {key}")

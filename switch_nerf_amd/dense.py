@@ -36,6 +36,8 @@ class DenseNeRF(SwitchNeRF):
         super().__init__(cfg, dtype, device, capacity_factor=1.0, batch_prioritized=False, moe_l_aux_wt=0.0, lr=lr, seed=seed)
 
     def _configure(self, cfg):
+        if cfg.get("affine_appearance", False):
+            raise NotImplementedError("affine_appearance is not built for the dense NeRF (models/nerf.py:117): only SwitchNeRF applies it")
         W, L, xd = cfg["layer_dim"], cfg["layers"], cfg.get("xyz_dim", 3)
         skips = tuple(cfg["skip_layers"])
         assert len(skips) <= 1 and all(0 < s < L for s in skips), "at most one concat-skip layer, not the first"

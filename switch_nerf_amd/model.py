@@ -128,6 +128,8 @@ class SwitchNeRF:
         self.gate_noise, self.gate_noise_draw = float(gate_noise), None
         self.base_lr = lr             # undecayed rate ('initial_lr' of the reference's ExponentialLR); self.lr = the current rate
         spec = self._configure(cfg)
+        if self.affine:               # the colour transform runs in the heads' own launches (swn_heads_affine_*), behind the unfused tail
+            self.sw.update(fused_heads=False, fused_tail=False, fused_tail_bwd=False)
         self.spec, off = {}, 0
         self.n_dense = None           # elements of the flat buffer before the first expert parameter (all of it for dense models)
         for i, (name, shape) in enumerate(spec):
@@ -168,7 +170,12 @@ class SwitchNeRF:
         self.in_dir = 3 + 6 * cfg["pos_dir_dim"]
         self.KP = _ceil_to(self.in_xyz, 64)          # padded PE width (chain K granularity)
         self.DP = _ceil_to(self.in_dir, 8)
-        self.n_ray_feat = self.in_dir + cfg["appearance_dim"]
+        # --affine_appearance (opts.py:55; models/nerf_moe.py:153-161): the appearance embedding feeds a Linear(appearance_dim, 12) whose
+        # output transforms the colour head's output per image (:436-438) and no longer enters layer "2" (:161, :426)
+        self.affine = bool(cfg.get("affine_appearance", False))
+        if self.affine and cfg["appearance_dim"] <= 0:
+            raise ValueError("affine_appearance needs appearance_dim > 0 (models/nerf_moe.py:154)")
+        self.n_ray_feat = self.in_dir + (0 if self.affine else cfg["appearance_dim"])
         spec = [("xyz.w", (self.KP, M)), ("xyz.b", (M,)), ("gate0.w", (M, G)), ("gate0.b", (G,)),
                 ("gate1.w", (G, G)), ("gate1.b", (G,)), ("ln.w", (G,)), ("ln.b", (G,)), ("wg", (E, G))]
         spec += [("l1.w", (M, M)), ("l1.b", (M,)), ("l2h.w", (M, H2)), ("l2r.w", (self.n_ray_feat, H2)), ("l2.b", (H2,)),
@@ -185,6 +192,8 @@ class SwitchNeRF:
         if self.hash is not None:                     # trainable encoding: the first layer's input gradient feeds the table
             spec.append(("hash.table", (self.hash["n_levels"], 1 << self.hash["log2_table"], 2)))
             self._fwd_only_weights = set()
+        if self.affine:                               # appended to the dense prefix: no other parameter moves
+            spec += [("affine.w", (12, cfg["appearance_dim"])), ("affine.b", (12,))]
         self._n_dense_spec = len(spec)
         return spec + self._expert_spec
 
@@ -230,6 +239,8 @@ class SwitchNeRF:
         sd["embedding_a.weight"] = torch.randn(cfg["appearance_count"], cfg["appearance_dim"], generator=g)
         if self.hash is not None:         # instant-NGP initialisation: U(-1e-4, 1e-4)
             sd["embedding_xyz.table"] = (torch.rand(self.spec["hash.table"][1], generator=g) * 2 - 1) * 1e-4
+        if self.affine:
+            sd["affine.weight"], sd["affine.bias"] = lin(12, cfg["appearance_dim"])
         self.load_state_dict(sd)
 
     def load_state_dict(self, sd):
@@ -278,6 +289,9 @@ class SwitchNeRF:
             p["emb"].copy_(t("embedding_a.weight"))
             if self.hash is not None:
                 p["hash.table"].copy_(t("embedding_xyz.table"))
+            if self.affine:
+                p["affine.w"].copy_(t("affine.weight"))
+                p["affine.b"].copy_(t("affine.bias"))
 
     def _to_ref_layout(self, d):
         M = self.M
@@ -305,6 +319,10 @@ class SwitchNeRF:
         out["embedding_a.weight"] = d["emb"].clone()
         if self.hash is not None:
             out["embedding_xyz.table"] = d["hash.table"].clone()
+        if self.affine:      # (an affine model lists its keys in the order the reference registers them: checkpoint.param_order)
+            from . import checkpoint
+            out["affine.weight"], out["affine.bias"] = d["affine.w"].clone(), d["affine.b"].clone()
+            out = {k: out[k] for k in checkpoint.param_order(out.keys())}
         return out
 
     def state_dict(self, layout="expertmlp", prefix=""):
@@ -323,6 +341,8 @@ class SwitchNeRF:
 
     def refresh_compute_copies(self):
         """fp32 master [in, out] -> MFMA-fragment-major compute copies: forward (N=out, K=in), backward (N=in, K=out)."""
+        if self.dev.type != "cuda":      # a host-resident model holds parameters only (key layout, checkpoints): no kernel can run on it
+            return
         pairs = []
         for n in self._chain_weights:
             w = self.p[n + ".w"]
@@ -375,6 +395,9 @@ class SwitchNeRF:
         for k, v in kw.items():
             if k not in self.sw:
                 raise KeyError(f"unknown kernel switch {k!r} (known: {sorted(self.sw)})")
+            if self.affine and k in ("fused_heads", "fused_tail", "fused_tail_bwd") and v:
+                raise ValueError(f"kernel switch {k!r}: an affine_appearance model runs the heads as their own launches (the fused tail "
+                                 "does not apply the colour transform)")
             prev[k] = self.sw[k]
             self.sw[k] = type(self.sw[k])(v)
         if "overlap" in kw:
@@ -427,6 +450,9 @@ class SwitchNeRF:
         their full size (3.7 M expert parameters); gather_expert_shards() refreshes every rank's copy from the owners before a
         checkpoint / evaluation without expert parallelism."""
         assert ep is None or ep.E == self.E
+        if ep is not None and self.affine:
+            raise NotImplementedError("affine_appearance is not built for expert parallelism (ExpertParallel, owner_tail included): the "
+                                      "colour transform runs in the local tail only")
         if ep is not None and self.cf == 0:
             raise ValueError(DYNCAP_EP_ERROR)
         if ep is None and self.ep is not None:       # leaving expert parallelism: every rank needs every expert's trained weights
@@ -473,6 +499,7 @@ class SwitchNeRF:
         return t[r * El:(r + 1) * El]
 
     # ------------------------------------------------------------------------------------------ buffers
+    affine = False          # cfg["affine_appearance"]: the per-image affine colour transform (set by _configure)
     _saving = True          # False inside an inference forward: the chains skip the activation saves and ReLU masks
     hash = None             # multiresolution hash-grid input encoding (cfg["hash"]) or None
     _grow_bufs = False      # True: one buffer per name, grown to the largest row count seen (row counts that vary per step)
@@ -676,6 +703,11 @@ class SwitchNeRF:
     def _ray_feat(self, c, pe_dir, image_indices):
         """The per-ray part of layer "2": [PE(dir), appearance embedding] @ W2r + b2 (N_rays x 75) -> c["ray_feat"], c["c_ray"]."""
         # (one launch: swn_ray_feat_fwd - was cat / embedding lookup / addmm in torch)
+        if self.affine:      # the direction encoding only; the embedding goes through affine -> the per-ray 3 x 4 colour transform
+            idx = image_indices.contiguous()
+            c["ray_feat"], c["c_ray"] = ops.ray_feat_dir_fwd(pe_dir, self.in_dir, self.p["emb"], idx, self.p["l2r.w"], self.p["l2.b"])
+            c["aff_T"] = ops.affine_ray_fwd(self.p["emb"], idx, self.p["affine.w"], self.p["affine.b"])
+            return
         c["ray_feat"], c["c_ray"] = ops.ray_feat_fwd(pe_dir, self.in_dir, self.p["emb"], image_indices.contiguous(), self.p["l2r.w"], self.p["l2.b"])
 
     def _l2h_pad(self, forward: bool):
@@ -746,6 +778,8 @@ class SwitchNeRF:
         if row_range is not None:  # a row range of the point grid: the rows' rays through an explicit per-row gather
             rowbias, rpb = c["c_ray"].index_select(0, torch.arange(r0, r1, device=self.dev) // S), 1
             c["ragged"], c["row0"] = True, r0
+        if self.affine:      # the heads' view of the per-ray transform: one matrix per S rows, or (a row range) per row
+            c["aff_rows"] = (c["aff_T"], S) if row_range is None else (c["aff_T"].index_select(0, torch.arange(r0, r1, device=self.dev) // S), 1)
         self._tail_forward(c, c["eo"], sigma_noise, rowbias, rpb, combine=(c["row_of_tok"], c["gmax"]))
         return c
 
@@ -1004,7 +1038,10 @@ class SwitchNeRF:
                         o.Layer(self.wf["l2h"], None, relu=1, rowbias=rowbias, rows_per_bias=rows_per_bias)], c["h2"], group_stride=P, tag=4,
                     heads=(self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"], sigma_noise, c["raw"]) if fused else None,
                     **kw)
-        if not fused:      # ---- heads as their own launch (SWN_NO_FUSED_HEADS=1: rounds 1-2)
+        if self.affine:    # ---- heads + the per-image colour transform (models/nerf_moe.py:436-438) as their own launch
+            c["raw"] = o.heads_affine_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
+                                          sigma_noise, *c["aff_rows"])
+        elif not fused:    # ---- heads as their own launch (SWN_NO_FUSED_HEADS=1: rounds 1-2)
             c["raw"] = o.heads_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                    sigma_noise)
 
@@ -1086,6 +1123,10 @@ class SwitchNeRF:
         else:
             g["l2r.w"].addmm_(c["ray_feat"].t(), dc_ray)
             g["l2.b"].add_(dc_ray.sum(0))
+        if self.affine:      # the embedding's only gradient path: dT -> affine's parameters, dT @ W_a -> the ordered embedding reduction
+            idx = c["image_indices"].contiguous()
+            o.emb_grad(o.affine_ray_bwd(c["aff_dT"], self.p["emb"], idx, self.p["affine.w"], g["affine.w"], g["affine.b"]), idx, g["emb"])
+            return
         d_feat_emb = dc_ray @ self.p["l2r.w"][self.in_dir:].t()
         o.emb_grad(d_feat_emb, c["image_indices"].contiguous(), g["emb"])        # (rays added in order: torch's index_add_ uses atomics)
 
@@ -1094,7 +1135,13 @@ class SwitchNeRF:
         # per-ray bias gradient (the column sums of a ray's dh2 rows: from the heads' launch) and the tiny per-ray GEMM's parameters
         o, g = ops, self.g
         N, S, P, H2 = c["N"], c["S"], c["P"], self.H2
-        if c.get("ragged"):      # a row range of the point grid: rays may be cut at either end - per-ray sums through the rows' ray index
+        if self.affine:
+            if c.get("ragged"):
+                raise NotImplementedError("affine_appearance: the backward of a ragged last model chunk is not built (dT is summed per "
+                                          "whole ray); use a batch of rays x samples that is a multiple of the model chunk")
+            dh2, dsig, dc_ray, c["aff_dT"] = o.heads_affine_bwd(y_heads, c["h2"], self.p["color.w"], self.p["color.b"], c["aff_T"], c["raw"],
+                                                                d_raw, g["sigma.w"], g["sigma.b"], g["color.w"], g["color.b"], rows_per_group=S)
+        elif c.get("ragged"):      # a row range of the point grid: rays may be cut at either end - per-ray sums through the rows' ray index
             dh2, dsig = o.heads_bwd(y_heads, c["h2"], self.p["color.w"], c["raw"], d_raw, g["sigma.w"], g["sigma.b"], g["color.w"],
                                     g["color.b"])
             ray_of_row = torch.arange(c["row0"], c["row0"] + P, device=self.dev) // S

@@ -652,6 +652,75 @@ def ray_feat_wgrad(feat, dc_ray, d_w2r, d_b2):
     call("swn_ray_feat_wgrad", _p(feat), _p(dc_ray), N, F, H2, _p(d_w2r), _p(d_b2), _p(ws), nb, _stream())
 
 
+def ray_feat_dir_fwd(pe_dir, in_dir: int, emb, image_indices, w2r, b2):
+    """swn_ray_feat_fwd with NO embedding columns (affine_appearance: layer "2" sees the direction encoding only) ->
+    feat [N, in_dir] f32, c_ray [N, h2] f32."""
+    N, h2 = pe_dir.shape[0], w2r.shape[1]
+    assert w2r.shape[0] == in_dir
+    feat = torch.empty(N, in_dir, dtype=torch.float32, device=pe_dir.device)
+    c_ray = torch.empty(N, h2, dtype=torch.float32, device=pe_dir.device)
+    ip, i64 = _idx_arg(image_indices)
+    call("swn_ray_feat_fwd", _p(pe_dir), _dt(pe_dir), pe_dir.shape[1], int(in_dir), _p(emb), 0, ip, i64, _p(w2r), _p(b2), N, h2,
+         _p(feat), _p(c_ray), _stream())
+    return feat, c_ray
+
+
+def affine_ray_fwd(emb, image_indices, w_affine, b_affine):
+    """-> T [N, 12] f32 = emb[image_indices] @ w_affine^T + b_affine, the per-ray 3 x 4 colour transform (swn_affine_ray_fwd)."""
+    N, A = image_indices.shape[0], emb.shape[1]
+    assert w_affine.shape == (12, A) and b_affine.numel() == 12 and all(t.dtype == torch.float32 and t.is_contiguous() for t in (emb, w_affine, b_affine))
+    T = torch.empty(N, 12, dtype=torch.float32, device=emb.device)
+    ip, i64 = _idx_arg(image_indices)
+    call("swn_affine_ray_fwd", _p(emb), A, ip, i64, _p(w_affine), _p(b_affine), N, _p(T), _stream())
+    return T
+
+
+def affine_ray_bwd(dT, emb, image_indices, w_affine, d_w_affine, d_b_affine):
+    """d_w_affine [12, A] += dT^T emb[image_indices], d_b_affine [12] += dT.sum(0) (ordered block sums) -> d_feat [N, A] = dT @ w_affine,
+    the per-ray embedding gradient (for emb_grad)."""
+    N, A = dT.shape[0], emb.shape[1]
+    assert dT.shape == (N, 12) and image_indices.shape[0] == N and d_w_affine.numel() == 12 * A and d_b_affine.numel() == 12
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (dT, emb, w_affine, d_w_affine, d_b_affine))
+    nb = C.c_size_t(0)
+    call("swn_affine_ray_bwd_workspace_bytes", N, A, C.byref(nb))
+    ws = torch.empty(max(int(nb.value), 4) // 4, dtype=torch.float32, device=dT.device)
+    d_feat = torch.empty(N, A, dtype=torch.float32, device=dT.device)
+    ip, i64 = _idx_arg(image_indices)
+    call("swn_affine_ray_bwd", _p(dT), _p(emb), A, ip, i64, _p(w_affine), N, _p(d_w_affine), _p(d_b_affine), _p(d_feat), _p(ws),
+         int(nb.value), _stream())
+    return d_feat
+
+
+def heads_affine_fwd(y, h2, w_sigma, b_sigma, w_color, b_color, sigma_noise, T, rows_per_group: int):
+    """heads_fwd with the per-ray colour transform T [P / rows_per_group, 12] (swn_heads_affine_fwd) -> raw [P, 4] f32."""
+    P, M = y.shape
+    H2 = h2.shape[1]
+    assert T.dtype == torch.float32 and T.is_contiguous() and T.shape == (P // rows_per_group, 12) and P % rows_per_group == 0
+    raw = torch.empty(P, 4, dtype=torch.float32, device=y.device)
+    call("swn_heads_affine_fwd", _p(y), _p(h2), _dt(y), _p(w_sigma), _p(b_sigma), _p(w_color), _p(b_color), _p(sigma_noise), _p(T),
+         int(rows_per_group), P, M, H2, _p(raw), _stream())
+    return raw
+
+
+def heads_affine_bwd(y, h2, w_color, b_color, T, raw, d_raw, d_w_sigma, d_b_sigma, d_w_color, d_b_color, rows_per_group: int,
+                     want_colsum: bool = True):
+    """heads_bwd with the colour transform (swn_heads_affine_bwd) -> (dh2, dsig, colsum [P / rows_per_group, H2] f32 or None,
+    dT [P / rows_per_group, 12] f32).  y may be None (d_w_sigma untouched)."""
+    P, H2 = h2.shape
+    M = d_w_sigma.numel()
+    assert T.dtype == torch.float32 and T.is_contiguous() and T.shape == (P // rows_per_group, 12) and P % rows_per_group == 0
+    dh2 = torch.empty_like(h2)
+    dsig = torch.empty(P, dtype=torch.float32, device=h2.device)
+    nb = C.c_size_t(0)
+    call("swn_heads_affine_bwd_workspace_bytes", P, M, H2, int(rows_per_group), C.byref(nb))
+    ws = torch.empty(max(int(nb.value), 4) // 4, dtype=torch.float32, device=h2.device)
+    cs = torch.empty(P // rows_per_group, H2, dtype=torch.float32, device=h2.device) if want_colsum else None
+    dT = torch.empty(P // rows_per_group, 12, dtype=torch.float32, device=h2.device)
+    call("swn_heads_affine_bwd", _p(y), _p(h2), _dt(h2), _p(w_color), _p(b_color), _p(T), _p(raw), _p(d_raw), P, M, H2, int(rows_per_group),
+         _p(dh2), _p(dsig), _p(d_w_sigma), _p(d_b_sigma), _p(d_w_color), _p(d_b_color), _p(cs), _p(dT), _p(ws), int(nb.value), _stream())
+    return dh2, dsig, cs, dT
+
+
 def step_loss(rgb, target, l_aux_a, l_aux_b, wt: float, loss_scale_dev=None):
     """-> (out4 = [photo, gate_loss, loss, psnr] on the device, d_rgb, d_l_aux_a, d_l_aux_b or None)."""
     dev = rgb.device

@@ -81,11 +81,21 @@ def _device_noise(nerf, bg_nerf, hparams) -> bool:
     return True
 
 
+def _check_affine(nerf, hparams):
+    """hparams.affine_appearance (opts.py:55) must say what the model was built with (cfg["affine_appearance"]): a model with the other
+    layer "2" width and parameter set is never used silently."""
+    want, have = bool(getattr(hparams, "affine_appearance", False)), bool(getattr(nerf, "affine", False))
+    if want != have:
+        raise NotImplementedError(f"hparams.affine_appearance = {want} but the model was built with affine_appearance = {have}: "
+                                  "build the model from a cfg with the same switch")
+
+
 def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch.Tensor], hparams, sphere_center=None,
                 sphere_radius=None, get_depth: bool = True, get_depth_variance: bool = True,
                 get_bg_fg_rgb: bool = False) -> Tuple[Dict[str, torch.Tensor], bool]:
     if getattr(hparams, "use_cascade", False):
         raise NotImplementedError("use_cascade is outside the hot path")
+    _check_affine(nerf, hparams)
     F = int(getattr(hparams, "fine_samples", 0))
     N = rays.shape[0]
     S = hparams.coarse_samples
@@ -278,6 +288,7 @@ def render_rays_mip(nerf, rays: torch.Tensor, radii: torch.Tensor, image_indices
     """Mirror of rendering_mip.render_rays (/root/reference/switch_nerf/rendering_mip.py:133-172) for MipNeRFMoE-style models:
     results carry rgb_coarse, gate_loss_coarse and, with fine_samples > 0, rgb_fine, depth_fine, depth_variance_fine,
     gate_loss_fine (the coarse level reports depth only when it is the last one, :207-208)."""
+    _check_affine(nerf, hparams)
     N = rays.shape[0]
     S, F = hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
     perturb = hparams.perturb if nerf.training else 0
