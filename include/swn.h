@@ -444,7 +444,7 @@ int swn_composite_bounded_fwd(const float* raw, const float* z, const float* las
 int swn_composite_bounded_bwd(const float* raw, const float* z, const float* last_delta, int flip, const float* d_rgb,
                               const float* d_bg_lambda, int n_rays, int n_samples, float* d_raw, void* stream);
 
-/* dst[r] = src[index[r]] for r < n_rows (rows of row_bytes bytes, a multiple of 16), zero rows where index[r] < 0.
+/* dst[r] = src[index[r]] for r < n_rows (rows of row_bytes bytes, a multiple of 4 like swn_scatter_rows'), zero rows where index[r] < 0.
  * Builds the send buffer of the expert-parallel token exchange (the reference's all-to-all payload,
  * tutel_moe_layer_nobatch.py:157, 172) from the routing permutation.                                            */
 int swn_gather_rows(const void* src, const int32_t* index, long n_rows, int row_bytes, void* dst, void* stream);

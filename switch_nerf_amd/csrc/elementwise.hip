@@ -1006,18 +1006,20 @@ __global__ void cast_transpose_kernel(const float* __restrict__ in, T* __restric
   }
 }
 
-// dst[r] = src[index[r]] (16-byte pieces), zero rows for index < 0: the send buffer of the expert-parallel exchange
+// dst[r] = src[index[r]] (pieces of V: 16 bytes, or 4 for rows / buffers that are no multiple of 16), zero rows for index < 0: the send
+// buffer of the expert-parallel exchange
+template <typename V>
 __global__ void gather_rows_kernel(const char* __restrict__ src, const int32_t* __restrict__ index, long n_rows, int row_bytes,
                                    char* __restrict__ dst) {
-  const int cpr = row_bytes >> 4;
+  const int cpr = row_bytes / (int)sizeof(V);
   const long total = n_rows * cpr;
   for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (long)gridDim.x * blockDim.x) {
     const long r = c / cpr;
     const int ch = (int)(c - r * cpr);
     const int s_ = index[r];
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (s_ >= 0) v = *(const uint4*)(src + (long)s_ * row_bytes + ch * 16);
-    *(uint4*)(dst + c * 16) = v;
+    V v = V{};
+    if (s_ >= 0) v = *(const V*)(src + (long)s_ * row_bytes + (long)ch * sizeof(V));
+    *(V*)(dst + c * (long)sizeof(V)) = v;
   }
 }
 
@@ -1566,12 +1568,18 @@ extern "C" int swn_cast_transpose(const float* in, void* out, int dtype, int bat
 
 extern "C" int swn_gather_rows(const void* src, const int32_t* index, long n_rows, int row_bytes, void* dst, void* stream) {
   SWN_CHECK(src && index && dst, "swn_gather_rows: null pointer");
-  SWN_CHECK(row_bytes > 0 && row_bytes % 16 == 0, "swn_gather_rows: row_bytes %d must be a multiple of 16", row_bytes);
+  SWN_CHECK(row_bytes > 0 && row_bytes % 4 == 0, "swn_gather_rows: row_bytes %d must be a multiple of 4", row_bytes);
   if (n_rows <= 0) return 0;
-  long blocks = (n_rows * (row_bytes >> 4) + 255) / 256;
+  // (rows of 4 / 8 / 12 ... bytes, the widths swn_scatter_rows takes, move in 4-byte pieces; so do 16-byte rows of an unaligned buffer)
+  const bool wide = row_bytes % 16 == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0);
+  long blocks = (n_rows * (row_bytes / (wide ? 16 : 4)) + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const char*)src, index, n_rows,
-                     row_bytes, (char*)dst);
+  if (wide)
+    hipLaunchKernelGGL(gather_rows_kernel<uint4>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const char*)src, index, n_rows,
+                       row_bytes, (char*)dst);
+  else
+    hipLaunchKernelGGL(gather_rows_kernel<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const char*)src, index, n_rows,
+                       row_bytes, (char*)dst);
   SWN_LAUNCH_CHECK();
   return 0;
 }

@@ -595,10 +595,13 @@ __global__ __launch_bounds__(256) void load_importance_partial_kernel(const floa
   __syncthreads();
   if (threadIdx.x < 32) {
     const int c = threadIdx.x;
-    float a = 0.f;
-    for (int t = 0; t < 256; ++t) a += red[t][c];
+    // The 256 per-thread sums, and the up to 512 block sums in load_importance_final_kernel, are added in double: 768 fp32 additions in a
+    // row behind every Imp_e / Load_e cost the loss 1.6e-6 relative at 131372 tokens (cv2 amplifies the sums' error;
+    // profiles/r11_topk_gate_kernel_parity.md).  Only the running sum is double: `partial` and v[] hold it rounded to fp32.
+    double a = 0.0;
+    for (int t = 0; t < 256; ++t) a += (double)red[t][c];
     const int e = c & 15;
-    if (e < E) partial[(long)blockIdx.x * 2 * E + (c >> 4) * E + e] = a;
+    if (e < E) partial[(long)blockIdx.x * 2 * E + (c >> 4) * E + e] = (float)a;
   }
 }
 
@@ -609,9 +612,9 @@ __global__ __launch_bounds__(64) void load_importance_final_kernel(const float* 
   __shared__ float v[32];
   const int c = threadIdx.x;
   if (c < 2 * E) {
-    float a = 0.f;
-    for (int b = 0; b < nblk; ++b) a += partial[(long)b * 2 * E + c];
-    v[c] = a;
+    double a = 0.0;
+    for (int b = 0; b < nblk; ++b) a += (double)partial[(long)b * 2 * E + c];
+    v[c] = (float)a;
   }
   __syncthreads();
   if (c < 2) {          // thread 0: importance, thread 1: load

@@ -299,11 +299,12 @@ def gate_bwd_dense(g, ln_w, ln_b, wg, gates, idx, d_gmax, d_probs, stats, counts
     return dg
 
 
-def gate_logits(g, wg, noise=None, noise_scale: float = 0.0):
-    """The fp32 router's logits g @ wg^T (+ noise_scale * noise) [P, E] (swn_gate_logits; no LayerNorm)."""
+def gate_logits(g, wg, noise=None, noise_scale: float = 0.0, out=None):
+    """The fp32 router's logits g @ wg^T (+ noise_scale * noise) [P, E] (swn_gate_logits; no LayerNorm); out: the fp32 [P, E] buffer to fill."""
     P, G = g.shape
     E = wg.shape[0]
-    logits = torch.empty(P, E, dtype=torch.float32, device=g.device)
+    logits = torch.empty(P, E, dtype=torch.float32, device=g.device) if out is None else out
+    assert logits.shape == (P, E) and logits.dtype == torch.float32
     call("swn_gate_logits", _p(g), _dt(g), _p(wg), _p(noise), float(noise_scale), P, G, E, _p(logits), _stream())
     return logits
 
