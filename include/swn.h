@@ -444,6 +444,28 @@ int swn_composite_bounded_fwd(const float* raw, const float* z, const float* las
 int swn_composite_bounded_bwd(const float* raw, const float* z, const float* last_delta, int flip, const float* d_rgb,
                               const float* d_bg_lambda, int n_rays, int n_samples, float* d_raw, void* stream);
 
+/* ---- fixed-shape background rows (csrc/bg_compact.hip): the background model of a scene runs on `capacity` rows whatever the batch,
+ * the first n_bg of them being the batch's background rays in ascending ray order, so that nothing is sized by a host read.
+ * swn_bg_compact: stable compaction of has_bg [n_rays] (swn_fg_bounds), 1 <= capacity <= n_rays.  One workgroup, a block scan
+ *   per 1024 rays, no atomics: the output is a pure function of the input.
+ *     row j < min(*n_bg, capacity): idx_bg[j] = the j-th ray with has_bg != 0, rays_b[j] / img_b[j] = its ray / image index
+ *     row j >= *n_bg (padding):     idx_bg[j] = 0, img_b[j] = 0, rays_b[j] = pad_ray_host (8 floats in HOST memory: a ray every
+ *                                   background intermediate of which is finite - the caller's business)
+ *     *n_bg = the number of set rays, ALSO when it exceeds capacity (the surplus rays are counted, not written)
+ *   image_indices / img_b: int64 (idx_is_i64 != 0) or int32; rays / rays_b 16-byte aligned.
+ * swn_bg_blend_fwd: for j < min(*n_bg, capacity), i = idx_bg[j]: rgb[i] += rgb_b[j] * bg_lambda[i], depth[i] += depth_b[j] *
+ *   bg_lambda[i] (product and sum rounded separately: with distinct indices value for value torch's index_add of the products);
+ *   no other element is written.
+ * swn_bg_blend_bwd: d_bg_lambda [n_rays] = sum_c d_rgb[i, c] * rgb_b[j, c] ((c0 + c2) + c1) on the rays i = idx_bg[j], j <
+ *   min(*n_bg, capacity), and 0 on every other ray; d_rgb_b [capacity, 3] = d_rgb[i] * bg_lambda[i] on those rows and exactly +0
+ *   on the padding rows - what keeps them out of every gradient sum behind it.                                             */
+int swn_bg_compact(const int32_t* has_bg, const float* rays, const void* image_indices, int idx_is_i64, const float* pad_ray_host,
+                   int n_rays, int capacity, int64_t* idx_bg, int32_t* n_bg, float* rays_b, void* img_b, void* stream);
+int swn_bg_blend_fwd(const int64_t* idx_bg, const int32_t* n_bg, const float* bg_lambda, const float* rgb_b, const float* depth_b,
+                     int n_rays, int capacity, float* rgb, float* depth, void* stream);
+int swn_bg_blend_bwd(const int64_t* idx_bg, const int32_t* n_bg, const float* bg_lambda, const float* rgb_b, const float* d_rgb,
+                     int n_rays, int capacity, float* d_bg_lambda, float* d_rgb_b, void* stream);
+
 /* dst[r] = src[index[r]] for r < n_rows (rows of row_bytes bytes, a multiple of 4 like swn_scatter_rows'), zero rows where index[r] < 0.
  * Builds the send buffer of the expert-parallel token exchange (the reference's all-to-all payload,
  * tutel_moe_layer_nobatch.py:157, 172) from the routing permutation.                                            */

@@ -112,6 +112,9 @@ SIGNATURES = {
     "swn_fg_bounds": [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp],
     "swn_bg_sample_pe": [vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp],
     "swn_bg_sample_pe_rng": [vp, vp, vp, vp, u64, vp, i64, vp, i64, f32, i32, i32, i32, i32, vp, vp, vp, i32, vp],
+    "swn_bg_compact": [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp],
+    "swn_bg_blend_fwd": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
+    "swn_bg_blend_bwd": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
     "swn_composite_bounded_fwd": [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp],
     "swn_composite_bounded_bwd": [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp],
     "swn_point_fields": [vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp],

@@ -19,6 +19,15 @@ Seeded device noise (BackgroundScene.set_device_noise; csrc/philox.hpp): the sce
 models.  The foreground model draws its own streams through that counter exactly as it does without a background; the background's
 draws live in the generator's second domain and are addressed through each background ray's position in the batch (idx_bg), so a
 background ray's noise depends on (seed, step, global ray) only - not on which other rays of the batch leave the bound.
+
+Two forms of the background rows.  The COMPACT form (default, bg_capacity=None) mirrors the reference: the background rays are found
+with nonzero() and every background tensor has exactly Nb rows - a host read per step, so the step cannot be captured into a hipGraph.
+The PADDED form (bg_capacity=C, 1 <= C <= N) runs the background model on C rows whatever the batch: swn_bg_compact puts the batch's
+n_bg background rays into the first rows in ascending ray order and fills the rest with a benign ray; n_bg stays on the device.  A
+padding row's activations are finite and its dL/d rgb is exactly 0 (swn_bg_blend_bwd), so it adds exact zeros to every gradient sum;
+swn_bg_blend_fwd skips it.  Nothing is read on the host until ONE 8-byte readback of (n_bg, n_out) behind the step's last launch
+(apply_step) - which is what graph.GraphedBackgroundStep captures.  C < N saves the padding's work on scenes where few rays leave the
+bound; a batch with n_bg > C is refused (RuntimeError) before any parameter is touched.
 """
 from __future__ import annotations
 
@@ -146,7 +155,8 @@ class BackgroundScene:
     # ------------------------------------------------------------------------------------------ forward
     def forward(self, rays, image_indices, n_samples, seg_tokens, perturb=0.0, perturb_rand=None, perturb_rand_bg=None,
                 sigma_noise=None, sigma_noise_bg=None, fine_samples=0, fine_u=None, fine_u_bg=None, sigma_noise_fine=None,
-                sigma_noise_bg_fine=None, no_batch=False, noise_std=0.0, training=True, ray_index=None):
+                sigma_noise_bg_fine=None, no_batch=False, noise_std=0.0, training=True, ray_index=None, bg_capacity=None,
+                ray_index_limit=None):
         """sigma_noise_bg / sigma_noise_bg_fine: [Nb * samples] tensors, or the string "randn" to draw noise_std * N(0,1)
         here (the number of background rays is only known inside).
         The scene's device noise on (set_device_noise) and a training pass: what is not supplied is drawn from the seeded generator -
@@ -154,27 +164,51 @@ class BackgroundScene:
         sigma noise (noise_std > 0; "randn" or None) and fine u through swn_rng_fill_rows; the drawn tensors are kept in ctx["bg"]
         ("sigma_noise", "fine_u", "sigma_noise_fine").  Supplied tensors win.
         ray_index (int64 [N], optional): the position in the full batch of each ray of this call - the BACKGROUND's draws are addressed
-        by ray_base + ray_index[i] instead of ray_base + i (a call on a subset of a batch reproduces that batch's background draws)."""
+        by ray_base + ray_index[i] instead of ray_base + i (a call on a subset of a batch reproduces that batch's background draws).
+        bg_capacity = C (an int, 1 <= C <= N): the padded form (module doc) - the background tensors, supplied noise included
+        (perturb_rand_bg [C, Sb], sigma_noise_bg [C * Sb], fine_u_bg [C, Fb], sigma_noise_bg_fine [C * Fb]), have C rows of which the
+        first n_bg are meaningful; ctx carries "C", "n_bg_dev", "n_out_dev", and ctx["Nb"] stays None until the host has read the
+        count (read_counts).  The out-of-bound and overflow checks happen there, not here.  ray_index then needs ray_index_limit (an
+        exclusive upper bound of its entries, e.g. the full batch's rays) instead of a host read of its maximum."""
         o, nerf, bg = ops, self.nerf, self.bg
         self._check_noise_sources()
         dn = self._noise if training else None
         N, S, Fn = rays.shape[0], n_samples, int(fine_samples)
-        rays_fg, fg_far, last0, has_bg, n_out = o.fg_bounds(rays, self.center, self.radius)
-        idx_bg = has_bg.nonzero().view(-1)                      # rays_with_bg, rendering.py:36 (host sync, like the reference)
-        if int(n_out.item()) > 0:
-            raise Exception("Not all your cameras are bounded by the unit sphere; please make sure the cameras are normalized properly!")
-        Nb = idx_bg.numel()
-        ctx = dict(N=N, S=S, F=Fn, idx_bg=idx_bg, Nb=Nb, fg_far=fg_far, has_bg=has_bg)
+        padded = bg_capacity is not None
+        if padded:
+            Nb = int(bg_capacity)                # the ROW count of every background tensor below
+            if not 1 <= Nb <= N:
+                raise ValueError(f"bg_capacity {Nb} outside [1, {N} rays]")
+            if ray_index is not None and ray_index_limit is None:
+                raise ValueError("bg_capacity with ray_index needs ray_index_limit (the padded form reads nothing on the host)")
+            counts = torch.zeros(2, dtype=torch.int32, device=self.dev)           # (n_bg, n_out): read back together, once
+            rays_fg, fg_far, last0, has_bg, n_out = o.fg_bounds(rays, self.center, self.radius, n_out=counts[1:])
+            idx_bg, n_bg_dev, rays_b, img_b = o.bg_compact(has_bg, rays, image_indices.contiguous(), Nb,
+                                                           o.bg_pad_ray(self.center, self.radius), n_bg=counts[:1])
+            ctx = dict(N=N, S=S, F=Fn, idx_bg=idx_bg, Nb=None, C=Nb, n_bg_dev=n_bg_dev, n_out_dev=n_out, counts_dev=counts,
+                       fg_far=fg_far, has_bg=has_bg)
+        else:
+            rays_fg, fg_far, last0, has_bg, n_out = o.fg_bounds(rays, self.center, self.radius)
+            idx_bg = has_bg.nonzero().view(-1)                      # rays_with_bg, rendering.py:36 (host sync, like the reference)
+            if int(n_out.item()) > 0:
+                raise Exception(self._UNBOUNDED)
+            Nb = idx_bg.numel()
+            ctx = dict(N=N, S=S, F=Fn, idx_bg=idx_bg, Nb=Nb, fg_far=fg_far, has_bg=has_bg)
         det_u = lambda n, k: torch.linspace(0, 1, k).expand(n, k).contiguous().to(self.dev) if perturb == 0 else torch.rand(n, k, device=self.dev)
         # ---- background first (the reference's order, and so the order of its random draws)
         bg._saving = bool(training)          # (DenseNeRF._net_forward is called directly below; reset after the block)
         if Nb > 0:
             Sb = S // 2
-            rays_b = rays.index_select(0, idx_bg).contiguous()
-            img_b = image_indices.index_select(0, idx_bg).contiguous()
+            if not padded:
+                rays_b = rays.index_select(0, idx_bg).contiguous()
+                img_b = image_indices.index_select(0, idx_bg).contiguous()
             drawn = {}
             if dn is not None:               # background row j is global ray ray_base + rows[j]; every entry < lim
-                rows, lim = (idx_bg, N) if ray_index is None else (ray_index.index_select(0, idx_bg), int(ray_index.max().item()) + 1)
+                if ray_index is None:
+                    rows, lim = idx_bg, N
+                else:
+                    rows = ray_index.index_select(0, idx_bg)
+                    lim = int(ray_index_limit) if ray_index_limit is not None else int(ray_index.max().item()) + 1
                 draw = lambda stream, per_row, kind, scale=1.0: o.rng_fill_rows(
                     Nb, per_row, dn["ray_base"], rows, kind, dn["seed"], self._noise_step, stream, o.RNG_DOMAIN_BG, scale, lim)
             if dn is not None and perturb > 0 and perturb_rand_bg is None:
@@ -239,7 +273,9 @@ class BackgroundScene:
         last_delta = torch.where(has_bg > 0, fg_far - z_last, last0).contiguous()          # :216-217 / :249-250
         rgb, depth, dvar, _, lam = o.composite_bounded_fwd(raw, z, last_delta, False, None, want_bg_lambda=True)
         ctx.update(raw=raw, z=z, last_delta=last_delta, bg_lambda=lam, fg_rgb=rgb, fg_depth=depth, depth_variance=dvar)
-        if Nb > 0:                                                        # :104-131
+        if padded:                                                        # :104-131 on the first n_bg rows (swn_bg_blend_fwd)
+            rgb, depth = o.bg_blend_fwd(rgb.clone(), depth.clone(), idx_bg, ctx["n_bg_dev"], lam, ctx["bg"]["rgb"], ctx["bg"]["depth"])
+        elif Nb > 0:                                                      # :104-131
             lam_b = lam.index_select(0, idx_bg)
             rgb = rgb.index_add(0, idx_bg, ctx["bg"]["rgb"] * lam_b[:, None])
             depth = depth.index_add(0, idx_bg, ctx["bg"]["depth"] * lam_b)
@@ -247,17 +283,25 @@ class BackgroundScene:
         return ctx
 
     # ------------------------------------------------------------------------------------------ backward
-    def backward(self, ctx, d_rgb, wt_coarse, wt_fine=0.0):
-        """Accumulates both models' parameter gradients given dL/d rgb [N,3]; wt_* = the weight of each level's mean gate loss."""
+    def backward(self, ctx, d_rgb, wt_coarse, wt_fine=0.0, loss_scale_dev=None, bg_capacity=None):
+        """Accumulates both models' parameter gradients given dL/d rgb [N,3]; wt_* = the weight of each level's mean gate loss.
+        loss_scale_dev: a device scalar the gate-loss weights are multiplied by (the loss scale of a step that reads nothing on the
+        host; d_rgb then carries it already).  The form follows the context's; bg_capacity, when given, must be the forward's."""
         o, nerf, bg = ops, self.nerf, self.bg
-        S, Fn, Nb, idx_bg = ctx["S"], ctx["F"], ctx["Nb"], ctx["idx_bg"]
+        S, Fn, idx_bg = ctx["S"], ctx["F"], ctx["idx_bg"]
+        padded = ctx.get("C") is not None
+        if bg_capacity is not None and int(bg_capacity) != ctx.get("C"):
+            raise ValueError(f"backward: bg_capacity {bg_capacity} but the forward ran with {ctx.get('C')}")
         d_lam = None
-        if Nb > 0:
+        if padded or ctx["Nb"] > 0:
             b = ctx["bg"]
-            d_rgb_sel = d_rgb.index_select(0, idx_bg)
-            d_lam = torch.zeros(ctx["N"], dtype=torch.float32, device=self.dev)
-            d_lam.index_copy_(0, idx_bg, (d_rgb_sel * b["rgb"]).sum(-1))
-            d_rgb_b = (d_rgb_sel * ctx["bg_lambda"].index_select(0, idx_bg)[:, None]).contiguous()
+            if padded:                       # dL/d rgb of a padding row is exactly 0: the row adds zeros to every sum behind it
+                d_lam, d_rgb_b = o.bg_blend_bwd(d_rgb, idx_bg, ctx["n_bg_dev"], ctx["bg_lambda"], b["rgb"])
+            else:
+                d_rgb_sel = d_rgb.index_select(0, idx_bg)
+                d_lam = torch.zeros(ctx["N"], dtype=torch.float32, device=self.dev)
+                d_lam.index_copy_(0, idx_bg, (d_rgb_sel * b["rgb"]).sum(-1))
+                d_rgb_b = (d_rgb_sel * ctx["bg_lambda"].index_select(0, idx_bg)[:, None]).contiguous()
             d_raw_b = o.composite_bounded_bwd(b["raw"], b["z"], d_rgb_b, None, True, None)
             if Fn > 0:
                 d_f, d_c = o.unmerge_grad(d_raw_b, b["order"], Fn // 2, S // 2)
@@ -267,7 +311,9 @@ class BackgroundScene:
                 bg.backward_net(b["c"], d_raw_b)
         d_raw = o.composite_bounded_bwd(ctx["raw"], ctx["z"], d_rgb, ctx["last_delta"], False, d_lam)
         c = ctx["c"]
-        full = lambda cc, w: torch.full((cc["n_seg"],), w / cc["n_seg"], dtype=torch.float32, device=self.dev)
+        def full(cc, w):
+            t = torch.full((cc["n_seg"],), w / cc["n_seg"], dtype=torch.float32, device=self.dev)
+            return t if loss_scale_dev is None else t * loss_scale_dev
         if Fn > 0:
             d_f, d_c = o.unmerge_grad(d_raw, ctx["order"], Fn, S)
             nerf.backward_net(ctx["cf"], d_f, full(ctx["cf"], wt_fine))
@@ -276,15 +322,24 @@ class BackgroundScene:
             nerf.backward_net(c, d_raw, full(c, wt_coarse))
 
     # ------------------------------------------------------------------------------------------ training step
+    _UNBOUNDED = "Not all your cameras are bounded by the unit sphere; please make sure the cameras are normalized properly!"
+
     def train_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, optimizer_step=True, grad_allreduce=None,
-                   fine_samples=0, **kw):
+                   fine_samples=0, bg_capacity=None, **kw):
         """Runner._training_step with a background model (runner.py:1077-1123): loss = mse(rgb) + wt * gate loss of the
         foreground MoE (the dense background model has none); both models take an Adam step (runner.py:305-318 builds one
-        optimizer over the parameters of both)."""
+        optimizer over the parameters of both).  = grad_step + apply_step.  bg_capacity: the padded form (module doc)."""
+        res = self.grad_step(rgbs, rays, image_indices, n_samples, seg_tokens, perturb, fine_samples, bg_capacity, **kw)
+        return self.apply_step(res, optimizer_step, grad_allreduce)
+
+    def grad_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, fine_samples=0, bg_capacity=None, **kw):
+        """Forward + loss + backward of both models: fills both gradients (zeroed first) and returns train_step's dict without
+        "bg_nerf_rays_present".  In the padded form nothing here reads the host - the loss scale reaches the backward through the
+        models' device scalar - so the launch sequence can be captured (graph.GraphedBackgroundStep)."""
         nerf, bg = self.nerf, self.bg
         nerf.grad.zero_()
         bg.grad.zero_()
-        ctx = self.forward(rays, image_indices, n_samples, seg_tokens, perturb, fine_samples=fine_samples, **kw)
+        ctx = self.forward(rays, image_indices, n_samples, seg_tokens, perturb, fine_samples=fine_samples, bg_capacity=bg_capacity, **kw)
         fine = fine_samples > 0
         gate_loss = ctx["c"]["l_aux"].mean()
         if fine:
@@ -294,13 +349,49 @@ class BackgroundScene:
         loss = photo + nerf.wt * gate_loss
         # fp16 (the reference's single GradScaler over both optimizers, runner.py:483, 679-690): one loss scale - the foreground model's
         # scaler - multiplies the loss gradient; both models unscale by it, and a non-finite gradient in either skips that model's step
-        ls = 1.0
+        ls, ls_dev = 1.0, None
         if self.loss_scaler is not None:
-            ls = float(self.loss_scaler.scale)
             for m in (nerf, bg):
                 m._loss_scale_tensor()                    # (records the scale this backward uses: _found_inf divides by it)
-        d_rgb = (diff * (2.0 * ls / diff.numel())).contiguous()
-        self.backward(ctx, d_rgb, ls * nerf.wt * (0.5 if fine else 1.0), ls * nerf.wt * 0.5)
+            if bg_capacity is None:
+                ls = float(self.loss_scaler.scale)
+            else:
+                ls_dev = nerf._ls_dev                     # the padded form reads the scale on the device (a replay follows it)
+        d_rgb = diff * (2.0 * ls / diff.numel())
+        if ls_dev is not None:
+            d_rgb = d_rgb * ls_dev
+        self.backward(ctx, d_rgb.contiguous(), ls * nerf.wt * (0.5 if fine else 1.0), ls * nerf.wt * 0.5, loss_scale_dev=ls_dev)
+        return dict(loss=loss, photo_loss=photo, gate_loss=gate_loss, psnr=-10.0 * torch.log10(photo), rgb=ctx["rgb"],
+                    depth=ctx["depth"], depth_variance=ctx["depth_variance"].mean(), ctx=ctx)
+
+    def read_counts(self, ctx):
+        """Padded form: the ONE readback of (n_bg, n_out) - 8 bytes, behind everything enqueued so far - into ctx["Nb"] / ctx["n_out"],
+        and the two checks the compact form makes inside forward.  Nothing to do for a compact context."""
+        if ctx.get("C") is None:
+            return
+        if ctx["Nb"] is None:
+            ctx["Nb"], ctx["n_out"] = (int(v) for v in ctx["counts_dev"].tolist())
+        if ctx["n_out"] > 0:
+            raise Exception(self._UNBOUNDED)
+        if ctx["Nb"] > ctx["C"]:
+            raise RuntimeError(f"BackgroundScene: n_bg = {ctx['Nb']} rays of this batch leave the foreground bound but bg_capacity = "
+                               f"{ctx['C']}: the step was computed without the surplus rays and is not applied; raise bg_capacity "
+                               f"(at most the batch's {ctx['N']} rays)")
+
+    def apply_step(self, res, optimizer_step=True, grad_allreduce=None, refresh=None, advance=True):
+        """The tail both forms of the step share: gradient all-reduce, the shared loss scaler, both Adam steps under the bg_present
+        rule, the advance of the noise counter.  -> res with "bg_nerf_rays_present".
+        Padded form: starts with the noise advance (advance=False: it was captured with the step) and the readback of (n_bg, n_out);
+        a batch with cameras outside the bound or with n_bg > bg_capacity raises before any parameter of either model is touched
+        (the noise counter has advanced: that step's draws are skipped).
+        refresh: a replacement for BOTH models' refresh_compute_copies (the replay of their captured graph), run once."""
+        nerf, bg = self.nerf, self.bg
+        ctx = res["ctx"]
+        padded = ctx.get("C") is not None
+        if padded:
+            if advance:
+                self._noise_advance()
+            self.read_counts(ctx)
         # the reference skips the background optimizer on batches without background rays (runner.py:683: `if key == 'bg_nerf'
         # and not bg_nerf_rays_present: continue`): no Adam step, no moment decay, no step-counter increment - in a SINGLE-process
         # run.  In a distributed run ('RANK' in os.environ) render_rays makes a dummy background forward on a rank without background
@@ -321,6 +412,7 @@ class BackgroundScene:
             self.loss_scaler.update(any(found.values()))
             for m in (nerf, bg):
                 m._loss_scale_tensor()
+        stepped = False
         for m in models:
             if optimizer_step and not found[id(m)]:
                 sc = scale[id(m)]
@@ -328,7 +420,12 @@ class BackgroundScene:
                     sc /= m._applied_loss_scale
                 m.step_count += 1
                 ops.adam_step(m.flat, m.grad, m.m, m.v, None, m.step_count, m.lr, grad_scale=sc)
-                m.refresh_compute_copies()
-        self._noise_advance()              # device noise: ONE advance per step, with or without background rays / a background Adam step
-        return dict(loss=loss, photo_loss=photo, gate_loss=gate_loss, psnr=-10.0 * torch.log10(photo), rgb=ctx["rgb"],
-                    depth=ctx["depth"], depth_variance=ctx["depth_variance"].mean(), ctx=ctx, bg_nerf_rays_present=bg_present)
+                if refresh is None:
+                    m.refresh_compute_copies()
+                stepped = True
+        if stepped and refresh is not None:
+            refresh()
+        if not padded and advance:
+            self._noise_advance()          # device noise: ONE advance per step, with or without background rays / a background Adam step
+        res["bg_nerf_rays_present"] = bg_present
+        return res

@@ -268,3 +268,95 @@ class GraphedRenderTrain:
             self.d_laux_f.copy_(d_laux_f)
         self.bwd_graph.replay()
         return self.model.grad
+
+
+class GraphedBackgroundStep:
+    """step = GraphedBackgroundStep(scene, rgbs, rays, image_indices, n_samples, seg_tokens, ...); res = step(rgbs, rays, image_indices)
+
+    The training step of a background.BackgroundScene in its padded form (bg_capacity = C rows for the background model, default the
+    batch's N rays) captured once and replayed - built like GraphedTrainStep: static input buffers, warm-up on a side stream, the
+    device-noise counter put back behind the warm-up, ONE capture of grad.zero_() + forward + loss + backward of both models + the
+    noise advance (BackgroundScene.grad_step), and a second small graph for both models' refresh_compute_copies.  The tail
+    (BackgroundScene.apply_step: the 8-byte readback of (n_bg, n_out), all-reduce, the shared loss scaler, both Adam steps) runs outside
+    the graph.  Same result dict as BackgroundScene.train_step (tensors live in static graph memory: read them before the next call).
+
+    One capture serves every batch of its shape, whatever share of its rays leaves the bound - up to C of them: a batch with more
+    raises RuntimeError, one with cameras outside the bound raises like the eager step, in both cases with no parameter touched (the
+    noise counter has advanced, as in the eager padded step).  With the scene's device noise on (BackgroundScene.set_device_noise) the
+    replays equal the eager padded steps bit for bit; without it the jitter and the sigma noise of both models are drawn inside the graph
+    from the framework's device generator.  Only the plain step (fine_samples = 0) is graphed; the hierarchical padded step stays eager."""
+
+    def __init__(self, scene, rgbs, rays, image_indices, n_samples: int, seg_tokens: int, perturb: float = 1.0, noise_std: float = 1.0,
+                 bg_capacity=None, warmup: int = 2):
+        nerf, bg = scene.nerf, scene.bg
+        N, S = rays.shape[0], int(n_samples)
+        P = N * S
+        if nerf.ep is not None:
+            seg_payload = nerf.E * nerf.capacity(min(int(seg_tokens), P)) * nerf.M * (4 if nerf.dtype == torch.float32 else 2)
+            if not (nerf.ep.capturable and nerf.ep.use_padded(seg_payload)):
+                raise ValueError("GraphedBackgroundStep: the expert-parallel foreground step with unequal splits reads their sizes on the "
+                                 "host and cannot be captured; use BackgroundScene.train_step, or ExpertParallel(..., padded=True)")
+        scene._check_noise_sources()
+        self.scene = scene
+        dev = scene.dev
+        C = self.bg_capacity = N if bg_capacity is None else int(bg_capacity)
+        if not 1 <= C <= N:
+            raise ValueError(f"GraphedBackgroundStep: bg_capacity {C} outside [1, {N} rays]")
+        self.rgbs, self.rays, self.idx = rgbs.clone().contiguous(), rays.clone().contiguous(), image_indices.clone().contiguous()
+        if scene.loss_scaler is not None:
+            for m in (nerf, bg):
+                m._loss_scale_tensor()                     # exist before the capture (read, not created, inside the graph)
+        dn = scene.device_noise                            # on: the step draws from the seeded generator, nothing is passed
+        Sb = S // 2
+
+        def run():
+            kw = {}
+            if not dn:
+                if perturb > 0:
+                    kw.update(perturb_rand=torch.rand(N, S, device=dev), perturb_rand_bg=torch.rand(C, Sb, device=dev))
+                if noise_std > 0:
+                    kw.update(sigma_noise=torch.randn(P, device=dev) * noise_std, sigma_noise_bg="randn")
+            res = scene.grad_step(self.rgbs, self.rays, self.idx, S, min(int(seg_tokens), P), perturb, 0, C, noise_std=noise_std, **kw)
+            scene._noise_advance()
+            return res
+
+        profiles = (nerf.profile, bg.profile)
+        nerf.profile = bg.profile = False
+        step0 = scene.noise_state_dict()["step"]           # the warm-up steps advance the noise counter like real ones: put it back
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                      # warm-up on a side stream: allocates every cached buffer / workspace
+            for _ in range(max(1, warmup)):
+                run()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        if dn:
+            scene._noise_step.fill_(step0)
+            torch.cuda.synchronize()
+        # the background model's cached buffers grow with the largest row count seen (a later eager compact step on a larger batch
+        # replaces them): the capture keeps the ones it baked in alive
+        self._held = list(bg._bufs.values()) + [getattr(bg, "_ones", None)]
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=side):
+            self.res = run()
+        self.copies = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.copies, stream=side):
+            nerf.refresh_compute_copies()
+            bg.refresh_compute_copies()
+        nerf.profile, bg.profile = profiles
+
+    def __call__(self, rgbs=None, rays=None, image_indices=None, grad_allreduce=None, optimizer_step=True):
+        scene = self.scene
+        if rgbs is not None:
+            self.rgbs.copy_(rgbs)
+        if rays is not None:
+            self.rays.copy_(rays)
+        if image_indices is not None:
+            self.idx.copy_(image_indices)
+        if scene.loss_scaler is not None:
+            for m in (scene.nerf, scene.bg):
+                m._loss_scale_tensor()                     # a scale the caller set on the host reaches the device scalar the replay reads
+        self.graph.replay()
+        ctx = self.res["ctx"]
+        ctx["Nb"] = ctx["n_out"] = None                    # the counts of THIS replay are read in apply_step
+        return scene.apply_step(self.res, optimizer_step, grad_allreduce, refresh=self.copies.replay, advance=False)

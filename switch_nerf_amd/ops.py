@@ -851,20 +851,36 @@ def _host3(v):
     return (C.c_float * 3)(*vals)
 
 
-def fg_bounds(rays, center, radius):
+def fg_bounds(rays, center, radius, n_out=None):
     """render_rays' foreground bound (rendering.py:32-44, 497-518) -> rays with the clipped far plane, fg_far [N],
-    last_delta [N] (fg_far for rays that continue into the background, 1e10 otherwise), has_bg [N] int32.
-    Raises like the reference when a ray's closest approach to the centre is outside the bound."""
+    last_delta [N] (fg_far for rays that continue into the background, 1e10 otherwise), has_bg [N] int32, n_out int32 [1] (the rays
+    whose closest approach to the centre is outside the bound: the caller raises like the reference).  n_out: a ZEROED int32 [1] to
+    count into (e.g. a slice of a larger counter tensor), or None."""
     N = rays.shape[0]
     dev = rays.device
     rays_fg = torch.empty_like(rays)
     fg_far = torch.empty(N, dtype=torch.float32, device=dev)
     last_delta = torch.empty(N, dtype=torch.float32, device=dev)
     has_bg = torch.empty(N, dtype=torch.int32, device=dev)
-    n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n_out is None:
+        n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    assert n_out.dtype == torch.int32 and n_out.numel() == 1
     call("swn_fg_bounds", _p(rays), _host3(center), _host3(radius), N, _p(rays_fg), _p(fg_far), _p(last_delta), _p(has_bg), _p(n_out),
          _stream())
     return rays_fg, fg_far, last_delta, has_bg, n_out
+
+
+_bg_t_steps = {}
+
+
+def _bg_linspace(S: int, dev):
+    """linspace(0, 1, S) computed on the host like the reference's, cached per (S, device): no pageable host-to-device copy inside a
+    step (such a copy cannot be captured into a hipGraph)."""
+    key = (int(S), str(dev))
+    t = _bg_t_steps.get(key)
+    if t is None:
+        t = _bg_t_steps[key] = torch.linspace(0, 1, int(S), dtype=torch.float32).to(dev)
+    return t
 
 
 def bg_sample_pe(rays, center, radius, n_samples, l_xyz, dtype, pe_stride, perturb_rand=None, perturb=0.0, z_in=None, pe_out=None):
@@ -875,7 +891,7 @@ def bg_sample_pe(rays, center, radius, n_samples, l_xyz, dtype, pe_stride, pertu
     z = torch.empty(N, S, dtype=torch.float32, device=dev) if z_in is None else z_in
     dreal = torch.empty(N, S, dtype=torch.float32, device=dev)
     pe = pe_out if pe_out is not None else torch.empty(N * S, pe_stride, dtype=dtype, device=dev)
-    t_steps = torch.linspace(0, 1, S, dtype=torch.float32).to(dev) if z_in is None else None
+    t_steps = _bg_linspace(S, dev) if z_in is None else None
     call("swn_bg_sample_pe", _p(rays), _host3(center), _host3(radius), _p(t_steps), _p(perturb_rand), float(perturb), N, S, int(l_xyz),
          _code(dtype), _p(z_in), _p(z) if z_in is None else None, _p(dreal), _p(pe), int(pe_stride), _stream())
     return z, dreal, pe
@@ -892,11 +908,65 @@ def bg_sample_pe_rng(rays, center, radius, n_samples, l_xyz, dtype, pe_stride, s
     z = torch.empty(N, S, dtype=torch.float32, device=dev)
     dreal = torch.empty(N, S, dtype=torch.float32, device=dev)
     pe = pe_out if pe_out is not None else torch.empty(N * S, pe_stride, dtype=dtype, device=dev)
-    t_steps = torch.linspace(0, 1, S, dtype=torch.float32).to(dev)
+    t_steps = _bg_linspace(S, dev)
     call("swn_bg_sample_pe_rng", _p(rays), _host3(center), _host3(radius), _p(t_steps), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev),
          int(ray_base), _p(row_index), limit, float(perturb), N, S, int(l_xyz), _code(dtype), _p(z), _p(dreal), _p(pe), int(pe_stride),
          _stream())
     return z, dreal, pe
+
+
+def bg_pad_ray(center, radius):
+    """The ray of a padding row of the fixed-shape background (bg_compact): origin at the bound's centre, direction (0, 0, 1), near 0,
+    far twice the way to the bound.  Normalised to the unit sphere it starts at the origin, so its background samples, points and
+    metric depths (swn_bg_sample_pe) are finite and every later intermediate of a padding row is."""
+    c = [0.0, 0.0, 0.0] if center is None else [float(x) for x in _host3(center)]
+    rz = 1.0 if radius is None else float(_host3(radius)[2])
+    return (C.c_float * 8)(c[0], c[1], c[2], 0.0, 0.0, 1.0, 0.0, 2.0 * rz)
+
+
+def bg_compact(has_bg, rays, image_indices, capacity: int, pad_ray, n_bg=None):
+    """Stable device-side compaction of the rays with has_bg != 0 into `capacity` rows (swn_bg_compact, include/swn.h) ->
+    idx_bg int64 [C], n_bg int32 [1] (the true count, also above C), rays_b [C, 8], img_b [C]; rows from n_bg on are padding
+    (idx 0, image 0, pad_ray: bg_pad_ray).  n_bg: an int32 [1] to write the count to, or None."""
+    N, Cc = rays.shape[0], int(capacity)
+    if not 1 <= Cc <= N:
+        raise ValueError(f"bg_compact: capacity {Cc} outside [1, {N} rays]")
+    dev = rays.device
+    assert has_bg.dtype == torch.int32 and has_bg.numel() == N and rays.dtype == torch.float32 and tuple(rays.shape) == (N, 8)
+    assert image_indices.numel() == N
+    idx_bg = torch.empty(Cc, dtype=torch.int64, device=dev)
+    if n_bg is None:
+        n_bg = torch.empty(1, dtype=torch.int32, device=dev)
+    assert n_bg.dtype == torch.int32 and n_bg.numel() == 1
+    rays_b = torch.empty(Cc, 8, dtype=torch.float32, device=dev)
+    img_b = torch.empty(Cc, dtype=image_indices.dtype, device=dev)
+    ip, i64 = _idx_arg(image_indices)
+    call("swn_bg_compact", _p(has_bg), _p(rays), ip, i64, pad_ray, N, Cc, _p(idx_bg), _p(n_bg), _p(rays_b), _p(img_b), _stream())
+    return idx_bg, n_bg, rays_b, img_b
+
+
+def _blend_check(idx_bg, n_bg, lam):
+    assert idx_bg.dtype == torch.int64 and n_bg.dtype == torch.int32 and n_bg.numel() == 1 and lam.dtype == torch.float32
+    return lam.numel(), idx_bg.numel()
+
+
+def bg_blend_fwd(rgb, depth, idx_bg, n_bg, lam, rgb_b, depth_b):
+    """IN PLACE: rgb[idx_bg[j]] += rgb_b[j] * lam[idx_bg[j]], depth likewise, for j < min(n_bg, C) (swn_bg_blend_fwd)."""
+    N, Cc = _blend_check(idx_bg, n_bg, lam)
+    assert rgb.dtype == depth.dtype == rgb_b.dtype == depth_b.dtype == torch.float32
+    assert tuple(rgb.shape) == (N, 3) and depth.numel() == N and tuple(rgb_b.shape) == (Cc, 3) and depth_b.numel() == Cc
+    call("swn_bg_blend_fwd", _p(idx_bg), _p(n_bg), _p(lam), _p(rgb_b), _p(depth_b), N, Cc, _p(rgb), _p(depth), _stream())
+    return rgb, depth
+
+
+def bg_blend_bwd(d_rgb, idx_bg, n_bg, lam, rgb_b):
+    """-> d_lam [N] (0 on rays without background), d_rgb_b [C, 3] (exactly 0 on padding rows): swn_bg_blend_bwd."""
+    N, Cc = _blend_check(idx_bg, n_bg, lam)
+    assert d_rgb.dtype == rgb_b.dtype == torch.float32 and tuple(d_rgb.shape) == (N, 3) and tuple(rgb_b.shape) == (Cc, 3)
+    d_lam = torch.empty(N, dtype=torch.float32, device=lam.device)
+    d_rgb_b = torch.empty(Cc, 3, dtype=torch.float32, device=lam.device)
+    call("swn_bg_blend_bwd", _p(idx_bg), _p(n_bg), _p(lam), _p(rgb_b), _p(d_rgb), N, Cc, _p(d_lam), _p(d_rgb_b), _stream())
+    return d_lam, d_rgb_b
 
 
 def composite_bounded_fwd(raw, z, last_delta=None, flip=False, depth_real=None, want_weights=False, want_bg_lambda=False):

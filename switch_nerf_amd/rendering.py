@@ -248,10 +248,14 @@ def _render_rays_bg(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, 
     if use_noise and not dn:        # rendering.py:366: randn per evaluated chunk, for either model
         kw = dict(sigma_noise=torch.randn(N * S, device=rays.device) * std, sigma_noise_bg="randn", sigma_noise_bg_fine="randn",
                   sigma_noise_fine=torch.randn(N * F, device=rays.device) * std if F else None)
+    cap = getattr(hparams, "bg_capacity", None)     # the padded form of the background rows (background.py), when the recipe asks for it
+    if cap is not None:
+        kw["bg_capacity"] = max(1, min(int(cap), N))
     ctx = scene.forward(rays.contiguous(), image_indices, S, min(hparams.model_chunk_size, N * S), float(perturb), fine_samples=F,
                         no_batch=nerf.moe_no_batch, noise_std=std, training=nerf.training, **kw)
     if dn:
         scene._noise_advance()
+    scene.read_counts(ctx)                          # (padded form: the one readback and the checks the compact form made inside forward)
     typ = "fine" if F > 0 else "coarse"
     res = {f"rgb_{typ}": ctx["rgb"], "gate_loss_coarse": ctx["c"]["l_aux"]}
     if F > 0:
