@@ -798,6 +798,33 @@ int swn_cast(const float* in, void* out, int dtype, long n, void* stream);
 /* out[b][c][r] = in[b][r][c]  (fp32 master -> dtype compute copy, transposed) */
 int swn_cast_transpose(const float* in, void* out, int dtype, int batch, int rows, int cols, void* stream);
 
+/* ---- spatial cells (Mega-NeRF) ----------------------------------------------------------------------------------
+ * The cell router of models/mega_nerf.py:19-61 around n_cells <= 64 dense NeRFs (switch_nerf_amd/mega.py): geometric, no parameters,
+ * a point may belong to several cells.  All buffers are the caller's, one stream, no synchronisation inside.
+ * swn_cells_assign: x [n_points, stride] fp32 with the position in columns 0..2, centroids [n_cells, 3].  Distance per (point, cell):
+ *   d = sqrt(sum_{j >= dim_start} (x_j - c_j)^2), evaluated directly in fp32 in ascending j (dim_start 1: cluster_2d).
+ *   margin == 1: weights[p][i] = 1 for the FIRST index of the minimum, 0 elsewhere.  margin > 1: inv = 1 / (d + 1e-8), zero where
+ *   d > margin * d_min, divided by its row sum (added in ascending i).  A member is a cell of weight > 0.
+ *   weights [n_points, n_cells] fp32, counts [n_cells] int32 (members per cell; integer adds, deterministic).                     */
+int swn_cells_assign(const float* x, int stride, const float* centroids, int n_cells, int dim_start, float margin, int n_points,
+                     float* weights, int32_t* counts, void* stream);
+/* swn_cells_pack: the packed row space of a membership.  begin [n_cells + 1] = exclusive scan of counts; rows [begin[n_cells]] = the
+ *   point indices grouped by cell, ascending inside a cell (entries at or past rows_capacity are not written); slot [n_points, n_cells]
+ *   = the row of point p inside cell i, or -1.  Stable: ranks come from ballots and integer prefixes, never from the order of atomics.
+ *   workspace: swn_cells_pack_workspace_bytes().                                                                                    */
+int swn_cells_pack_workspace_bytes(int n_points, int n_cells, size_t* bytes);
+int swn_cells_pack(const float* weights, const int32_t* counts, int n_points, int n_cells, int32_t* begin, int32_t* rows,
+                   long rows_capacity, int32_t* slot, void* workspace, size_t workspace_bytes, void* stream);
+/* swn_cells_gather: x_out [total, stride - col0] = columns [col0, stride) of x[rows[r]] (col0 = 3 drops the real position of an
+ *   xyz_real model, mega_nerf.py:36); noise_out [total] = sigma_noise[rows[r]] when sigma_noise [n_points] is given (both or neither). */
+int swn_cells_gather(const float* x, int stride, int col0, const int32_t* rows, long total, int n_points, const float* sigma_noise,
+                     float* x_out, float* noise_out, void* stream);
+/* swn_cells_blend: out[p][:] = sum over the member cells i, ascending, of weights[p][i] * sub_out[begin[i] + slot[p][i]][:], channels 1
+ *   or 4; hard != 0 (margin == 1): the plain copy of the one member's row (:47).  One thread per point: no atomics, no zero fill,
+ *   the sum order is the reference's loop order.                                                                                   */
+int swn_cells_blend(const float* weights, const int32_t* slot, const int32_t* begin, const float* sub_out, long total, int n_points,
+                    int n_cells, int channels, int hard, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -969,6 +969,58 @@ def bg_blend_bwd(d_rgb, idx_bg, n_bg, lam, rgb_b):
     return d_lam, d_rgb_b
 
 
+def cells_assign(x, centroids, dim_start: int, margin: float):
+    """Spatial-cell membership of the points x [P, stride] (position in columns 0..2) among centroids [K, 3] (swn_cells_assign,
+    mega_nerf.py:21-30) -> weights [P, K] fp32 (margin == 1: one-hot of the first nearest cell), counts [K] int32."""
+    P, K = x.shape[0], centroids.shape[0]
+    assert x.dtype == centroids.dtype == torch.float32 and x.dim() == 2 and centroids.dim() == 2 and centroids.shape[1] == 3
+    weights = torch.empty(P, K, dtype=torch.float32, device=x.device)
+    counts = torch.empty(K, dtype=torch.int32, device=x.device)
+    call("swn_cells_assign", _p(x), x.shape[1], _p(centroids), K, int(dim_start), float(margin), P, _p(weights), _p(counts), _stream())
+    return weights, counts
+
+
+def cells_pack(weights, counts, rows_capacity: Optional[int] = None):
+    """The packed row space of a membership (swn_cells_pack) -> begin [K + 1], rows [rows_capacity] (the first begin[K] entries: point
+    indices by cell, ascending inside a cell), slot [P, K] (row inside the cell, or -1).  rows_capacity defaults to P * K."""
+    P, K = weights.shape
+    assert weights.dtype == torch.float32 and counts.dtype == torch.int32 and counts.numel() == K
+    dev = weights.device
+    cap = P * K if rows_capacity is None else int(rows_capacity)
+    begin = torch.empty(K + 1, dtype=torch.int32, device=dev)
+    rows = torch.empty(cap, dtype=torch.int32, device=dev)
+    slot = torch.empty(P, K, dtype=torch.int32, device=dev)
+    need = C.c_size_t(0)
+    call("swn_cells_pack_workspace_bytes", P, K, C.byref(need))
+    ws = torch.empty(max(1, need.value // 4), dtype=torch.int32, device=dev)
+    call("swn_cells_pack", _p(weights), _p(counts), P, K, _p(begin), _p(rows), cap, _p(slot), _p(ws), need.value, _stream())
+    return begin, rows, slot
+
+
+def cells_gather(x, rows, total: int, col0: int = 0, sigma_noise=None):
+    """x_out [total, stride - col0] = x[rows[r], col0:], noise_out [total] = sigma_noise[rows[r]] or None (swn_cells_gather)."""
+    P, stride = x.shape
+    assert x.dtype == torch.float32 and rows.dtype == torch.int32 and rows.numel() >= total
+    x_out = torch.empty(total, stride - col0, dtype=torch.float32, device=x.device)
+    noise_out = None
+    if sigma_noise is not None:
+        assert sigma_noise.dtype == torch.float32 and sigma_noise.numel() == P
+        noise_out = torch.empty(total, dtype=torch.float32, device=x.device)
+    call("swn_cells_gather", _p(x), stride, int(col0), _p(rows), int(total), P, _p(sigma_noise), _p(x_out), _p(noise_out), _stream())
+    return x_out, noise_out
+
+
+def cells_blend(weights, slot, begin, sub_out, hard: bool):
+    """out [P, C] = sum over the member cells (ascending) of weights * sub_out[begin[i] + slot] (swn_cells_blend), C = sub_out.shape[1]
+    in {1, 4}; hard: the plain copy of the one member's row."""
+    P, K = weights.shape
+    total, Cn = sub_out.shape
+    assert sub_out.dtype == torch.float32 and slot.dtype == begin.dtype == torch.int32 and tuple(slot.shape) == (P, K)
+    out = torch.empty(P, Cn, dtype=torch.float32, device=weights.device)
+    call("swn_cells_blend", _p(weights), _p(slot), _p(begin), _p(sub_out), total, P, K, Cn, 1 if hard else 0, _p(out), _stream())
+    return out
+
+
 def composite_bounded_fwd(raw, z, last_delta=None, flip=False, depth_real=None, want_weights=False, want_bg_lambda=False):
     """Compositing with a per-ray last delta / descending depths / metric depth source / leftover transmittance
     (rendering.py:435-494 with last_delta, flip, depth_real, get_bg_lambda) -> rgb, depth, depth_variance, weights, bg_lambda."""

@@ -95,6 +95,10 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
                 get_bg_fg_rgb: bool = False) -> Tuple[Dict[str, torch.Tensor], bool]:
     if getattr(hparams, "use_cascade", False):
         raise NotImplementedError("use_cascade is outside the hot path")
+    if getattr(nerf, "is_mega_nerf", False) or getattr(bg_nerf, "is_mega_nerf", False):      # the spatial-cell model (--container_path): mega.py
+        from . import mega
+        return mega.render_rays(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, sphere_radius, get_depth,
+                                get_depth_variance, get_bg_fg_rgb)
     _check_affine(nerf, hparams)
     F = int(getattr(hparams, "fine_samples", 0))
     N = rays.shape[0]
