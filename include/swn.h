@@ -789,6 +789,27 @@ int swn_heads_affine_bwd(const void* y, const void* h2, int dtype, const float* 
                          float* dsig, float* d_w_sigma, float* d_b_sigma, float* d_w_color, float* d_b_color, float* group_colsum,
                          float* dT, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- spherical-harmonics colour (--sh_deg d, opts.py:69; sh.hip) ------------------------------------------------------------------
+ * models/nerf.py:137-143 (rgb = nn.Linear(layer_dim // 2, 3 B), B = (d + 1)^2, no activation) and rendering.py:344-347:
+ *     rgb = torch.sigmoid(eval_sh(sh_deg, model_chunk[:, :3 B].view(-1, 3, B), rays_d))
+ * swn_heads_sh_fwd is swn_heads_affine_fwd's sibling (same row layout, rows_per_group, sigma path): w_color [3 B, h2_dim] and
+ * b_color [3 B] fp32, row c B + b = colour c, basis b; dirs [n_points / rows_per_group, 3] fp32, used as given (not normalised);
+ * deg 0..4.  raw[i] = (sigmoid(sum_b Y_b(dirs[i / rows_per_group]) lin[i][c B + b]) c < 3, softplus(..)), lin = h2 Wc^T + bc.  The
+ * contraction is folded into the weights once per ray (sum_b Y_b Wc[c B + b]).  coef (may be NULL): lin [n_points, 3 B] fp32, computed
+ * per point; raw is the same bits with and without it. */
+int swn_heads_sh_fwd(const void* y, const void* h2, int dtype, const float* w_sigma, const float* b_sigma, const float* w_color,
+                     const float* b_color, const float* sigma_noise, const float* dirs, int rows_per_group, int deg, int n_points,
+                     int model_dim, int h2_dim, float* raw, float* coef, void* stream);
+/* swn_heads_bwd with the basis: d_lin[c B + b] = d_raw_c rgb_c (1 - rgb_c) Y_b (rgb from raw).  dh2 (masked by h2 > 0), dsig,
+ * group_colsum (per-ray column sums of the stored dh2 rows; may be NULL), and the four parameter gradients ACCUMULATED: d_w_sigma /
+ * d_b_sigma from block partial sums, d_w_color [3 B, h2_dim] / d_b_color [3 B] from per-ray sums expanded by the basis over blocks of
+ * rays - both through the ordered reduce (fixed order, no atomics).  The direction gets no gradient.  y must be given. */
+int swn_heads_sh_bwd_workspace_bytes(int n_points, int model_dim, int h2_dim, int rows_per_group, int deg, size_t* bytes);
+int swn_heads_sh_bwd(const void* y, const void* h2, int dtype, const float* w_color, const float* b_color, const float* dirs,
+                     const float* raw, const float* d_raw, int n_points, int model_dim, int h2_dim, int rows_per_group, int deg,
+                     void* dh2, float* dsig, float* d_w_sigma, float* d_b_sigma, float* d_w_color, float* d_b_color,
+                     float* group_colsum, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimiser -------------------------------------------------------------------------------------------------
  * torch.optim.Adam (runner.py:486) over one flat fp32 parameter buffer; grad_scale multiplies the gradient
  * (1/world_size after a sum all-reduce).  Also refreshes the compute copies: shadow (dtype) same layout.         */

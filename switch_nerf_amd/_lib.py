@@ -152,6 +152,9 @@ SIGNATURES = {
     "swn_heads_affine_fwd": [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp],
     "swn_heads_affine_bwd_workspace_bytes": [i32, i32, i32, i32, C.POINTER(sz)],
     "swn_heads_affine_bwd": [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "swn_heads_sh_fwd": [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp],
+    "swn_heads_sh_bwd_workspace_bytes": [i32, i32, i32, i32, i32, C.POINTER(sz)],
+    "swn_heads_sh_bwd": [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "swn_cells_assign": [vp, i32, vp, i32, i32, f32, i32, vp, vp, vp],
     "swn_cells_pack_workspace_bytes": [i32, i32, C.POINTER(sz)],
     "swn_cells_pack": [vp, vp, i32, i32, vp, vp, i64, vp, vp, sz, vp],

@@ -45,6 +45,8 @@ class BackgroundScene:
         if getattr(nerf, "affine", False):      # (the reference builds BOTH models from hparams.affine_appearance: model_utils.py:90-120)
             raise NotImplementedError("affine_appearance is not built for scenes with a background model: the dense background NeRF "
                                       "(models/nerf.py:117) has no affine branch")
+        if getattr(nerf, "sh_deg", None) is not None or getattr(bg_nerf, "sh_deg", None) is not None:
+            raise NotImplementedError("sh_deg: spherical-harmonics colour is not built for scenes with a background model")
         self.nerf, self.bg = nerf, bg_nerf
         self.center, self.radius = sphere_center, sphere_radius
         bg_nerf._grow_bufs = True           # the number of background rays changes every batch

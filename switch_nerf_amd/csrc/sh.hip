@@ -1,0 +1,443 @@
+// Spherical-harmonics colour (--sh_deg d, opts.py:69; models/nerf.py:137-143 + rendering.py:317-349): the colour head emits 3 B
+// coefficients per point, B = (d + 1)^2, row c B + b of the head belonging to colour c and basis function b, and
+//     rgb_c[i] = sigmoid(sum_b Y_b(dir[ray(i)]) lin[i][c B + b]),      lin[i] = h2[i] Wc^T + bc        (Wc [3 B, H2], bc [3 B])
+// with Y_b the real spherical-harmonics polynomials of the ray direction, taken as given (the reference does not normalise it).
+//
+// The direction is constant along a ray and the contraction is linear, so it is folded into the WEIGHTS once per ray,
+//     Weff[c] = sum_b Y_b Wc[c B + b]   (3 x H2),      beff[c] = sum_b Y_b bc[c B + b],      rgb_c[i] = sigmoid(h2[i] . Weff[c] + beff[c]),
+// and every point of the ray runs the plain three-row head against Weff in LDS: 3 B H2 multiply-adds per RAY plus 3 H2 per point
+// instead of 3 B H2 per point, whatever the degree - the kernels stay bound by reading y and h2.  The backward uses the same fold:
+// d_lin[c B + b] = p_c Y_b with p_c = d_raw_c rgb_c (1 - rgb_c), so dh2 = sum_c p_c Weff[c], and the weight gradient factors per ray,
+//     d_Wc[c B + b] = sum_rays Y_b(ray) A_c(ray),      A_c(ray) = sum_{i in ray} p_c[i] h2[i]      (3 x H2 per ray),
+// formed in two steps: the heads' launch leaves A_c and sum_i p_c per ray, a second small launch expands them by the basis over
+// blocks of rays, and the existing ordered reduce adds the blocks.  Arithmetic is fp32 (one exception: the terms of d_b_sigma, see
+// heads_sh_bwd_kernel), no atomics, every cross-thread sum is added in a fixed order.  The optional `coef` output (the module's return value, octree sampling) is computed directly per point.
+#include "common.hpp"
+#include "row16.hpp"
+
+namespace swn {
+
+constexpr int SH_MAXB = 25;      // (4 + 1)^2
+
+// Real spherical harmonics up to degree 4 as polynomials of an (unnormalised) direction, with the sign of each term folded into
+// its value: Y[b] multiplies coefficient b.
+__device__ __forceinline__ void sh_basis(int deg, float x, float y, float z, float* Y) {
+#pragma unroll
+  for (int b = 0; b < SH_MAXB; ++b) Y[b] = 0.f;
+  Y[0] = 0.28209479177387814f;
+  if (deg < 1) return;
+  const float k1 = 0.4886025119029199f;
+  Y[1] = -k1 * y;
+  Y[2] = k1 * z;
+  Y[3] = -k1 * x;
+  if (deg < 2) return;
+  const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+  const float k2 = 1.0925484305920792f;
+  Y[4] = k2 * xy;
+  Y[5] = -k2 * yz;
+  Y[6] = 0.31539156525252005f * (2.f * zz - xx - yy);
+  Y[7] = -k2 * xz;
+  Y[8] = 0.5462742152960396f * (xx - yy);
+  if (deg < 3) return;
+  const float k3a = 0.5900435899266435f, k3b = 0.4570457994644658f;
+  Y[9] = -k3a * y * (3.f * xx - yy);
+  Y[10] = 2.890611442640554f * xy * z;
+  Y[11] = -k3b * y * (4.f * zz - xx - yy);
+  Y[12] = 0.3731763325901154f * z * (2.f * zz - 3.f * xx - 3.f * yy);
+  Y[13] = -k3b * x * (4.f * zz - xx - yy);
+  Y[14] = 1.445305721320277f * z * (xx - yy);
+  Y[15] = -k3a * x * (xx - 3.f * yy);
+  if (deg < 4) return;
+  const float k4a = 1.7701307697799304f, k4b = 0.6690465435572892f;
+  Y[16] = 2.5033429417967046f * xy * (xx - yy);
+  Y[17] = -k4a * yz * (3.f * xx - yy);
+  Y[18] = 0.9461746957575601f * xy * (7.f * zz - 1.f);
+  Y[19] = -k4b * yz * (7.f * zz - 3.f);
+  Y[20] = 0.10578554691520431f * (zz * (35.f * zz - 30.f) + 3.f);
+  Y[21] = -k4b * xz * (7.f * zz - 3.f);
+  Y[22] = 0.47308734787878004f * (xx - yy) * (7.f * zz - 1.f);
+  Y[23] = -k4a * xz * (xx - 3.f * yy);
+  Y[24] = 0.6258357354491761f * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy));
+}
+
+// a + b as an unevaluated pair: s = fl(a + b), e = the rounding error of that add, exactly (Knuth's TwoSum; plain fp32 adds, no
+// reassociation: the library is not built with fast-math)
+__device__ __forceinline__ void two_sum(float a, float b, float& s, float& e) {
+  s = a + b;
+  const float bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+
+// The fold of one ray, by the whole block: ys = the basis at dir, weff[c][lane][value] = Weff[c] in the 16-lane row layout (each lane's
+// weights in its own value order, like wc_lds of swn_heads_bwd), beff[c].  Ends in a barrier; the caller puts one in front of the next fold.
+template <typename RH, int H2>
+__device__ __forceinline__ void sh_fold(const float* __restrict__ wc, const float* __restrict__ bc, const float* __restrict__ dir, int deg,
+                                        float* ys, float (*weff)[16][RH::VPL], float* beff) {
+  const int B = (deg + 1) * (deg + 1);
+  if (threadIdx.x == 0) {
+    float Y[SH_MAXB];
+    sh_basis(deg, dir[0], dir[1], dir[2], Y);
+#pragma unroll
+    for (int b = 0; b < SH_MAXB; ++b) ys[b] = Y[b];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 3 * H2; e += 256) {
+    const int c = e / H2, col = e - c * H2;
+    const float* w = wc + (long)c * B * H2 + col;
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) acc = fmaf(ys[b], w[(long)b * H2], acc);
+    const int chunk = col / RH::EPC, within = col - chunk * RH::EPC;      // the inverse of Row16::col
+    weff[c][chunk & 15][(chunk >> 4) * RH::EPC + within] = acc;
+  }
+  if (threadIdx.x < 3) {
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) acc = fmaf(ys[b], bc[threadIdx.x * B + b], acc);
+    beff[threadIdx.x] = acc;
+  }
+  __syncthreads();
+}
+
+// raw[i] = (sigmoid(h2[i] . Weff[c] + beff[c]) c < 3, softplus(y . ws + bs + noise - 1)); coef[i] = h2[i] Wc^T + bc when asked for.
+// A block walks whole rays (units of rows_per_group rows), its 16-lane groups the unit's rows q, q + 16, ...
+template <typename T_, int M, int H2>
+__global__ __launch_bounds__(256) void heads_sh_fwd_kernel(const T_* __restrict__ y, const T_* __restrict__ h2, const float* __restrict__ ws,
+                                                           const float* __restrict__ bs, const float* __restrict__ wc,
+                                                           const float* __restrict__ bc, const float* __restrict__ noise,
+                                                           const float* __restrict__ dirs, int rows_per_group, int deg, long P,
+                                                           float* __restrict__ raw, float* __restrict__ coef) {
+  using RY = Row16<T_, M>;
+  using RH = Row16<T_, H2>;
+  __shared__ float ys[SH_MAXB];
+  __shared__ float weff[3][16][RH::VPL];
+  __shared__ float beff[3];
+  const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const int B = (deg + 1) * (deg + 1);
+  float wsv[RY::VPL];
+  RY::loadf(ws, j, wsv);
+  const float b_s = bs[0];
+  const long rows = rows_per_group, n_units = P / rows_per_group;
+  for (long u = blockIdx.x; u < n_units; u += gridDim.x) {
+    sh_fold<RH, H2>(wc, bc, dirs + u * 3, deg, ys, weff, beff);
+    const float b0 = beff[0], b1 = beff[1], b2 = beff[2];
+    for (long r = grp; r < rows; r += 16) {
+      const long i = u * rows + r;
+      float yv[RY::VPL], hv[RH::VPL];
+      RY::load(y + i * M, j, yv);
+      RH::load(h2 + i * H2, j, hv);
+      float s = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
+#pragma unroll
+      for (int v = 0; v < RY::VPL; ++v) s += yv[v] * wsv[v];
+#pragma unroll
+      for (int v = 0; v < RH::VPL; ++v) { c0 += hv[v] * weff[0][j][v]; c1 += hv[v] * weff[1][j][v]; c2 += hv[v] * weff[2][j][v]; }
+      s = sum16(s); c0 = sum16(c0); c1 = sum16(c1); c2 = sum16(c2);
+      if (j == 0) {
+        const float uu = s + b_s + (noise ? noise[i] : 0.f) - 1.f;  // ShiftedSoftplus, models/nerf.py:68-69
+        float4 o;
+        o.x = 1.f / (1.f + expf(-(c0 + b0)));
+        o.y = 1.f / (1.f + expf(-(c1 + b1)));
+        o.z = 1.f / (1.f + expf(-(c2 + b2)));
+        o.w = uu > 20.f ? uu : log1pf(expf(uu));
+        *(float4*)(raw + i * 4) = o;
+      }
+      if (coef) {      // the linear outputs themselves (not on the training path): one row of Wc at a time, from global memory
+        for (int k = 0; k < 3 * B; ++k) {
+          float wv[RH::VPL];
+          RH::loadf(wc + (long)k * H2, j, wv);
+          float a = 0.f;
+#pragma unroll
+          for (int v = 0; v < RH::VPL; ++v) a += hv[v] * wv[v];
+          a = sum16(a);
+          if (j == 0) coef[i * (3 * B) + k] = a + bc[k];
+        }
+      }
+    }
+    __syncthreads();      // (the next unit's fold overwrites weff)
+  }
+}
+
+// The backward of the heads with the fold.  Per unit (ray): dh2 rows (masked by h2 > 0), dsig, rowsum[u] = the column sums of the dh2 rows
+// as stored, and ray_acc[u] = [A_0 | A_1 | A_2 | sum p_0, sum p_1, sum p_2, 0]  (3 H2 + 4 floats), the 16 row stripes added in a fixed
+// order.  The block's sums for d_w_sigma and d_b_sigma -> partial[block] (M + 2 floats).  d_b_sigma is ONE scalar summed over every
+// point, signed terms that cancel: it is carried as a compensated fp32 pair (sum, accumulated rounding errors) from the first add to
+// the last (sh_bsig_reduce_kernel), so that its error is a rounding of the result and not a random walk over the partial sums.
+template <typename T_, int M, int H2>
+__global__ __launch_bounds__(256) void heads_sh_bwd_kernel(const T_* __restrict__ y, const T_* __restrict__ h2, const float* __restrict__ wc,
+                                                           const float* __restrict__ bc, const float* __restrict__ dirs,
+                                                           const float* __restrict__ raw, const float* __restrict__ d_raw, long P,
+                                                           int rows_per_group, int deg, T_* __restrict__ dh2, float* __restrict__ dsig,
+                                                           float* __restrict__ rowsum, float* __restrict__ ray_acc,
+                                                           float* __restrict__ partial) {
+  using RY = Row16<T_, M>;
+  using RH = Row16<T_, H2>;
+  constexpr int ACC = 3 * H2 + 4;
+  __shared__ float ys[SH_MAXB];
+  __shared__ float weff[3][16][RH::VPL];
+  __shared__ float beff[3];
+  __shared__ float st_lds[16][H2];      // the 16 row stripes of one quantity at a time
+  __shared__ float p_lds[16][3];
+  const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  float aws[RY::VPL], abs_ = 0.f, abs_lo = 0.f;
+#pragma unroll
+  for (int v = 0; v < RY::VPL; ++v) aws[v] = 0.f;
+  const long rows = rows_per_group, n_units = P / rows_per_group;
+  for (long u = blockIdx.x; u < n_units; u += gridDim.x) {
+    sh_fold<RH, H2>(wc, bc, dirs + u * 3, deg, ys, weff, beff);
+    float cs[RH::VPL], awc[3][RH::VPL], ap0 = 0.f, ap1 = 0.f, ap2 = 0.f;
+#pragma unroll
+    for (int v = 0; v < RH::VPL; ++v) { cs[v] = 0.f; awc[0][v] = 0.f; awc[1][v] = 0.f; awc[2][v] = 0.f; }
+    for (long r = grp; r < rows; r += 16) {
+      const long i = u * rows + r;
+      const float4 rr = *(const float4*)(raw + i * 4);
+      const float4 d = *(const float4*)(d_raw + i * 4);
+      uint4 yr[RY::NCH], hr[RH::NCH];
+      RY::load_raw(y + i * M, j, yr);
+      RH::load_raw(h2 + i * H2, j, hr);
+      const float p0 = d.x * rr.x * (1.f - rr.x), p1 = d.y * rr.y * (1.f - rr.y), p2 = d.z * rr.z * (1.f - rr.z);
+      const float dsp = d.w * -expm1f(-rr.w);      // softplus'(u) = 1 - exp(-softplus(u))
+      if (j == 0) {
+        dsig[i] = dsp;
+        // the bias term once more in double (this lane only): over 10^4 .. 10^6 signed terms the fp32 roundings of expm1f and of the
+        // product are a random walk larger than the sum's own rounding; dsig itself and every other sum stay fp32
+        const double t_ = (double)d.w * (1.0 - exp(-(double)rr.w));
+        const float th_ = (float)t_;
+        float e_;
+        two_sum(abs_, th_, abs_, e_);
+        abs_lo += e_ + (float)(t_ - (double)th_);
+      }
+      ap0 += p0; ap1 += p1; ap2 += p2;
+      float yv[RY::VPL];
+      RY::unpack(yr, yv);
+#pragma unroll
+      for (int v = 0; v < RY::VPL; ++v) aws[v] += dsp * yv[v];
+      float hv[RH::VPL], o[RH::VPL];
+      RH::unpack(hr, hv);
+#pragma unroll
+      for (int v = 0; v < RH::VPL; ++v) {
+        awc[0][v] += p0 * hv[v]; awc[1][v] += p1 * hv[v]; awc[2][v] += p2 * hv[v];
+        const float gg = p0 * weff[0][j][v] + p1 * weff[1][j][v] + p2 * weff[2][j][v];
+        o[v] = hv[v] > 0.f ? gg + 0.f : 0.f;      // (+ 0: a row whose d_raw is zero leaves +0 whatever the weights' signs)
+      }
+      RH::store(dh2 + i * H2, j, o);
+      if constexpr (sizeof(T_) == 2) {
+#pragma unroll
+        for (int v = 0; v < RH::VPL; v += 2) {           // what the store kept: the values rounded to T_
+          const uint32_t pk = pack_bf16x2(o[v], o[v + 1]);
+          cs[v] += bf16_to_f32((bf16_t)(pk & 0xFFFF));
+          cs[v + 1] += bf16_to_f32((bf16_t)(pk >> 16));
+        }
+      } else {
+#pragma unroll
+        for (int v = 0; v < RH::VPL; ++v) cs[v] += o[v];
+      }
+    }
+    // the 16 row stripes meet in LDS, one quantity after the other, each added in a fixed order
+    float* acc_out = ray_acc + u * ACC;
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int v = 0; v < RH::VPL; ++v) st_lds[grp][RH::col(j, v)] = q == 0 ? cs[v] : awc[q - 1][v];
+      if (q == 0 && j == 0) { p_lds[grp][0] = ap0; p_lds[grp][1] = ap1; p_lds[grp][2] = ap2; }
+      __syncthreads();
+      float* dst = q == 0 ? (rowsum ? rowsum + u * H2 : nullptr) : acc_out + (q - 1) * H2;
+      if (dst) {
+        for (int c = threadIdx.x; c < H2; c += 256) {
+          float s_ = 0.f;
+#pragma unroll
+          for (int g = 0; g < 16; ++g) s_ += st_lds[g][c];
+          dst[c] = s_;
+        }
+      }
+      if (q == 0 && threadIdx.x < 4) {
+        float s_ = 0.f;
+        if (threadIdx.x < 3) {
+#pragma unroll
+          for (int g = 0; g < 16; ++g) s_ += p_lds[g][threadIdx.x];
+        }
+        acc_out[3 * H2 + threadIdx.x] = s_;
+      }
+      __syncthreads();
+    }
+  }
+  // block-level reduction of the sigma head's sums, the 16 row groups one after the other; ordered_reduce_kernel adds the blocks in order
+  __shared__ float red[M + 2];
+  for (int t = threadIdx.x; t < M + 2; t += 256) red[t] = 0.f;
+  __syncthreads();
+  for (int gq = 0; gq < 16; ++gq) {
+    if (grp == gq) {
+#pragma unroll
+      for (int v = 0; v < RY::VPL; ++v) red[RY::col(j, v)] += aws[v];
+      if (j == 0) {
+        float s_, e_;
+        two_sum(red[M], abs_, s_, e_);
+        red[M] = s_;
+        red[M + 1] += e_ + abs_lo;
+      }
+    }
+    __syncthreads();
+  }
+  float* part = partial + (size_t)blockIdx.x * (M + 2);     // [M | b_sigma: sum, rounding errors]
+  for (int t = threadIdx.x; t < M + 2; t += 256) part[t] = red[t];
+}
+
+// d_b_sigma += the blocks' pairs (columns M, M + 1 of partial, row stride M + 2), added in ascending order with two_sum: lane l takes
+// the run of consecutive blocks l * per .. , lane 0 then adds the 64 run pairs in order.  One wave, fixed order: the same bits every run.
+__global__ __launch_bounds__(64) void sh_bsig_reduce_kernel(const float* __restrict__ partial, int n_blocks, int M, float* __restrict__ d_bs) {
+  __shared__ float hi[64], lo[64];
+  const int per = (n_blocks + 63) / 64, b0 = threadIdx.x * per, b1 = n_blocks < b0 + per ? n_blocks : b0 + per;
+  float s = 0.f, c = 0.f;
+  for (int b = b0; b < b1; ++b) {
+    const float* q = partial + (size_t)b * (M + 2) + M;
+    float e_;
+    two_sum(s, q[0], s, e_);
+    c += e_ + q[1];
+  }
+  hi[threadIdx.x] = s;
+  lo[threadIdx.x] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float S = 0.f, C = 0.f;
+    for (int l = 0; l < 64; ++l) {
+      float e_;
+      two_sum(S, hi[l], S, e_);
+      C += e_ + lo[l];
+    }
+    d_bs[0] += S + C;
+  }
+}
+
+// The per-ray sums expanded by the basis over SRB rays per block, rays in ascending order:
+// partial[block] = [sum_n Y_b(n) A_c(n)  (3 B x H2, row c B + b) | sum_n Y_b(n) sum p_c(n)  (3 B)]; ordered_reduce_kernel adds the blocks.
+constexpr int SRB = 64;
+__global__ __launch_bounds__(256) void sh_wgrad_kernel(const float* __restrict__ ray_acc, const float* __restrict__ dirs, long n_units, int deg,
+                                                       int H2, float* __restrict__ partial) {
+  __shared__ float ysr[SRB][SH_MAXB];
+  const int B = (deg + 1) * (deg + 1), ACC = 3 * H2 + 4;
+  const long r0 = (long)blockIdx.x * SRB;
+  const int nr = (int)(n_units - r0 < SRB ? n_units - r0 : SRB);
+  if (threadIdx.x < SRB) {
+    float Y[SH_MAXB];
+    if ((int)threadIdx.x < nr) {
+      const float* dir = dirs + (r0 + threadIdx.x) * 3;
+      sh_basis(deg, dir[0], dir[1], dir[2], Y);
+    } else {
+#pragma unroll
+      for (int b = 0; b < SH_MAXB; ++b) Y[b] = 0.f;
+    }
+#pragma unroll
+    for (int b = 0; b < SH_MAXB; ++b) ysr[threadIdx.x][b] = Y[b];
+  }
+  __syncthreads();
+  const int nw = 3 * B * H2, np = nw + 3 * B;
+  float* part = partial + (size_t)blockIdx.x * np;
+  for (int e = threadIdx.x; e < np; e += 256) {
+    int b;
+    const float* src;
+    if (e < nw) {
+      const int k = e / H2, col = e - k * H2, c = k / B;
+      b = k - c * B;
+      src = ray_acc + r0 * ACC + c * H2 + col;
+    } else {
+      const int k = e - nw, c = k / B;
+      b = k - c * B;
+      src = ray_acc + r0 * ACC + 3 * H2 + c;
+    }
+    float acc = 0.f;
+    for (int n = 0; n < nr; ++n) acc = fmaf(ysr[n][b], src[(long)n * ACC], acc);
+    part[e] = acc;
+  }
+}
+
+static int sh_blocks(long n_units) { return n_units > 2048 ? 2048 : (n_units < 1 ? 1 : (int)n_units); }
+
+// the three parts of the backward's workspace, each a multiple of 64 floats
+struct ShWs { size_t sig, ray, wg; };
+static ShWs sh_ws(int n_points, int model_dim, int h2_dim, int rows_per_group, int deg) {
+  const long n_units = n_points / rows_per_group;
+  const int B = (deg + 1) * (deg + 1);
+  auto up = [](size_t n) { return (n + 63) / 64 * 64; };
+  ShWs w;
+  w.sig = up((size_t)sh_blocks(n_units) * (size_t)(model_dim + 2));
+  w.ray = up((size_t)(n_units > 0 ? n_units : 1) * (size_t)(3 * h2_dim + 4));
+  w.wg = up((size_t)cdiv(n_units > 0 ? n_units : 1, SRB) * (size_t)(3 * B * h2_dim + 3 * B));
+  return w;
+}
+
+}  // namespace swn
+
+using namespace swn;
+
+#define SWN_SH_DISPATCH(MACRO)                                                                                                    \
+  do {                                                                                                                            \
+    if (dtype == SWN_HALF) {                                                                                                      \
+      if (model_dim == 256 && h2_dim == 128) MACRO(bf16_t, 256, 128); else if (model_dim == 512 && h2_dim == 256) MACRO(bf16_t, 512, 256); \
+      else if (model_dim == 256) MACRO(bf16_t, 256, 256); else MACRO(bf16_t, 512, 128);                                           \
+    } else {                                                                                                                      \
+      if (model_dim == 256 && h2_dim == 128) MACRO(float, 256, 128); else if (model_dim == 512 && h2_dim == 256) MACRO(float, 512, 256); \
+      else if (model_dim == 256) MACRO(float, 256, 256); else MACRO(float, 512, 128);                                             \
+    }                                                                                                                             \
+  } while (0)
+
+extern "C" int swn_heads_sh_fwd(const void* y, const void* h2, int dtype, const float* w_sigma, const float* b_sigma, const float* w_color,
+                                const float* b_color, const float* sigma_noise, const float* dirs, int rows_per_group, int deg,
+                                int n_points, int model_dim, int h2_dim, float* raw, float* coef, void* stream) {
+  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "swn_heads_sh_fwd: bad dtype");
+  SWN_CHECK(y && h2 && w_sigma && b_sigma && w_color && b_color && dirs && raw, "swn_heads_sh_fwd: null pointer");
+  SWN_CHECK((model_dim == 256 || model_dim == 512) && (h2_dim == 128 || h2_dim == 256),
+            "swn_heads_sh_fwd: model_dim in {256,512}, h2_dim in {128,256}");
+  SWN_CHECK(deg >= 0 && deg <= 4, "swn_heads_sh_fwd: deg %d outside 0..4", deg);
+  SWN_CHECK(n_points >= 0 && rows_per_group > 0 && n_points % rows_per_group == 0,
+            "swn_heads_sh_fwd: rows_per_group %d must be positive and divide n_points %d", rows_per_group, n_points);
+  if (n_points == 0) return 0;
+  const int blocks = sh_blocks(n_points / rows_per_group);
+#define SWN_SHF(T_, M_, H_) hipLaunchKernelGGL((heads_sh_fwd_kernel<T_, M_, H_>), dim3(blocks), dim3(256), 0, as_stream(stream), (const T_*)y, \
+                                               (const T_*)h2, w_sigma, b_sigma, w_color, b_color, sigma_noise, dirs, rows_per_group, deg,      \
+                                               (long)n_points, raw, coef)
+  SWN_SH_DISPATCH(SWN_SHF);
+#undef SWN_SHF
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_heads_sh_bwd_workspace_bytes(int n_points, int model_dim, int h2_dim, int rows_per_group, int deg, size_t* bytes) {
+  SWN_CHECK(bytes && n_points >= 0 && rows_per_group > 0 && deg >= 0 && deg <= 4 && model_dim > 0 && h2_dim > 0,
+            "swn_heads_sh_bwd_workspace_bytes: bad arguments");
+  const ShWs w = sh_ws(n_points, model_dim, h2_dim, rows_per_group, deg);
+  *bytes = (w.sig + w.ray + w.wg) * sizeof(float);
+  return 0;
+}
+
+extern "C" int swn_heads_sh_bwd(const void* y, const void* h2, int dtype, const float* w_color, const float* b_color, const float* dirs,
+                                const float* raw, const float* d_raw, int n_points, int model_dim, int h2_dim, int rows_per_group, int deg,
+                                void* dh2, float* dsig, float* d_w_sigma, float* d_b_sigma, float* d_w_color, float* d_b_color,
+                                float* group_colsum, void* workspace, size_t workspace_bytes, void* stream) {
+  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "swn_heads_sh_bwd: bad dtype");
+  SWN_CHECK(y && h2 && w_color && b_color && dirs && raw && d_raw && dh2 && dsig && d_w_sigma && d_b_sigma && d_w_color && d_b_color && workspace,
+            "swn_heads_sh_bwd: null pointer");      // (group_colsum may be NULL)
+  SWN_CHECK((model_dim == 256 || model_dim == 512) && (h2_dim == 128 || h2_dim == 256),
+            "swn_heads_sh_bwd: model_dim in {256,512}, h2_dim in {128,256}");
+  SWN_CHECK(deg >= 0 && deg <= 4, "swn_heads_sh_bwd: deg %d outside 0..4", deg);
+  SWN_CHECK(n_points >= 0 && rows_per_group > 0 && n_points % rows_per_group == 0,
+            "swn_heads_sh_bwd: rows_per_group %d must be positive and divide n_points %d", rows_per_group, n_points);
+  size_t need = 0;
+  swn_heads_sh_bwd_workspace_bytes(n_points, model_dim, h2_dim, rows_per_group, deg, &need);
+  SWN_CHECK(workspace_bytes >= need, "swn_heads_sh_bwd: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  if (n_points == 0) return 0;
+  const long n_units = n_points / rows_per_group;
+  const int B = (deg + 1) * (deg + 1), blocks = sh_blocks(n_units), nb2 = cdiv(n_units, SRB);
+  const ShWs w = sh_ws(n_points, model_dim, h2_dim, rows_per_group, deg);
+  float* p_sig = (float*)workspace;
+  float* ray_acc = p_sig + w.sig;
+  float* p_wg = ray_acc + w.ray;
+#define SWN_SHB(T_, M_, H_) hipLaunchKernelGGL((heads_sh_bwd_kernel<T_, M_, H_>), dim3(blocks), dim3(256), 0, as_stream(stream), (const T_*)y, \
+                                               (const T_*)h2, w_color, b_color, dirs, raw, d_raw, (long)n_points, rows_per_group, deg,         \
+                                               (T_*)dh2, dsig, group_colsum, ray_acc, p_sig)
+  SWN_SH_DISPATCH(SWN_SHB);
+#undef SWN_SHB
+  OrdDst od{{d_w_sigma, nullptr, nullptr, nullptr}, {model_dim, 0, 0, 0}};      // (the two columns behind it go to no destination here)
+  ordered_reduce_async(p_sig, blocks, model_dim + 2, od, true, as_stream(stream));
+  hipLaunchKernelGGL(sh_bsig_reduce_kernel, dim3(1), dim3(64), 0, as_stream(stream), p_sig, blocks, model_dim, d_b_sigma);
+  hipLaunchKernelGGL(sh_wgrad_kernel, dim3(nb2), dim3(256), 0, as_stream(stream), ray_acc, dirs, n_units, deg, h2_dim, p_wg);
+  OrdDst oc{{d_w_color, d_b_color, nullptr, nullptr}, {3 * B * h2_dim, 3 * B, 0, 0}};
+  ordered_reduce_async(p_wg, nb2, 3 * B * h2_dim + 3 * B, oc, true, as_stream(stream));
+  SWN_LAUNCH_CHECK();
+  return 0;
+}

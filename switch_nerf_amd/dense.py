@@ -15,6 +15,11 @@ weight gradient of the skip layer is two GEMMs (h^T dZ, enc^T dZ).
 
 The state_dict layout is the reference NeRF's (xyz_encodings.{i}.0.weight, xyz_encoding_final.weight, dir_a_encoding.0.*,
 sigma.*, rgb.*, embedding_a.weight), so checkpoints interchange.
+
+cfg["sh_deg"] = d (0..4; --sh_deg, opts.py:69): spherical-harmonics colour.  pos_dir_dim is 0 (nerf.py:82-83), so layer "2" sees
+[xyz_encoding_final, embedding] with NO direction block (in_dir = 0), the colour head has 3 (d + 1)^2 rows (nerf.py:137-143) and
+rendering.py:344-347 turns a point's coefficients into rgb with sigmoid(eval_sh(d, coef, ray direction)): the heads run as
+swn_heads_sh_fwd / swn_heads_sh_bwd (csrc/sh.hip) behind the unfused tail, like an affine model's.
 """
 from __future__ import annotations
 
@@ -31,22 +36,42 @@ DENSE = dict(layer_dim=256, layers=8, skip_layers=(4,), pos_xyz_dim=12, pos_dir_
              appearance_count=1920, xyz_dim=3)
 
 
+def validate_sh_cfg(cfg):
+    """cfg["sh_deg"] -> None or the degree 0..4; the combinations the dense path does not build raise, naming the key."""
+    d = cfg.get("sh_deg")
+    if d is None:
+        return None
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 0 <= int(d) <= 4:
+        raise ValueError(f"sh_deg = {d!r}: None or an integer 0..4 (spherical_harmonics.py:68)")
+    if cfg.get("affine_appearance", False):
+        raise NotImplementedError("sh_deg with affine_appearance is not built (the dense NeRF has no affine branch here)")
+    if cfg["pos_dir_dim"] != 0:
+        raise ValueError(f"sh_deg needs pos_dir_dim == 0 (models/nerf.py:82-83: rgb_dim > 3 asserts it), got pos_dir_dim = {cfg['pos_dir_dim']}")
+    if cfg["appearance_dim"] <= 0:
+        raise NotImplementedError("sh_deg with appearance_dim == 0 is a different topology (no xyz_encoding_final / dir_a_encoding: rgb "
+                                  "reads xyz_ directly, models/nerf.py:123-139, :185) and is not built")
+    return int(d)
+
+
 class DenseNeRF(SwitchNeRF):
     def __init__(self, cfg: dict = DENSE, dtype=torch.bfloat16, device="cuda", lr=5e-4, seed=0):
         super().__init__(cfg, dtype, device, capacity_factor=1.0, batch_prioritized=False, moe_l_aux_wt=0.0, lr=lr, seed=seed)
 
     def _configure(self, cfg):
         if cfg.get("affine_appearance", False):
-            raise NotImplementedError("affine_appearance is not built for the dense NeRF (models/nerf.py:117): only SwitchNeRF applies it")
+            raise NotImplementedError("affine_appearance is not built for the dense NeRF (models/nerf.py:117): only SwitchNeRF applies it"
+                                      + (" (sh_deg with affine_appearance included)" if cfg.get("sh_deg") is not None else ""))
+        self.sh_deg = validate_sh_cfg(cfg)
         W, L, xd = cfg["layer_dim"], cfg["layers"], cfg.get("xyz_dim", 3)
         skips = tuple(cfg["skip_layers"])
         assert len(skips) <= 1 and all(0 < s < L for s in skips), "at most one concat-skip layer, not the first"
         assert W % 64 == 0 and W <= 256, "layer_dim: a multiple of 64 up to 256"
         self.xyz_dim = xd
         self.in_xyz = xd + 2 * xd * cfg["pos_xyz_dim"]
-        self.in_dir = 3 + 6 * cfg["pos_dir_dim"]
+        self.in_dir = 3 + 6 * cfg["pos_dir_dim"] if self.sh_deg is None else 0       # (sh_deg: in_channels_dir = 0, nerf.py:105-110)
         self.KP = _ceil_to(self.in_xyz, 64)
-        self.DP = _ceil_to(self.in_dir, 8)
+        self.DP = max(_ceil_to(self.in_dir, 8), 8)          # (the direction kernel writes the 3 components whatever in_dir is)
+        self.n_color = 3 if self.sh_deg is None else 3 * (self.sh_deg + 1) ** 2
         self.n_ray_feat = self.in_dir + cfg["appearance_dim"]
         self.skip_l = skips[0] if skips else None
         M, H2 = W, W // 2
@@ -58,7 +83,7 @@ class DenseNeRF(SwitchNeRF):
             else:
                 spec += [(f"enc{i}.w", (self.KP if i == 0 else W, W)), (f"enc{i}.b", (W,))]
         spec += [("l1.w", (M, M)), ("l1.b", (M,)), ("l2h.w", (M, H2)), ("l2r.w", (self.n_ray_feat, H2)), ("l2.b", (H2,)),
-                 ("sigma.w", (M,)), ("sigma.b", (1,)), ("color.w", (3, H2)), ("color.b", (3,)),
+                 ("sigma.w", (M,)), ("sigma.b", (1,)), ("color.w", (self.n_color, H2)), ("color.b", (self.n_color,)),
                  ("emb", (cfg["appearance_count"], cfg["appearance_dim"]))]
         s = self.skip_l
         self._chain_weights = [f"enc{i}" for i in range(L) if i != s] + ([f"enc{s}p", f"enc{s}h"] if s is not None else []) + ["l1", "l2h"]
@@ -80,7 +105,7 @@ class DenseNeRF(SwitchNeRF):
         sd["xyz_encoding_final.weight"], sd["xyz_encoding_final.bias"] = lin(W, W)
         sd["dir_a_encoding.0.weight"], sd["dir_a_encoding.0.bias"] = lin(self.H2, W + self.n_ray_feat)
         sd["sigma.weight"], sd["sigma.bias"] = lin(1, W)
-        sd["rgb.weight"], sd["rgb.bias"] = lin(3, self.H2)
+        sd["rgb.weight"], sd["rgb.bias"] = lin(self.n_color, self.H2)
         sd["embedding_a.weight"] = torch.randn(cfg["appearance_count"], cfg["appearance_dim"], generator=g)
         self.load_state_dict(sd)
 
@@ -115,6 +140,9 @@ class DenseNeRF(SwitchNeRF):
             p["l2.b"].copy_(t("dir_a_encoding.0.bias"))
             p["sigma.w"].copy_(t("sigma.weight").view(-1))
             p["sigma.b"].copy_(t("sigma.bias"))
+            if tuple(t("rgb.weight").shape) != (self.n_color, self.H2):
+                raise ValueError(f"rgb.weight {tuple(t('rgb.weight').shape)}: this model's colour head is [{self.n_color}, {self.H2}] "
+                                 f"(sh_deg = {self.sh_deg})")
             p["color.w"].copy_(t("rgb.weight"))
             p["color.b"].copy_(t("rgb.bias"))
             p["emb"].copy_(t("embedding_a.weight"))
@@ -149,6 +177,15 @@ class DenseNeRF(SwitchNeRF):
         raise NotImplementedError("the dense NeRF has no experts to shard")
 
     # ------------------------------------------------------------------------------------------ forward
+    _sh_dirs = None          # sh_deg: the fp32 directions rays[:, 3:6] of the pass being run (forward_rays -> _net_forward)
+
+    def forward_rays(self, rays, *args, **kw):
+        if self.sh_deg is not None:
+            if self._noise_scene is not None or self.xyz_dim != 3:
+                raise NotImplementedError("sh_deg: a background model / a scene with one is not built with spherical-harmonics colour")
+            self._sh_dirs = rays[:, 3:6].contiguous()
+        return super().forward_rays(rays, *args, **kw)
+
     def _net_forward(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag):
         """NeRF.forward (nerf.py:143-190) over the N*S points whose encodings are in `pe` -> c["raw"] [N*S, 4]."""
         o, dt = ops, self.dtype
@@ -156,6 +193,12 @@ class DenseNeRF(SwitchNeRF):
         W, L, H2, s = self.M, self.L, self.H2, self.skip_l
         c = dict(N=N, S=S, P=P, n_seg=max(1, P // seg_tokens), seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
         c["pe"], c["pe_dir"] = pe, pe_dir
+        if self.sh_deg is not None:
+            d = self._sh_dirs
+            if d is None or d.shape != (N, 3) or d.dtype != torch.float32:
+                raise NotImplementedError("sh_deg: the directions of this pass are missing - only forward_rays / forward_hier / __call__ "
+                                          "run a spherical-harmonics model (no background scene, no mip path)")
+            c["sh_dirs"] = d
         c["acts"] = [self._cbuf(c, f"act{i}", (P, W), dt) for i in range(L)]          # post-ReLU outputs; acts[L-1] = xyz_ (c["y"])
         mw = o.chain_mask_words(dt, 1, P, max(W, self.KP))
         c["masks"] = [self._cbuf(c, f"mask{i}", (mw,), torch.int32) for i in range(L)]
@@ -188,8 +231,12 @@ class DenseNeRF(SwitchNeRF):
         S, P = c["S"], c["P"]
         W, L, H2, s = self.M, self.L, self.H2, self.skip_l
         g, acts, masks = self.g, c["acts"], c["masks"]
-        dh2, dsig, dc_ray = o.heads_bwd(c["y"], c["h2"], self.p["color.w"], c["raw"], d_raw, g["sigma.w"], g["sigma.b"], g["color.w"],
-                                        g["color.b"], rows_per_group=S)
+        if self.sh_deg is not None:
+            dh2, dsig, dc_ray = o.heads_sh_bwd(c["y"], c["h2"], self.p["color.w"], self.p["color.b"], c["sh_dirs"], c["raw"], d_raw,
+                                               g["sigma.w"], g["sigma.b"], g["color.w"], g["color.b"], S, self.sh_deg)
+        else:
+            dh2, dsig, dc_ray = o.heads_bwd(c["y"], c["h2"], self.p["color.w"], c["raw"], d_raw, g["sigma.w"], g["sigma.b"], g["color.w"],
+                                            g["color.b"], rows_per_group=S)
         self._ray_level_grads(c, dc_ray)
         dh1 = self._cbuf(c, "dh1", (P, W), dt)
         nsp = max(1, min(256, P // 1024))
@@ -233,6 +280,8 @@ class DenseNeRF(SwitchNeRF):
         inverted-sphere points): the points are encoded here on the host (BackgroundScene encodes them inside
         swn_bg_sample_pe instead)."""
         xd = self.xyz_dim
+        if self.sh_deg is not None:
+            return self._call_sh(x, sigma_only, sigma_noise)
         expected = xd if sigma_only else xd + 4
         if x.shape[1] != expected:
             raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(x.shape, expected, xd))
@@ -260,3 +309,24 @@ class DenseNeRF(SwitchNeRF):
             finally:
                 self._saving = True
         return c["raw"][:, 3:4] if sigma_only else c["raw"]
+
+    _sh_want_coef = False    # inside _call_sh: the heads' launch also leaves the colour head's linear outputs (c["coef"])
+
+    def _call_sh(self, x, sigma_only, sigma_noise):
+        """The sh_deg form of NeRF.forward (nerf.py:147-149, :191): x [P, xyz_dim + 1] = position, image index (no direction columns) ->
+        [P, 3 B + 1] = the raw coefficients (row-major [3, B] per point, no activation), then sigma; sigma_only: x [P, xyz_dim] -> [P, 1]."""
+        xd = self.xyz_dim
+        expected = xd if sigma_only else xd + 1
+        if x.shape[1] != expected:
+            raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(x.shape, expected, xd))
+        P = x.shape[0]
+        xf = x.to(torch.float32)
+        img = torch.zeros(P, dtype=torch.long, device=self.dev) if sigma_only else xf[:, xd].long().contiguous()
+        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
+        rays = torch.cat([xf[:, :3], torch.zeros(P, 5, device=self.dev)], 1).contiguous()      # o = xyz, d = 0, z = 0 -> sample = xyz
+        self._sh_want_coef = True
+        try:
+            c = self.forward_rays(rays, img, 1, P, 0.0, None, noise, training=self.training, composite=False)
+        finally:
+            self._sh_want_coef = False
+        return c["raw"][:, 3:4] if sigma_only else torch.cat([c["coef"], c["raw"][:, 3:4]], 1)

@@ -14,6 +14,12 @@ import torch
 MAX_CACHED_GRAPHS = 8
 
 
+def _refuse_sh(model, who: str):
+    """Graph capture of a spherical-harmonics model is not built (its per-pass directions are handed over on the host side)."""
+    if getattr(model, "sh_deg", None) is not None:
+        raise NotImplementedError(f"{who}: graph capture of an sh_deg model is not built; run it eagerly")
+
+
 def cached_graph(cache: dict, key, make):
     """cache[key], created with make() on a miss; the cache holds at most MAX_CACHED_GRAPHS captured graphs (least recently used one
     dropped: a graph owns a private memory pool with every activation of its batch shape).  Dropping a graph is safe - the buffers a
@@ -44,6 +50,7 @@ class GraphedTrainStep:
 
     def __init__(self, model, rgbs, rays, image_indices, n_samples: int, seg_tokens: int, perturb: float = 1.0, noise_std: float = 1.0,
                  routing_override=None, warmup: int = 2, split_backward=None):
+        _refuse_sh(model, "GraphedTrainStep")
         N, S = rays.shape[0], int(n_samples)
         if model.ep is not None:
             seg_payload = model.E * model.capacity(min(int(seg_tokens), N * S)) * model.M * (4 if model.dtype == torch.float32 else 2)
@@ -133,6 +140,7 @@ class GraphedRender:
 
     def __init__(self, model, rays, image_indices, n_samples: int, seg_tokens: int, fine_samples: int = 0, no_batch: bool = False,
                  warmup: int = 2):
+        _refuse_sh(model, "GraphedRender")
         if model.ep is not None and not model.ep.local:
             raise ValueError("GraphedRender: expert-parallel evaluation exchanges host-sized splits and cannot be captured")
         self.model = model
@@ -191,6 +199,7 @@ class GraphedRenderTrain:
 
     def __init__(self, model, rays, image_indices, n_samples: int, fine_samples: int, seg_tokens: int, perturb: float, noise_std: float,
                  warmup: int = 2):
+        _refuse_sh(model, "GraphedRenderTrain")
         if model.ep is not None and not model.ep.local:
             raise ValueError("GraphedRenderTrain: expert-parallel training is not captured")
         from . import ops

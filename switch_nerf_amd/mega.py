@@ -47,7 +47,9 @@ def dense_cfg_from_state_dict(sd, xyz_dim: int) -> dict:
     if "affine.weight" in sd:
         raise NotImplementedError("affine_appearance sub-models are not built on the dense path")
     if shape("rgb.weight")[0] != 3:
-        raise NotImplementedError("spherical-harmonics colour (sh_deg) is outside the Mega-NeRF path")
+        raise NotImplementedError("spherical-harmonics colour (sh_deg) sub-models are outside the Mega-NeRF path: with boundary_margin > 1 "
+                                  "the reference blends the coefficients of the cells before the sigmoid, which swn_cells_blend's "
+                                  "4-channel rows do not carry (DenseNeRF alone runs sh_deg)")
     in_dir = shape("dir_a_encoding.0.weight")[1] - W - app
     if in_dir < 3 or (in_dir - 3) % 6:
         raise ValueError(f"dir_a_encoding of {shape('dir_a_encoding.0.weight')[1]} inputs does not split into {W} + PE(dir) + {app}")

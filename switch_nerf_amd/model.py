@@ -128,8 +128,8 @@ class SwitchNeRF:
         self.gate_noise, self.gate_noise_draw = float(gate_noise), None
         self.base_lr = lr             # undecayed rate ('initial_lr' of the reference's ExponentialLR); self.lr = the current rate
         spec = self._configure(cfg)
-        if self.affine:               # the colour transform runs in the heads' own launches (swn_heads_affine_*), behind the unfused tail
-            self.sw.update(fused_heads=False, fused_tail=False, fused_tail_bwd=False)
+        if self.affine or self.sh_deg is not None:      # the colour transform / the spherical-harmonics contraction runs in the heads' own
+            self.sw.update(fused_heads=False, fused_tail=False, fused_tail_bwd=False)      # launches (swn_heads_affine_*, swn_heads_sh_*), behind the unfused tail
         self.spec, off = {}, 0
         self.n_dense = None           # elements of the flat buffer before the first expert parameter (all of it for dense models)
         for i, (name, shape) in enumerate(spec):
@@ -163,6 +163,9 @@ class SwitchNeRF:
     def _configure(self, cfg):
         """Sets the network dimensions and returns the flat parameter layout [(name, shape)]; Linear weights are [in, out]."""
         assert tuple(cfg["skips"]) == (3,) or len(cfg["skips"]) <= 1, "one skip connection supported"
+        if cfg.get("sh_deg") is not None:
+            raise NotImplementedError("sh_deg: spherical-harmonics colour is the dense NeRF's (DenseNeRF); NeRFMoE asserts a 4-channel sigma "
+                                      "layer when pos_dir_dim == 0 (models/nerf_moe.py:186-189) and cannot carry the coefficients")
         M, E, L, G, H2 = cfg["model_dim"], cfg["num_experts"], cfg["expert_layers"], cfg["gate_hidden"], cfg["layer2_out"]
         assert G == M, "external gate width must equal model_dim (building.yaml)"
         self.hash = cfg.get("hash")                  # multiresolution hash-grid input encoding (ops.hash_encode_fwd) or None
@@ -398,6 +401,9 @@ class SwitchNeRF:
             if self.affine and k in ("fused_heads", "fused_tail", "fused_tail_bwd") and v:
                 raise ValueError(f"kernel switch {k!r}: an affine_appearance model runs the heads as their own launches (the fused tail "
                                  "does not apply the colour transform)")
+            if self.sh_deg is not None and k in ("fused_heads", "fused_tail", "fused_tail_bwd") and v:
+                raise ValueError(f"kernel switch {k!r}: an sh_deg model runs the heads as their own launches (the fused tail keeps its "
+                                 "3-row colour head)")
             prev[k] = self.sw[k]
             self.sw[k] = type(self.sw[k])(v)
         if "overlap" in kw:
@@ -500,6 +506,7 @@ class SwitchNeRF:
 
     # ------------------------------------------------------------------------------------------ buffers
     affine = False          # cfg["affine_appearance"]: the per-image affine colour transform (set by _configure)
+    sh_deg = None           # cfg["sh_deg"]: spherical-harmonics colour of that degree (DenseNeRF only; set by its _configure)
     _saving = True          # False inside an inference forward: the chains skip the activation saves and ReLU masks
     hash = None             # multiresolution hash-grid input encoding (cfg["hash"]) or None
     _grow_bufs = False      # True: one buffer per name, grown to the largest row count seen (row counts that vary per step)
@@ -1041,6 +1048,10 @@ class SwitchNeRF:
         if self.affine:    # ---- heads + the per-image colour transform (models/nerf_moe.py:436-438) as their own launch
             c["raw"] = o.heads_affine_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                           sigma_noise, *c["aff_rows"])
+        elif self.sh_deg is not None:      # ---- heads + the spherical-harmonics contraction against the ray's direction (rendering.py:344-347)
+            out = o.heads_sh_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
+                                 sigma_noise, c["sh_dirs"], rows_per_bias, self.sh_deg, want_coef=self._sh_want_coef)
+            c["raw"], c["coef"] = out if self._sh_want_coef else (out, None)
         elif not fused:    # ---- heads as their own launch (SWN_NO_FUSED_HEADS=1: rounds 1-2)
             c["raw"] = o.heads_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                    sigma_noise)

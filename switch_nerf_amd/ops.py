@@ -722,6 +722,47 @@ def heads_affine_bwd(y, h2, w_color, b_color, T, raw, d_raw, d_w_sigma, d_b_sigm
     return dh2, dsig, cs, dT
 
 
+def _sh_check(w_color, b_color, dirs, P: int, H2: int, rows_per_group: int, deg: int):
+    B = (int(deg) + 1) ** 2
+    assert 0 <= int(deg) <= 4, f"sh_deg {deg} outside 0..4"
+    assert rows_per_group > 0 and P % rows_per_group == 0
+    assert w_color.shape == (3 * B, H2) and b_color.numel() == 3 * B and dirs.shape == (P // rows_per_group, 3)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (w_color, b_color, dirs))
+    return B
+
+
+def heads_sh_fwd(y, h2, w_sigma, b_sigma, w_color, b_color, sigma_noise, dirs, rows_per_group: int, deg: int, want_coef: bool = False):
+    """heads_fwd with spherical-harmonics colour (swn_heads_sh_fwd): w_color [3 B, H2], b_color [3 B], B = (deg + 1)^2, dirs
+    [P / rows_per_group, 3] f32 (not normalised) -> raw [P, 4] f32, or (raw, coef [P, 3 B] f32 = the colour head's linear outputs)."""
+    P, M = y.shape
+    H2 = h2.shape[1]
+    B = _sh_check(w_color, b_color, dirs, P, H2, rows_per_group, deg)
+    raw = torch.empty(P, 4, dtype=torch.float32, device=y.device)
+    coef = torch.empty(P, 3 * B, dtype=torch.float32, device=y.device) if want_coef else None
+    call("swn_heads_sh_fwd", _p(y), _p(h2), _dt(y), _p(w_sigma), _p(b_sigma), _p(w_color), _p(b_color), _p(sigma_noise), _p(dirs),
+         int(rows_per_group), int(deg), P, M, H2, _p(raw), _p(coef), _stream())
+    return (raw, coef) if want_coef else raw
+
+
+def heads_sh_bwd(y, h2, w_color, b_color, dirs, raw, d_raw, d_w_sigma, d_b_sigma, d_w_color, d_b_color, rows_per_group: int, deg: int,
+                 want_colsum: bool = True):
+    """heads_bwd with spherical-harmonics colour (swn_heads_sh_bwd) -> (dh2, dsig, colsum [P / rows_per_group, H2] f32 or None); the four
+    parameter gradients are accumulated (d_w_color [3 B, H2], d_b_color [3 B]).  The direction gets no gradient."""
+    P, H2 = h2.shape
+    M = d_w_sigma.numel()
+    B = _sh_check(w_color, b_color, dirs, P, H2, rows_per_group, deg)
+    assert d_w_color.numel() == 3 * B * H2 and d_b_color.numel() == 3 * B and y is not None
+    dh2 = torch.empty_like(h2)
+    dsig = torch.empty(P, dtype=torch.float32, device=h2.device)
+    nb = C.c_size_t(0)
+    call("swn_heads_sh_bwd_workspace_bytes", P, M, H2, int(rows_per_group), int(deg), C.byref(nb))
+    ws = torch.empty(max(int(nb.value), 4) // 4, dtype=torch.float32, device=h2.device)
+    cs = torch.empty(P // rows_per_group, H2, dtype=torch.float32, device=h2.device) if want_colsum else None
+    call("swn_heads_sh_bwd", _p(y), _p(h2), _dt(h2), _p(w_color), _p(b_color), _p(dirs), _p(raw), _p(d_raw), P, M, H2, int(rows_per_group),
+         int(deg), _p(dh2), _p(dsig), _p(d_w_sigma), _p(d_b_sigma), _p(d_w_color), _p(d_b_color), _p(cs), _p(ws), int(nb.value), _stream())
+    return dh2, dsig, cs
+
+
 def step_loss(rgb, target, l_aux_a, l_aux_b, wt: float, loss_scale_dev=None):
     """-> (out4 = [photo, gate_loss, loss, psnr] on the device, d_rgb, d_l_aux_a, d_l_aux_b or None)."""
     dev = rgb.device

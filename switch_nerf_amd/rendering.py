@@ -90,6 +90,20 @@ def _check_affine(nerf, hparams):
                                   "build the model from a cfg with the same switch")
 
 
+def _check_sh(nerf, bg_nerf, hparams):
+    """hparams.sh_deg (opts.py:69) must say what the model was built with (cfg["sh_deg"]), the rule of _check_affine.  Only the dense
+    NeRF carries the coefficients: NeRFMoE asserts a 4-channel sigma layer when pos_dir_dim == 0 (models/nerf_moe.py:186-189)."""
+    want, have = getattr(hparams, "sh_deg", None), getattr(nerf, "sh_deg", None)
+    if want is not None and not hasattr(nerf, "n_color"):
+        raise NotImplementedError(f"hparams.sh_deg = {want}: spherical-harmonics colour is the dense NeRF's; NeRFMoE asserts a 4-channel "
+                                  "sigma layer when pos_dir_dim == 0 (models/nerf_moe.py:186-189), so a SwitchNeRF cannot carry it")
+    if want != have:
+        raise NotImplementedError(f"hparams.sh_deg = {want} but the model was built with sh_deg = {have}: build the model from a cfg "
+                                  "with the same sh_deg")
+    if (have is not None and bg_nerf is not None) or getattr(bg_nerf, "sh_deg", None) is not None:
+        raise NotImplementedError("sh_deg: a background model (bg_nerf) with spherical-harmonics colour is not built")
+
+
 def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch.Tensor], hparams, sphere_center=None,
                 sphere_radius=None, get_depth: bool = True, get_depth_variance: bool = True,
                 get_bg_fg_rgb: bool = False) -> Tuple[Dict[str, torch.Tensor], bool]:
@@ -100,6 +114,7 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
         return mega.render_rays(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, sphere_radius, get_depth,
                                 get_depth_variance, get_bg_fg_rgb)
     _check_affine(nerf, hparams)
+    _check_sh(nerf, bg_nerf, hparams)
     F = int(getattr(hparams, "fine_samples", 0))
     N = rays.shape[0]
     S = hparams.coarse_samples
