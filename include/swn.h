@@ -845,6 +845,16 @@ int swn_cells_gather(const float* x, int stride, int col0, const int32_t* rows, 
  *   the sum order is the reference's loop order.                                                                                   */
 int swn_cells_blend(const float* weights, const int32_t* slot, const int32_t* begin, const float* sub_out, long total, int n_points,
                     int n_cells, int channels, int hard, float* out, void* stream);
+/* swn_cells_blend_sh (sh.hip): swn_cells_blend for sub-models with spherical-harmonics colour, fused with rendering.py:344-347.  sub_out
+ *   [total, 3 B + 1] fp32, B = (deg + 1)^2: a row is the coefficients row-major [3, B], then sigma (what DenseNeRF's sh_deg call
+ *   returns).  coef[p][:] = sum over the member cells i, ascending, of weights[p][i] * sub_out[begin[i] + slot[p][i]][:]  (hard != 0:
+ *   the one member's row, copied);  raw[p] = (sigmoid(sum_b Y_b(dirs[p / rows_per_group]) coef[p][c B + b]) c < 3, coef[p][3 B]).
+ *   dirs [n_points / rows_per_group, 3] fp32, used as given (not normalised); the basis is swn_heads_sh_fwd's.  coef_out (may be NULL):
+ *   the blended rows [n_points, 3 B + 1]; raw is the same bits with and without it.  deg >= 1: a point's channels lie over 16 lanes, so
+ *   a member row is read as consecutive runs, and the basis is computed once per ray of a workgroup's 64 points; deg 0: one thread per
+ *   point.  No atomics, fixed summation order.  Errors: n_cells > 64, deg outside 0..4, rows_per_group < 1, n_points no multiple of it. */
+int swn_cells_blend_sh(const float* weights, const int32_t* slot, const int32_t* begin, const float* sub_out, long total, const float* dirs,
+                       int rows_per_group, int deg, int n_points, int n_cells, int hard, float* raw, float* coef_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -346,6 +346,136 @@ __global__ __launch_bounds__(256) void sh_wgrad_kernel(const float* __restrict__
   }
 }
 
+// ---- swn_cells_blend_sh: the Mega-NeRF blend (mega_nerf.py:34-49) of rows of 3 B coefficients + sigma, then sigmoid(eval_sh) ----------
+// A member row is up to 76 floats, so a point's channels lie over the 16 lanes of a group (channel j + 16 v in lane j): the group reads
+// a member row as consecutive 64-byte runs, and the four groups of a wave take four consecutive points.  The slots and weights of 16
+// cells are read once by the group (lane j: cell c0 + j); a ballot gives the members, walked in ascending order with the values handed
+// round by shuffles.  A workgroup takes BSH_TILE consecutive points; the basis of every ray among them is computed once, by one thread
+// each, into LDS.  The blended row goes through LDS to meet the basis: lane 4 c + q adds the terms b = q, q + 4, .. of colour c, the four
+// partial sums are joined as (q0 + q1) + (q2 + q3).  Plain loads and stores, no atomics, every sum in a fixed order.
+constexpr int BSH_MAX_CELLS = 64;
+constexpr int BSH_TILE = 64;         // points per workgroup: 16 groups x 4 passes
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+template <int DEG>
+__global__ __launch_bounds__(256) void cells_blend_sh_kernel(const float* __restrict__ weights, const int32_t* __restrict__ slot,
+                                                            const int32_t* __restrict__ begin, const float* __restrict__ sub_out, long total,
+                                                            const float* __restrict__ dirs, int rows_per_group, int K, int hard, long P,
+                                                            float* __restrict__ raw, float* __restrict__ coef_out) {
+#pragma clang fp contract(off)
+  constexpr int B = (DEG + 1) * (DEG + 1), WD = 3 * B + 1, VPL = (WD + 15) / 16;
+  __shared__ float ys[BSH_TILE][SH_MAXB];
+  __shared__ float row[16][VPL * 16];
+  const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const long p0 = (long)blockIdx.x * BSH_TILE;
+  const long p_end = p0 + BSH_TILE < P ? p0 + BSH_TILE : P;
+  const long ray0 = p0 / rows_per_group;
+  const int n_dirs = (int)((p_end - 1) / rows_per_group - ray0) + 1;      // <= BSH_TILE
+  if ((int)threadIdx.x < n_dirs) {
+    const float* d = dirs + (ray0 + threadIdx.x) * 3;
+    float Y[SH_MAXB];
+    sh_basis(DEG, d[0], d[1], d[2], Y);
+#pragma unroll
+    for (int b = 0; b < B; ++b) ys[threadIdx.x][b] = Y[b];
+  }
+  __syncthreads();
+  for (int q = 0; q < BSH_TILE / 16; ++q) {      // (the same trip count for every thread: ballots, shuffles and barriers inside)
+    const long p = p0 + q * 16 + grp;
+    const bool valid = p < P;
+    float acc[VPL];
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) acc[v] = 0.f;
+    for (int c0 = 0; c0 < K; c0 += 16) {
+      const int i = c0 + j;
+      int s = -1;
+      float wt = 0.f;
+      if (valid && i < K) {
+        s = slot[p * K + i];
+        wt = weights[p * K + i];
+      }
+      unsigned bits = (unsigned)((__ballot(s >= 0) >> (threadIdx.x & 48)) & 0xFFFFull);      // this group's members among the 16 cells
+      while (bits) {                              // ascending cell order (:34); the lanes of a group walk it together
+        const int b = __ffs(bits) - 1;
+        bits &= bits - 1;
+        const int si = __shfl(s, b, 16);
+        const float wi = __shfl(wt, b, 16);
+        const long r = (long)begin[c0 + b] + si;
+        if (r < 0 || r >= total) continue;        // (never for a slot list of swn_cells_pack)
+        const float* src = sub_out + r * WD;
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) {
+          const int ch = j + 16 * v;
+          if (ch < WD) {
+            const float val = src[ch];
+            if (hard) {                           // results[cluster_mask] = sub_result (:47)
+              acc[v] = val;
+            } else {                              // results[cluster_mask] += sub_result * weights[cluster_mask, i] (:49)
+              const float prod = val * wi;
+              acc[v] = acc[v] + prod;
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const int ch = j + 16 * v;
+      row[grp][ch] = acc[v];
+      if (valid && coef_out && ch < WD) coef_out[p * WD + ch] = acc[v];
+    }
+    __syncthreads();
+    const int c = j >> 2, part = j & 3;
+    float sres = 0.f;
+    if (valid && c < 3) {
+      const float* Y = ys[(int)(p / rows_per_group - ray0)];
+      for (int b = part; b < B; b += 4) sres = fmaf(Y[b], row[grp][c * B + b], sres);
+    }
+    sres = sres + __shfl_xor(sres, 1, 16);
+    sres = sres + __shfl_xor(sres, 2, 16);
+    const float s1 = __shfl(sres, 4, 16), s2 = __shfl(sres, 8, 16);
+    if (valid && j == 0) *(float4*)(raw + p * 4) = make_float4(sigmoidf_(sres), sigmoidf_(s1), sigmoidf_(s2), row[grp][3 * B]);
+    __syncthreads();                              // (the next pass overwrites row)
+  }
+}
+
+// Degree 0: a row is four floats, one thread per point like cells_blend_kernel<4>; the same blend, then the same evaluation with B = 1.
+__global__ __launch_bounds__(256) void cells_blend_sh0_kernel(const float* __restrict__ weights, const int32_t* __restrict__ slot,
+                                                             const int32_t* __restrict__ begin, const float* __restrict__ sub_out, long total,
+                                                             const float* __restrict__ dirs, int rows_per_group, int K, int hard, long P,
+                                                             float* __restrict__ raw, float* __restrict__ coef_out) {
+#pragma clang fp contract(off)
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < K; ++i) {
+    const int s = slot[p * K + i];
+    if (s < 0) continue;
+    const long r = (long)begin[i] + s;
+    if (r < 0 || r >= total) continue;
+    const float4 qv = *reinterpret_cast<const float4*>(sub_out + r * 4);
+    const float v[4] = {qv.x, qv.y, qv.z, qv.w};
+    if (hard) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = v[c];
+    } else {
+      const float wt = weights[p * K + i];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float prod = v[c] * wt;
+        acc[c] = acc[c] + prod;
+      }
+    }
+  }
+  if (coef_out) *reinterpret_cast<float4*>(coef_out + p * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  const float* d = dirs + (p / rows_per_group) * 3;
+  float Y[SH_MAXB];
+  sh_basis(0, d[0], d[1], d[2], Y);
+  // (the partial sums of the wide kernel that have no term are + 0: the same bits)
+  *reinterpret_cast<float4*>(raw + p * 4) = make_float4(sigmoidf_(fmaf(Y[0], acc[0], 0.f)), sigmoidf_(fmaf(Y[0], acc[1], 0.f)),
+                                                        sigmoidf_(fmaf(Y[0], acc[2], 0.f)), acc[3]);
+}
+
 static int sh_blocks(long n_units) { return n_units > 2048 ? 2048 : (n_units < 1 ? 1 : (int)n_units); }
 
 // the three parts of the backward's workspace, each a multiple of 64 floats
@@ -438,6 +568,34 @@ extern "C" int swn_heads_sh_bwd(const void* y, const void* h2, int dtype, const 
   hipLaunchKernelGGL(sh_wgrad_kernel, dim3(nb2), dim3(256), 0, as_stream(stream), ray_acc, dirs, n_units, deg, h2_dim, p_wg);
   OrdDst oc{{d_w_color, d_b_color, nullptr, nullptr}, {3 * B * h2_dim, 3 * B, 0, 0}};
   ordered_reduce_async(p_wg, nb2, 3 * B * h2_dim + 3 * B, oc, true, as_stream(stream));
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cells_blend_sh(const float* weights, const int32_t* slot, const int32_t* begin, const float* sub_out, long total,
+                                  const float* dirs, int rows_per_group, int deg, int n_points, int n_cells, int hard, float* raw,
+                                  float* coef_out, void* stream) {
+  SWN_CHECK(n_cells >= 1 && n_cells <= BSH_MAX_CELLS, "swn_cells_blend_sh: n_cells %d outside [1, %d]", n_cells, BSH_MAX_CELLS);
+  SWN_CHECK(deg >= 0 && deg <= 4, "swn_cells_blend_sh: deg %d outside 0..4", deg);
+  SWN_CHECK(rows_per_group >= 1, "swn_cells_blend_sh: rows_per_group %d < 1", rows_per_group);
+  SWN_CHECK(n_points >= 1 && total >= 1, "swn_cells_blend_sh: bad sizes (n_points %d, total %ld)", n_points, total);
+  SWN_CHECK(n_points % rows_per_group == 0, "swn_cells_blend_sh: n_points %d is no multiple of rows_per_group %d", n_points, rows_per_group);
+  SWN_CHECK(weights && slot && begin && sub_out && dirs && raw, "swn_cells_blend_sh: null pointer");      // (coef_out may be NULL)
+  SWN_CHECK(((((uintptr_t)raw) | (deg == 0 ? ((uintptr_t)sub_out) | ((uintptr_t)coef_out) : 0)) & 15) == 0,
+            "swn_cells_blend_sh: raw (deg 0: sub_out and coef_out too) must be 16-byte aligned");
+#define SWN_BSH(D_) hipLaunchKernelGGL(cells_blend_sh_kernel<D_>, dim3(cdiv(n_points, BSH_TILE)), dim3(256), 0, as_stream(stream), weights, \
+                                       slot, begin, sub_out, total, dirs, rows_per_group, n_cells, hard, (long)n_points, raw, coef_out)
+  switch (deg) {
+    case 0:
+      hipLaunchKernelGGL(cells_blend_sh0_kernel, dim3(cdiv(n_points, 256)), dim3(256), 0, as_stream(stream), weights, slot, begin, sub_out,
+                         total, dirs, rows_per_group, n_cells, hard, (long)n_points, raw, coef_out);
+      break;
+    case 1: SWN_BSH(1); break;
+    case 2: SWN_BSH(2); break;
+    case 3: SWN_BSH(3); break;
+    default: SWN_BSH(4); break;
+  }
+#undef SWN_BSH
   SWN_LAUNCH_CHECK();
   return 0;
 }

@@ -296,12 +296,7 @@ class DenseNeRF(SwitchNeRF):
             rays = torch.cat([xf[:, :6], torch.zeros(P, 2, device=self.dev)], 1).contiguous()
             c = self.forward_rays(rays, img, 1, P, 0.0, None, noise, training=self.training, composite=False)
         else:
-            pts = xf[:, :xd]
-            f = 2.0 ** torch.arange(self.cfg["pos_xyz_dim"], device=self.dev, dtype=torch.float32)
-            ang = pts[:, None, :] * f[:, None]                                             # [P, L, xd]
-            enc = torch.cat([pts, torch.stack([torch.sin(ang), torch.cos(ang)], 2).reshape(P, -1)], 1)   # nerf.py:21-26 order
-            pe = torch.zeros(P, self.KP, dtype=self.dtype, device=self.dev)
-            pe[:, : self.in_xyz] = enc.to(self.dtype)
+            pe = self._pe_points(xf[:, :xd])
             rays = torch.cat([torch.zeros(P, 3, device=self.dev), xf[:, xd:xd + 3], torch.zeros(P, 2, device=self.dev)], 1).contiguous()
             self._saving = bool(self.training)
             try:
@@ -309,6 +304,16 @@ class DenseNeRF(SwitchNeRF):
             finally:
                 self._saving = True
         return c["raw"][:, 3:4] if sigma_only else c["raw"]
+
+    def _pe_points(self, pts):
+        """The positional encoding [P, KP] of explicit points [P, xyz_dim] (fp32), on the host."""
+        P = pts.shape[0]
+        f = 2.0 ** torch.arange(self.cfg["pos_xyz_dim"], device=self.dev, dtype=torch.float32)
+        ang = pts[:, None, :] * f[:, None]                                             # [P, L, xd]
+        enc = torch.cat([pts, torch.stack([torch.sin(ang), torch.cos(ang)], 2).reshape(P, -1)], 1)   # nerf.py:21-26 order
+        pe = torch.zeros(P, self.KP, dtype=self.dtype, device=self.dev)
+        pe[:, : self.in_xyz] = enc.to(self.dtype)
+        return pe
 
     _sh_want_coef = False    # inside _call_sh: the heads' launch also leaves the colour head's linear outputs (c["coef"])
 
@@ -323,10 +328,22 @@ class DenseNeRF(SwitchNeRF):
         xf = x.to(torch.float32)
         img = torch.zeros(P, dtype=torch.long, device=self.dev) if sigma_only else xf[:, xd].long().contiguous()
         noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
-        rays = torch.cat([xf[:, :3], torch.zeros(P, 5, device=self.dev)], 1).contiguous()      # o = xyz, d = 0, z = 0 -> sample = xyz
         self._sh_want_coef = True
         try:
-            c = self.forward_rays(rays, img, 1, P, 0.0, None, noise, training=self.training, composite=False)
+            if xd == 3:
+                rays = torch.cat([xf[:, :3], torch.zeros(P, 5, device=self.dev)], 1).contiguous()      # o = xyz, d = 0, z = 0 -> sample = xyz
+                c = self.forward_rays(rays, img, 1, P, 0.0, None, noise, training=self.training, composite=False)
+            else:       # the background half of a Mega-NeRF container: explicit inverted-sphere points, encoded like __call__ does
+                if self.training:
+                    raise NotImplementedError("sh_deg: a model with xyz_dim 4 is called on points in evaluation mode only")
+                self._sync_compute_copies()
+                rays = torch.zeros(P, 8, device=self.dev)
+                self._sh_dirs = rays[:, 3:6].contiguous()       # (the heads' own rgb is not returned: the caller evaluates the basis)
+                self._saving = False
+                try:
+                    c = self._net_forward(self._pe_points(xf[:, :xd]), self._dir_pe(rays), img, P, 1, P, noise, None, False, "c")
+                finally:
+                    self._saving = True
         finally:
             self._sh_want_coef = False
         return c["raw"][:, 3:4] if sigma_only else torch.cat([c["coef"], c["raw"][:, 3:4]], 1)

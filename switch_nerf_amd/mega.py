@@ -12,6 +12,10 @@ Structurally a second kind of gate - geometric, multi-membership, no parameters 
     sub_out[begin[i]:begin[i + 1]] = sub_modules[i](xin[...], ...)           DenseNeRF.__call__; empty cells are skipped
     out = ops.cells_blend(weights, slot, begin, sub_out, hard)               per-point gather in ascending cell order, no atomics
 
+Sub-models with spherical-harmonics colour (DenseNeRF cfg["sh_deg"], the workflow --sh_deg exists for): a cell returns [n, 3 B + 1] raw
+rows and the reference blends THOSE before rendering.py:344-347 applies sigmoid(eval_sh(...)).  ops.cells_blend_sh does the blend of the
+wide rows and the evaluation in one launch (call_rgb; render_rays), or leaves the blended rows (the module mirror, __call__).
+
 Inside a cell the rows ascend by point index - the order x[cluster_mask] has in the reference, so sigma_noise[cluster_mask] lines up.
 Inference only: joint_training (the reference's distributed-training hack), device noise and graph capture are not built.
 render_rays() below is what rendering.render_rays runs for a MegaNeRF foreground.
@@ -29,12 +33,15 @@ from .dense import DenseNeRF
 MAX_CELLS = 64      # swn_cells_*: the centroids live in LDS, a point's membership in one 64-bit mask
 
 
-def dense_cfg_from_state_dict(sd, xyz_dim: int) -> dict:
-    """The DenseNeRF configuration of a reference NeRF state_dict (models/nerf.py:75-143 key layout), read off the tensor shapes."""
+def dense_cfg_from_state_dict(sd, xyz_dim: int, allow_sh: bool = False) -> dict:
+    """The DenseNeRF configuration of a reference NeRF state_dict (models/nerf.py:75-143 key layout), read off the tensor shapes.
+    allow_sh: also recognise the spherical-harmonics layout (rgb.weight of 3 (d + 1)^2 rows, no direction block) and return
+    pos_dir_dim = 0 and sh_deg = d for it; MegaNeRF.from_state_dicts / from_container pass it.  Without it that layout raises, as it
+    did before MegaNeRF took such sub-models: a caller written for the direction layout gets no cfg with keys it does not know."""
     def shape(k):
         if k not in sd:
-            raise NotImplementedError(f"sub-model state_dict has no `{k}`: only the direction + appearance NeRF (pos_dir_dim > 0, "
-                                      "appearance_dim > 0, no affine transform) is built on the dense path")
+            raise NotImplementedError(f"sub-model state_dict has no `{k}`: only the appearance NeRF (appearance_dim > 0, no affine "
+                                      "transform; a direction block or spherical-harmonics colour) is built on the dense path")
         return tuple(sd[k].shape)
     W, in_xyz = shape("xyz_encodings.0.0.weight")
     layers = 0
@@ -46,15 +53,27 @@ def dense_cfg_from_state_dict(sd, xyz_dim: int) -> dict:
     count, app = shape("embedding_a.weight")
     if "affine.weight" in sd:
         raise NotImplementedError("affine_appearance sub-models are not built on the dense path")
-    if shape("rgb.weight")[0] != 3:
-        raise NotImplementedError("spherical-harmonics colour (sh_deg) sub-models are outside the Mega-NeRF path: with boundary_margin > 1 "
-                                  "the reference blends the coefficients of the cells before the sigmoid, which swn_cells_blend's "
-                                  "4-channel rows do not carry (DenseNeRF alone runs sh_deg)")
-    in_dir = shape("dir_a_encoding.0.weight")[1] - W - app
+    n_rgb, in2 = shape("rgb.weight")[0], shape("dir_a_encoding.0.weight")[1]
+    common = dict(layer_dim=W, layers=layers, skip_layers=skips, pos_xyz_dim=(in_xyz // xyz_dim - 1) // 2)
+    if n_rgb != 3 and not allow_sh:
+        raise NotImplementedError(f"rgb.weight of {n_rgb} rows: a spherical-harmonics colour (sh_deg) sub-model - pass allow_sh=True to "
+                                  "read its degree off the state dict (the cfg then carries sh_deg and pos_dir_dim = 0), as "
+                                  "MegaNeRF.from_state_dicts / from_container do")
+    if allow_sh and (n_rgb != 3 or in2 == W + app):
+        # spherical-harmonics colour (models/nerf.py:82-83, :137-143): 3 B rows, B = (d + 1)^2, and no direction block in front of the
+        # appearance embedding (a 3-row head without one is degree 0)
+        B = n_rgb // 3
+        d = int(round(B ** 0.5)) - 1
+        if n_rgb % 3 or (d + 1) ** 2 != B or not 0 <= d <= 4:
+            raise ValueError(f"rgb.weight of {n_rgb} rows is no 3 (d + 1)^2 with d in 0..4: not a spherical-harmonics colour head")
+        if in2 != W + app:
+            raise ValueError(f"rgb.weight of {n_rgb} rows (sh_deg {d}) but dir_a_encoding of {in2} inputs is not {W} + {app}: a "
+                             "spherical-harmonics model has no direction block (pos_dir_dim == 0)")
+        return dict(common, pos_dir_dim=0, appearance_dim=app, appearance_count=count, xyz_dim=xyz_dim, sh_deg=d)
+    in_dir = in2 - W - app
     if in_dir < 3 or (in_dir - 3) % 6:
-        raise ValueError(f"dir_a_encoding of {shape('dir_a_encoding.0.weight')[1]} inputs does not split into {W} + PE(dir) + {app}")
-    return dict(layer_dim=W, layers=layers, skip_layers=skips, pos_xyz_dim=(in_xyz // xyz_dim - 1) // 2, pos_dir_dim=(in_dir - 3) // 6,
-                appearance_dim=app, appearance_count=count, xyz_dim=xyz_dim)
+        raise ValueError(f"dir_a_encoding of {in2} inputs does not split into {W} + PE(dir) + {app}")
+    return dict(common, pos_dir_dim=(in_dir - 3) // 6, appearance_dim=app, appearance_count=count, xyz_dim=xyz_dim)
 
 
 class MegaNeRF:
@@ -75,6 +94,13 @@ class MegaNeRF:
             if not isinstance(m, DenseNeRF) or m.xyz_dim != xd:
                 raise TypeError(f"sub-models must be DenseNeRF with xyz_dim {xd} (xyz_real = {bool(xyz_real)})")
             m.eval()
+        degs = [m.sh_deg for m in sub_modules]
+        if any(d != degs[0] for d in degs):      # one row width for every cell: the blend adds the cells' raw rows (mega_nerf.py:43-49)
+            if any(d is None for d in degs):
+                raise ValueError(f"sub-models mix spherical-harmonics colour and plain colour heads (sh_deg per cell: {degs})")
+            raise ValueError(f"sub-models of different spherical-harmonics degrees (sh_deg per cell: {degs})")
+        self.sh_deg = degs[0]                                    # None, or the degree of every cell (rendering._check_sh's rule)
+        self.n_out = 4 if self.sh_deg is None else 3 * (self.sh_deg + 1) ** 2 + 1
         self.sub_modules = sub_modules
         self.dev, self.dtype = sub_modules[0].dev, sub_modules[0].dtype
         self.centroids = cen.detach().to(torch.float32).to(self.dev).contiguous()
@@ -95,7 +121,7 @@ class MegaNeRF:
         xd = 4 if xyz_real else 3
         subs = []
         for sd in state_dicts:
-            c = dict(cfg, xyz_dim=xd) if cfg is not None else dense_cfg_from_state_dict(sd, xd)
+            c = dict(cfg, xyz_dim=xd) if cfg is not None else dense_cfg_from_state_dict(sd, xd, allow_sh=True)
             m = DenseNeRF(c, dtype=dtype, device=device)
             m.load_state_dict(sd)
             subs.append(m)
@@ -133,17 +159,46 @@ class MegaNeRF:
 
     def __call__(self, x, sigma_only: bool = False, sigma_noise=None):
         """MegaNeRF.forward (mega_nerf.py:19-61): x [P, 3 + 3 + 1] (position, direction, image index; with xyz_real [P, 3 + 4 + 3 + 1],
-        the real position in front of the inverted-sphere point) -> [P, 4]; sigma_only: x [P, 3] ([P, 3 + 4]) -> [P, 1]."""
+        the real position in front of the inverted-sphere point) -> [P, 4]; sigma_only: x [P, 3] ([P, 3 + 4]) -> [P, 1].
+        Sub-models with sh_deg: no direction columns (x [P, 3 + 1], [P, 3 + 4 + 1]; rendering.py:316-330) -> [P, 3 B + 1], the blended
+        raw rows (coefficients, sigma) that rendering.py:344-347 evaluates; call_rgb() does both in one launch."""
+        st = self._sub_outputs(x, sigma_only, sigma_noise)
+        if st is None:
+            return torch.empty(0, 1 if sigma_only else self.n_out, dtype=torch.float32, device=self.dev)
+        weights, slot, begin, sub_out, hard = st
+        if self.sh_deg is None or sigma_only:
+            return ops.cells_blend(weights, slot, begin, sub_out, hard)
+        P = x.shape[0]      # the module's own output is the blended rows: the evaluation's direction plays no part in them
+        return ops.cells_blend_sh(weights, slot, begin, sub_out, torch.zeros(P, 3, dtype=torch.float32, device=self.dev), 1, self.sh_deg,
+                                  hard, want_coef=True)[1]
+
+    def call_rgb(self, x, dirs, rows_per_group: int = 1, sigma_noise=None):
+        """Sub-models with sh_deg: x as __call__ takes it, dirs [P / rows_per_group, 3] (point p is seen along dirs[p // rows_per_group];
+        not normalised) -> [P, 4] = (sigmoid(eval_sh(blended coefficients, direction)), blended sigma): what rendering.py:344-349 makes
+        of the module's output, through swn_cells_blend_sh, the blended rows never written."""
+        if self.sh_deg is None:
+            raise NotImplementedError("call_rgb is the spherical-harmonics form (sub-models with sh_deg); __call__ returns rgb otherwise")
+        P, rpg = x.shape[0], int(rows_per_group)
+        if rpg < 1 or P % rpg or tuple(dirs.shape) != (P // max(rpg, 1), 3):
+            raise ValueError(f"call_rgb: dirs {tuple(dirs.shape)} for {P} points in groups of {rows_per_group}: expected [{P} / rows_per_group, 3]")
+        st = self._sub_outputs(x, False, sigma_noise)
+        if st is None:
+            return torch.empty(0, 4, dtype=torch.float32, device=self.dev)
+        weights, slot, begin, sub_out, hard = st
+        return ops.cells_blend_sh(weights, slot, begin, sub_out, dirs.to(torch.float32).contiguous(), rpg, self.sh_deg, hard)
+
+    def _sub_outputs(self, x, sigma_only, sigma_noise):
+        """(weights, slot, begin, sub_out [total, C], hard): the routing and every cell's packed outputs; None for no points."""
         if self.boundary_margin < 1:
             raise AssertionError("boundary_margin must be >= 1")
         col0 = 3 if self.xyz_real else 0
-        expected = col0 + self.xyz_dim + (0 if sigma_only else 4)
+        expected = col0 + self.xyz_dim + (0 if sigma_only else (4 if self.sh_deg is None else 1))
         if x.dim() != 2 or x.shape[1] != expected:
             raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(tuple(x.shape), expected, self.xyz_dim))
         P, K = x.shape[0], len(self.sub_modules)
-        Cn = 1 if sigma_only else 4
+        Cn = 1 if sigma_only else self.n_out
         if P == 0:
-            return torch.empty(0, Cn, dtype=torch.float32, device=self.dev)
+            return None
         x = x.to(torch.float32).contiguous()
         noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
         hard = self.boundary_margin == 1
@@ -159,21 +214,37 @@ class MegaNeRF:
             if n[i] > 0:                                       # (empty cells are skipped, :38)
                 sub_out[b:b + n[i]] = child(xin[b:b + n[i]], sigma_only, None if nin is None else nin[b:b + n[i]])
             b += n[i]
-        return ops.cells_blend(weights, slot, begin, sub_out, hard)
+        if self.sh_deg == 0 and not sigma_only:
+            # rgb_dim == 3: the reference's NeRF keeps its own nn.Sigmoid on the three outputs (models/nerf.py:140-141, :187-188), so
+            # at degree 0 a cell's row holds sigmoid(lin), and rendering.py:344-347 puts eval_sh and a second sigmoid on the blend.
+            # DenseNeRF's sh_deg call returns lin at every degree; the degenerate degree is squared with the reference here.
+            sub_out[:, :3] = torch.sigmoid(sub_out[:, :3])
+        return weights, slot, begin, sub_out, hard
 
 
 # ---------------------------------------------------------------------------------------------- rendering
-def _points(rays, z, image_indices):
-    """[N * S, 3 + 3 + 1]: position o + d z, direction and image index of every sample (rendering.py:357-360)."""
+def _points(rays, z, image_indices, with_dir=True):
+    """[N * S, 3 + 3 + 1]: position o + d z, direction and image index of every sample (rendering.py:357-360); with_dir False (sh_deg):
+    [N * S, 3 + 1], no direction columns (:320-323)."""
     N, S = z.shape
     pts = rays[:, None, :3] + rays[:, None, 3:6] * z[:, :, None]
     d = rays[:, None, 3:6].expand(N, S, 3)
     img = image_indices.to(torch.float32).view(N, 1, 1).expand(N, S, 1)
-    return torch.cat([pts, d, img], -1).view(N * S, 7)
+    return torch.cat([pts, d, img] if with_dir else [pts, img], -1).view(N * S, 7 if with_dir else 4)
 
 
-def _run(nerf, x, chunk):
-    return torch.cat([nerf(x[i:i + chunk]) for i in range(0, x.shape[0], chunk)], 0)
+def _run(nerf, x, chunk, dirs=None):
+    """The model over the points x [N * S, ..] (ray-major) per model chunk -> [N * S, 4].  dirs [N, 3] (sh_deg): through call_rgb, the
+    chunks cut on ray boundaries so that one direction serves the S samples of a ray (the points are independent: where the reference
+    cuts, rendering.py:320, does not reach the result); a chunk shorter than a ray takes per-point directions instead."""
+    if dirs is None:
+        return torch.cat([nerf(x[i:i + chunk]) for i in range(0, x.shape[0], chunk)], 0)
+    N, S = dirs.shape[0], x.shape[0] // dirs.shape[0]
+    if chunk >= S:
+        per = chunk // S
+        return torch.cat([nerf.call_rgb(x[r * S:(r + per) * S], dirs[r:r + per].contiguous(), S) for r in range(0, N, per)], 0)
+    d = dirs[:, None, :].expand(N, S, 3).reshape(N * S, 3)
+    return torch.cat([nerf.call_rgb(x[i:i + chunk], d[i:i + chunk].contiguous(), 1) for i in range(0, N * S, chunk)], 0)
 
 
 def _sphere_exit(rays, center, radius):
@@ -188,15 +259,16 @@ def _sphere_exit(rays, center, radius):
     return d1 + torch.sqrt(1. - pn * pn) * (1. / d.norm(dim=-1))
 
 
-def _bg_points(rays_b, img_b, pts4, real):
+def _bg_points(rays_b, img_b, pts4, real, with_dir=True):
     """[Nb * S, 3 + 4 + 3 + 1]: the real position (the cells' routing input, rendering.py:558-565) in front of the inverted-sphere point
-    pts4 [Nb * S, 4], then direction and image index.  real: [Nb, S, 3], or [Nb, 3] where it is the same for every sample of a ray."""
+    pts4 [Nb * S, 4], then direction and image index.  real: [Nb, S, 3], or [Nb, 3] where it is the same for every sample of a ray.
+    with_dir False (sh_deg): [Nb * S, 3 + 4 + 1], no direction columns."""
     Nb, S = rays_b.shape[0], pts4.shape[0] // rays_b.shape[0]
     if real.dim() == 2:
         real = real[:, None, :].expand(Nb, S, 3)
     d = rays_b[:, None, 3:6].expand(Nb, S, 3)
     img = img_b.to(torch.float32).view(Nb, 1, 1).expand(Nb, S, 1)
-    return torch.cat([real, pts4.view(Nb, S, 4), d, img], -1).view(Nb * S, 11)
+    return torch.cat([real, pts4.view(Nb, S, 4), d, img] if with_dir else [real, pts4.view(Nb, S, 4), img], -1).view(Nb * S, 11 if with_dir else 8)
 
 
 def _render_background(bg_nerf, cluster_2d, rays_b, img_b, center, radius, S, F, chunk, lin):
@@ -207,19 +279,21 @@ def _render_background(bg_nerf, cluster_2d, rays_b, img_b, center, radius, S, F,
     -> rgb [Nb, 3], depth [Nb]."""
     o = ops
     Nb, Sb = rays_b.shape[0], S // 2
+    sh = bg_nerf.sh_deg is not None
+    dirs = rays_b[:, 3:6].contiguous() if sh else None       # (sh_deg: one direction per ray, rows_per_group = the pass's samples)
     ro, rd = rays_b[:, None, :3], rays_b[:, None, 3:6]
     edge = None if cluster_2d else rays_b[:, :3] + rays_b[:, 3:6] * _sphere_exit(rays_b, center, radius).unsqueeze(-1)
     # (no frequencies, fp32, stride 4: the sampling op's encoding is then the inverted-sphere point itself)
     z_b, dreal_b, p4 = o.bg_sample_pe(rays_b, center, radius, Sb, 0, torch.float32, 4)
     real = ro + rd * dreal_b.flip(-1).unsqueeze(-1) if cluster_2d else edge      # (the points are flipped, depth_real is not: :302-304)
-    raw_b = _run(bg_nerf, _bg_points(rays_b, img_b, p4, real), chunk)
+    raw_b = _run(bg_nerf, _bg_points(rays_b, img_b, p4, real, not sh), chunk, dirs)
     rgb, depth, _, w_b, _ = o.composite_bounded_fwd(raw_b, z_b, None, True, dreal_b, want_weights=F > 0)
     if F > 0:
         Fb = F // 2
         z_f = o.sample_pdf(z_b.flip(-1).contiguous(), w_b, lin(Fb).expand(Nb, Fb).contiguous(), Fb)
         _, dreal_f, p4f = o.bg_sample_pe(rays_b, center, radius, Fb, 0, torch.float32, 4, z_in=z_f)
         real = ro + rd * dreal_f.unsqueeze(-1) if cluster_2d else edge
-        raw_f = _run(bg_nerf, _bg_points(rays_b, img_b, p4f, real), chunk)
+        raw_f = _run(bg_nerf, _bg_points(rays_b, img_b, p4f, real, not sh), chunk, dirs)
         zneg, order, raw_m = o.merge_samples((-z_f).contiguous(), (-z_b).contiguous(), raw_f, raw_b)      # descending sort (:421)
         dreal_m = torch.gather(torch.cat([dreal_f, dreal_b], 1), 1, order.long())                         # :432-433
         rgb, depth, _, _, _ = o.composite_bounded_fwd(raw_m, -zneg, None, True, dreal_m)
@@ -243,8 +317,13 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
                                   "(MegaNeRF.from_container(path, background=True)); a background model of another kind is not built")
     if getattr(hparams, "use_cascade", False):
         raise NotImplementedError("use_cascade is outside the hot path")
-    if getattr(hparams, "affine_appearance", False) or getattr(hparams, "sh_deg", None) is not None:
-        raise NotImplementedError("affine_appearance / sh_deg are not built for MegaNeRF")
+    if getattr(hparams, "affine_appearance", False):
+        raise NotImplementedError("affine_appearance is not built for MegaNeRF")
+    want = getattr(hparams, "sh_deg", None)                       # (rendering._check_sh's rule: hparams say what the model was built with)
+    for who, m in (("the model", nerf), ("the background model", bg_nerf)):
+        if m is not None and m.sh_deg != want:
+            raise NotImplementedError(f"hparams.sh_deg = {want} but {who} was built with sh_deg = {m.sh_deg}: build the container's "
+                                      "models and the hparams with the same sh_deg")
     if getattr(hparams, "device_noise_seed", None) is not None:
         raise NotImplementedError("device_noise_seed: MegaNeRF has no seeded device noise")
     if nerf.training or getattr(nerf, "graph_eval", False) or getattr(nerf, "graph_train", False):
@@ -256,6 +335,8 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
         image_indices = torch.zeros(N, dtype=torch.long, device=dev)
     chunk = int(hparams.model_chunk_size)
     lin = nerf.sub_modules[0]._linspace
+    sh = want is not None
+    dirs = rays[:, 3:6].contiguous() if sh else None              # (fg_bounds below changes the far bound only)
     Nb, bg_rgb, has_bg = 0, None, None
     if bg_nerf is not None:
         if bg_nerf.training or bg_nerf.dev != nerf.dev:
@@ -272,7 +353,7 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
                                                   image_indices.index_select(0, idx_bg).contiguous(), sphere_center, sphere_radius,
                                                   S, F, chunk, lin)
     z = ops.sample_z(rays, lin(S), None, 0.0, S)                  # evaluation: no jitter, no sigma noise (rendering.py:366)
-    raw = _run(nerf, _points(rays, z, image_indices), chunk)
+    raw = _run(nerf, _points(rays, z, image_indices, not sh), chunk, dirs)
     res: Dict[str, torch.Tensor] = {}
     if getattr(hparams, "return_sigma", False):
         res["sigma_coarse"] = raw[:, 3].view(N, S)
@@ -283,7 +364,7 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
         _, _, _, w = ops.composite_fwd(raw, z, want_weights=True)      # (the last delta only reaches the last weight, which :240 drops)
         u = lin(F).expand(N, F).contiguous()                      # det = (perturb == 0): linspace (rendering.py:605-609)
         z_fine = ops.sample_pdf(z, w, u, F)
-        raw_f = _run(nerf, _points(rays, z_fine, image_indices), chunk)
+        raw_f = _run(nerf, _points(rays, z_fine, image_indices, not sh), chunk, dirs)
         z, order, raw = ops.merge_samples(z_fine, z_c, raw_f, raw_c)
         typ, z_last = "fine", z_fine.max(dim=-1)[0]               # the FINE depths' maximum (:249-250)
         if getattr(hparams, "return_sigma", False):

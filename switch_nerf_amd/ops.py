@@ -1062,6 +1062,25 @@ def cells_blend(weights, slot, begin, sub_out, hard: bool):
     return out
 
 
+def cells_blend_sh(weights, slot, begin, sub_out, dirs, rows_per_group: int, deg: int, hard: bool, want_coef: bool = False):
+    """cells_blend for sub-models with spherical-harmonics colour, fused with the evaluation (swn_cells_blend_sh): sub_out [total, 3 B + 1]
+    (coefficients row-major [3, B], then sigma), dirs [P / rows_per_group, 3] f32 (not normalised) -> raw [P, 4] = (sigmoid(eval_sh of
+    the blended coefficients), blended sigma), or (raw, coef [P, 3 B + 1] = the blended rows).  The library checks deg, rows_per_group
+    and the sizes."""
+    P, K = weights.shape
+    total, width = sub_out.shape
+    assert weights.dtype == sub_out.dtype == dirs.dtype == torch.float32 and slot.dtype == begin.dtype == torch.int32
+    assert tuple(slot.shape) == (P, K) and begin.numel() == K + 1 and all(t.is_contiguous() for t in (weights, slot, begin, sub_out, dirs))
+    rows_per_group, deg = int(rows_per_group), int(deg)
+    if 0 <= deg <= 4 and rows_per_group >= 1 and P % rows_per_group == 0:      # (otherwise: the library's error)
+        assert width == 3 * (deg + 1) ** 2 + 1 and tuple(dirs.shape) == (P // rows_per_group, 3)
+    raw = torch.empty(P, 4, dtype=torch.float32, device=weights.device)
+    coef = torch.empty(P, width, dtype=torch.float32, device=weights.device) if want_coef else None
+    call("swn_cells_blend_sh", _p(weights), _p(slot), _p(begin), _p(sub_out), total, _p(dirs), rows_per_group, deg, P, K,
+         1 if hard else 0, _p(raw), _p(coef), _stream())
+    return (raw, coef) if want_coef else raw
+
+
 def composite_bounded_fwd(raw, z, last_delta=None, flip=False, depth_real=None, want_weights=False, want_bg_lambda=False):
     """Compositing with a per-ray last delta / descending depths / metric depth source / leftover transmittance
     (rendering.py:435-494 with last_delta, flip, depth_real, get_bg_lambda) -> rgb, depth, depth_variance, weights, bg_lambda."""
