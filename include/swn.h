@@ -845,6 +845,14 @@ int swn_cells_gather(const float* x, int stride, int col0, const int32_t* rows, 
  *   the sum order is the reference's loop order.                                                                                   */
 int swn_cells_blend(const float* weights, const int32_t* slot, const int32_t* begin, const float* sub_out, long total, int n_points,
                     int n_cells, int channels, int hard, float* out, void* stream);
+/* swn_cells_blend_bwd: the adjoint of swn_cells_blend with respect to sub_out (training through the cells; mega_nerf.py:47, :49).
+ *   d_sub[r][:] = w * d_out[rows[r]][:] for the packed rows r in [0, total), w = weights[rows[r]][i(r)] with i(r) the cell whose range
+ *   begin[i] <= r < begin[i + 1] holds r; hard != 0: w = 1, a plain copy (weights and begin are then not read and may be null).
+ *   rows / begin: swn_cells_pack's.  channels 1 or 4.  The weights depend on positions only and the router has no parameters, so this
+ *   is all that flows back.  Every packed row is written exactly once: no atomics, no zero fill, bit-deterministic; nothing past
+ *   d_sub[total] is touched.  total == 0: nothing is launched.  Errors: n_cells outside 1..64, channels, a null pointer.            */
+int swn_cells_blend_bwd(const float* weights, const int32_t* rows, const int32_t* begin, const float* d_out, long total, int n_points,
+                        int n_cells, int channels, int hard, float* d_sub, void* stream);
 /* swn_cells_blend_sh (sh.hip): swn_cells_blend for sub-models with spherical-harmonics colour, fused with rendering.py:344-347.  sub_out
  *   [total, 3 B + 1] fp32, B = (deg + 1)^2: a row is the coefficients row-major [3, B], then sigma (what DenseNeRF's sh_deg call
  *   returns).  coef[p][:] = sum over the member cells i, ascending, of weights[p][i] * sub_out[begin[i] + slot[p][i]][:]  (hard != 0:

@@ -160,6 +160,7 @@ SIGNATURES = {
     "swn_cells_pack": [vp, vp, i32, i32, vp, vp, i64, vp, vp, sz, vp],
     "swn_cells_gather": [vp, i32, i32, vp, i64, i32, vp, vp, vp, vp],
     "swn_cells_blend": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp],
+    "swn_cells_blend_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp],
     "swn_cells_blend_sh": [vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp, vp, vp],
     "swn_adam_step": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, f32, vp],
     "swn_cast": [vp, vp, i32, i64, vp],

@@ -6,6 +6,7 @@
 //   cells_place_kernel     slot[P, K] (row of a point inside a cell, or -1) and rows[total]   /
 //   cells_gather_kernel    every cell's input rows (and sigma-noise rows) from rows[]
 //   cells_blend_kernel     out[p] = sum over the member cells, ascending, of weights * sub-model output (a per-point gather: no atomics)
+//   cells_blend_bwd_kernel d_sub[r] = weights * d_out[rows[r]]: the blend's adjoint, one packed row per thread (training, mega.py)
 // Plain C++, fp32, fma contraction off: the distance is the direct sqrt(sum (x_j - c_j)^2) in the order j = dim_start .. 2 and the
 // weights are mega_nerf.py:21-27 operation by operation, so a CPU restatement with the same operation order gives the same bits.
 // Everything that decides an ORDER is an integer (counts, prefixes, ranks from wave ballots): the packing is a pure function of the
@@ -234,6 +235,45 @@ __global__ __launch_bounds__(256) void cells_blend_kernel(const float* __restric
     out[p] = acc[0];
 }
 
+// The adjoint of cells_blend_kernel with respect to sub_out: packed row r of cell i(r) belongs to point rows[r] and entered its output
+// with the factor weights[rows[r]][i(r)] (hard: 1), so that is what its gradient is.  One thread per packed row, every row written
+// once: no atomics, no zero fill.  i(r) is the cell with begin[i] <= r < begin[i + 1], found by bisection in the LDS copy of begin[]
+// (empty cells have begin[i] == begin[i + 1] and are never the answer); the hard form needs no weight and skips both.
+template <int C>
+__global__ __launch_bounds__(256) void cells_blend_bwd_kernel(const float* __restrict__ weights, const int32_t* __restrict__ rows,
+                                                             const int32_t* __restrict__ begin, const float* __restrict__ d_out, long total,
+                                                             int K, int hard, int P, float* __restrict__ d_sub) {
+#pragma clang fp contract(off)
+  __shared__ int sb[CELLS_MAX + 1];
+  if (!hard) {
+    if (threadIdx.x <= K) sb[threadIdx.x] = begin[threadIdx.x];
+    __syncthreads();
+  }
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  const int p = rows[r];
+  const bool ok = p >= 0 && p < P;            // (never false for a row list of swn_cells_pack)
+  float wt = 1.f;
+  if (!hard && ok) {
+    int lo = 0, hi = K - 1;                   // the first cell whose end lies past r
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if ((long)sb[mid + 1] > r) hi = mid; else lo = mid + 1;
+    }
+    wt = weights[(long)p * K + lo];
+  }
+  if constexpr (C == 4) {
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) q = *reinterpret_cast<const float4*>(d_out + (long)p * 4);
+    if (!hard) q.x = q.x * wt, q.y = q.y * wt, q.z = q.z * wt, q.w = q.w * wt;
+    *reinterpret_cast<float4*>(d_sub + r * 4) = q;
+  } else {
+    float v = ok ? d_out[p] : 0.f;
+    if (!hard) v = v * wt;
+    d_sub[r] = v;
+  }
+}
+
 }  // namespace swn
 
 using namespace swn;
@@ -307,6 +347,25 @@ extern "C" int swn_cells_blend(const float* weights, const int32_t* slot, const 
   else
     hipLaunchKernelGGL(cells_blend_kernel<1>, dim3(cdiv(n_points, 256)), dim3(256), 0, as_stream(stream), weights, slot, begin, sub_out,
                        total, n_cells, hard, n_points, out);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cells_blend_bwd(const float* weights, const int32_t* rows, const int32_t* begin, const float* d_out, long total,
+                                   int n_points, int n_cells, int channels, int hard, float* d_sub, void* stream) {
+  SWN_CHECK(n_cells >= 1 && n_cells <= CELLS_MAX, "swn_cells_blend_bwd: n_cells %d outside [1, %d]", n_cells, CELLS_MAX);
+  SWN_CHECK(channels == 1 || channels == 4, "swn_cells_blend_bwd: channels %d is neither 1 nor 4", channels);
+  SWN_CHECK(n_points >= 1 && total >= 0, "swn_cells_blend_bwd: bad sizes (n_points %d, total %ld)", n_points, total);
+  if (total == 0) return 0;
+  SWN_CHECK(rows && d_out && d_sub && (hard || (weights && begin)), "swn_cells_blend_bwd: null pointer");
+  SWN_CHECK(channels == 1 || ((((uintptr_t)d_out) | ((uintptr_t)d_sub)) & 15) == 0, "swn_cells_blend_bwd: d_out / d_sub must be 16-byte aligned");
+  SWN_CHECK(total <= 2147483647l * 256, "swn_cells_blend_bwd: %ld rows exceed the grid", total);      // (cdiv returns an int)
+  if (channels == 4)
+    hipLaunchKernelGGL(cells_blend_bwd_kernel<4>, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), weights, rows, begin, d_out,
+                       total, n_cells, hard, n_points, d_sub);
+  else
+    hipLaunchKernelGGL(cells_blend_bwd_kernel<1>, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), weights, rows, begin, d_out,
+                       total, n_cells, hard, n_points, d_sub);
   SWN_LAUNCH_CHECK();
   return 0;
 }

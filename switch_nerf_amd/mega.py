@@ -17,8 +17,24 @@ rows and the reference blends THOSE before rendering.py:344-347 applies sigmoid(
 wide rows and the evaluation in one launch (call_rgb; render_rays), or leaves the blended rows (the module mirror, __call__).
 
 Inside a cell the rows ascend by point index - the order x[cluster_mask] has in the reference, so sigma_noise[cluster_mask] lines up.
-Inference only: joint_training (the reference's distributed-training hack), device noise and graph capture are not built.
-render_rays() below is what rendering.render_rays runs for a MegaNeRF foreground.
+render_rays() below is what rendering.render_rays runs for a MegaNeRF foreground (evaluation).
+
+Training (--train_mega_nerf, models/model_utils.py:118-123: MegaNeRF([NeRF ...], centroids, 1, xyz_dim == 4, cluster_2d, True)) is opt-in,
+MegaNeRF(..., joint_training=True); without the flag the model is inference only, as before.  The same route -> pack -> gather, then
+
+    c_i = sub_modules[i].forward_rays(rows of cell i as one-sample rays, ..., training=True, composite=False)     a SAVING forward per cell
+    out = ops.cells_blend(weights, slot, begin, sub_out, hard)                                     forward_points -> ctx
+    d_sub = ops.cells_blend_bwd(weights, rows, begin, d_out, total, hard)                         the blend's adjoint (swn_cells_blend_bwd)
+    sub_modules[i].backward_net(c_i, d_sub[begin[i]:begin[i + 1]])                                backward_points: into each cell's gradient
+
+The weights depend on positions only and the router has no parameters: nothing else flows back.  grad_step / apply_step / train_step put
+the library's sampling, compositing, loss and Adam around it like SwitchNeRF.train_step does (coarse only, or coarse + fine with the
+sort-merge).  A cell that no point reached in a step keeps a ZERO gradient, not a missing one (the reference's joint_training branch,
+mega_nerf.py:51-59), so Adam still advances it.  What training costs here and does not hide: every cell runs its own launch sequence, and
+a cell's rows are not whole rays, so the per-ray feature and the head backward run per point (rows_per_group 1).
+Not built for training (each raises NotImplementedError): spherical-harmonics cells (swn_cells_blend_sh has no backward), the xyz_real
+background half, fp16 cells (one loss scale over K models), seeded device noise, graph capture (counts.tolist() sizes the ragged calls),
+expert / data parallelism, and rendering.render_rays on a model in training mode (the autograd bridge for a MegaNeRF is a later change).
 """
 from __future__ import annotations
 
@@ -79,9 +95,13 @@ def dense_cfg_from_state_dict(sd, xyz_dim: int, allow_sh: bool = False) -> dict:
 class MegaNeRF:
     is_mega_nerf = True      # what rendering.render_rays dispatches on (no import of this module on the other models' path)
 
-    def __init__(self, sub_modules: Sequence[DenseNeRF], centroids, boundary_margin: float, xyz_real: bool, cluster_2d: bool):
+    def __init__(self, sub_modules: Sequence[DenseNeRF], centroids, boundary_margin: float, xyz_real: bool, cluster_2d: bool,
+                 joint_training: bool = False):
         """sub_modules: one DenseNeRF per cell (xyz_dim 4 with xyz_real, the background model; 3 otherwise), all of one compute dtype;
-        they are put into evaluation mode.  centroids [K, 3].  Attributes as rendering.py:52-53 reads them."""
+        they are put into evaluation mode.  centroids [K, 3].  Attributes as rendering.py:52-53 reads them.
+        joint_training (mega_nerf.py:9, the reference's last constructor argument): the model trains through its cells (forward_points /
+        backward_points / train_step); model and cells then start in training mode like a fresh nn.Module, and train() / eval() switch
+        every cell.  The learning rate and the step count are the model's own (taken from the first cell), shared by every cell."""
         assert boundary_margin >= 1                              # mega_nerf.py:11
         sub_modules = list(sub_modules)
         cen = centroids if torch.is_tensor(centroids) else torch.from_numpy(np.asarray(centroids))
@@ -93,7 +113,8 @@ class MegaNeRF:
         for m in sub_modules:
             if not isinstance(m, DenseNeRF) or m.xyz_dim != xd:
                 raise TypeError(f"sub-models must be DenseNeRF with xyz_dim {xd} (xyz_real = {bool(xyz_real)})")
-            m.eval()
+            if not joint_training:
+                m.eval()
         degs = [m.sh_deg for m in sub_modules]
         if any(d != degs[0] for d in degs):      # one row width for every cell: the blend adds the cells' raw rows (mega_nerf.py:43-49)
             if any(d is None for d in degs):
@@ -108,16 +129,43 @@ class MegaNeRF:
         self.xyz_real = bool(xyz_real)
         self.xyz_dim = xd
         self.cluster_dim_start = 1 if cluster_2d else 0
-        self.joint_training = False
+        self.joint_training = bool(joint_training)
         self.training = False
         self.moe_no_batch = False
+        if self.joint_training:
+            self._check_trainable()
+            self.lr = self.base_lr = float(sub_modules[0].base_lr)
+            self.step_count = int(sub_modules[0].step_count)
+            for m in sub_modules:
+                m._grow_bufs = True                              # a cell's row count changes every step: one buffer per name, grown
+            self.train(True)
+
+    def _check_trainable(self):
+        """What training through the cells does not build, named at construction."""
+        if self.sh_deg is not None:
+            raise NotImplementedError("joint_training with spherical-harmonics cells (sh_deg) is not built: their blend is "
+                                      "swn_cells_blend_sh, which has no backward")
+        if self.xyz_real:
+            raise NotImplementedError("joint_training with xyz_real (the background half) is not built: it needs BackgroundScene's "
+                                      "bounded compositing backward around the cells")
+        if self.dtype == torch.float16:
+            raise NotImplementedError("joint_training with fp16 cells is not built: one loss scale shared over the cell models is "
+                                      "missing; use bfloat16 or float32")
+        for m in self.sub_modules:
+            if m.dtype != self.dtype or m.dev != self.dev:
+                raise ValueError("joint_training: every cell must have the same compute dtype and device")
+            if m.device_noise:
+                raise NotImplementedError("joint_training with seeded device noise (set_device_noise) on a cell is not built: supply "
+                                          "perturb_rand / sigma_noise, or let the step draw them with torch")
+            if m.ep is not None:
+                raise NotImplementedError("joint_training with expert parallelism is not built (a cell has no experts to shard)")
 
     # ------------------------------------------------------------------------------------------ construction
     @classmethod
     def from_state_dicts(cls, state_dicts, centroids, cfg: Optional[dict] = None, boundary_margin: float = 1.15, xyz_real: bool = False,
-                         cluster_2d: bool = False, dtype=torch.float32, device="cuda") -> "MegaNeRF":
+                         cluster_2d: bool = False, dtype=torch.float32, device="cuda", joint_training: bool = False) -> "MegaNeRF":
         """One DenseNeRF per reference-NeRF state_dict (DenseNeRF.load_state_dict takes that key layout); cfg None: derived from the
-        tensor shapes of each state_dict."""
+        tensor shapes of each state_dict.  joint_training: the constructor's."""
         xd = 4 if xyz_real else 3
         subs = []
         for sd in state_dicts:
@@ -125,13 +173,14 @@ class MegaNeRF:
             m = DenseNeRF(c, dtype=dtype, device=device)
             m.load_state_dict(sd)
             subs.append(m)
-        return cls(subs, centroids, boundary_margin, xyz_real, cluster_2d)
+        return cls(subs, centroids, boundary_margin, xyz_real, cluster_2d, joint_training)
 
     @classmethod
     def from_container(cls, path, boundary_margin: float = 1.15, background: bool = False, dtype=torch.float32,
                        device="cuda") -> "MegaNeRF":
         """A merged Mega-NeRF container (a TorchScript archive with `centroids`, `cluster_2d` and sub_module_{i} / bg_sub_module_{i},
-        model_utils.py:90-96): the foreground model, or with background=True the xyz_real background model."""
+        model_utils.py:90-96): the foreground model, or with background=True the xyz_real background model.  Inference only (a
+        container is what merging trained cells produces; to train, build from_state_dicts(..., joint_training=True))."""
         container = torch.jit.load(path, map_location="cpu")
         centroids = container.centroids
         prefix = "bg_sub_module_{}" if background else "sub_module_{}"
@@ -142,12 +191,51 @@ class MegaNeRF:
         return [m.state_dict() for m in self.sub_modules]
 
     def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("MegaNeRF is inference only: training through the cells (joint_training) is not built")
+        if not self.joint_training:
+            if mode:
+                raise NotImplementedError("MegaNeRF is inference only: training through the cells (joint_training) is not built "
+                                          "for this model - construct it with joint_training=True")
+            return self
+        self.training = bool(mode)
+        for m in self.sub_modules:
+            m.train(mode)
         return self
 
     def eval(self):
-        return self
+        return self.train(False)
+
+    # ------------------------------------------------------------------------------------------ parameters (all cells)
+    def named_parameters(self):
+        """(key, tensor) over every cell, keys `sub_modules.{i}.` + the reference NeRF's (the ModuleList keys of mega_nerf.py:14)."""
+        for i, m in enumerate(self.sub_modules):
+            for k, v in m.named_parameters():
+                yield f"sub_modules.{i}.{k}", v
+
+    def parameters(self):
+        return (v for _, v in self.named_parameters())
+
+    def grad_dict(self):
+        """Every cell's gradient under the keys of named_parameters()."""
+        return {f"sub_modules.{i}.{k}": v for i, m in enumerate(self.sub_modules) for k, v in m.grad_dict().items()}
+
+    def set_iteration(self, iteration: int, lr_decay_factor: float = 0.1, train_iterations: int = 500000):
+        """The learning-rate schedule hook of SwitchNeRF.set_iteration, forwarded to every cell: one rate for the whole model."""
+        self._need_joint("set_iteration")
+        for m in self.sub_modules:
+            m.base_lr = self.base_lr
+            self.lr = m.set_iteration(iteration, lr_decay_factor, train_iterations)
+        return self.lr
+
+    def set_expert_parallel(self, ep):
+        raise NotImplementedError("MegaNeRF: expert parallelism is not built (the cells are dense models; nothing is sharded)")
+
+    def set_device_noise(self, seed, step: int = 0, ray_base: int = 0):
+        if seed is not None:
+            raise NotImplementedError("MegaNeRF has no seeded device noise: supply perturb_rand / sigma_noise, or let the step draw them")
+
+    def _need_joint(self, what):
+        if not self.joint_training:
+            raise NotImplementedError(f"MegaNeRF.{what}: this model is inference only - construct it with joint_training=True")
 
     # ------------------------------------------------------------------------------------------ forward
     def route(self, x):
@@ -220,6 +308,127 @@ class MegaNeRF:
             # DenseNeRF's sh_deg call returns lin at every degree; the degenerate degree is squared with the reference here.
             sub_out[:, :3] = torch.sigmoid(sub_out[:, :3])
         return weights, slot, begin, sub_out, hard
+
+    # ------------------------------------------------------------------------------------------ training through the cells
+    def forward_points(self, x, sigma_noise=None, tag: str = "c"):
+        """The training form of __call__: x [P, 3 + 3 + 1] -> ctx with ctx["out"] [P, 4] and what backward_points needs.  Every non-empty
+        cell runs a SAVING forward on its packed rows (DenseNeRF.forward_rays on one-sample rays, as DenseNeRF.__call__ does), so a cell
+        holds ONE live context per tag: a second forward_points under the same tag overwrites the first one's saved activations (the
+        hierarchical step runs its fine pass under tag "f")."""
+        self._need_joint("forward_points")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("MegaNeRF: graph capture is not built - counts.tolist() sizes the ragged per-cell calls on the host")
+        if x.dim() != 2 or x.shape[1] != 7:
+            raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(tuple(x.shape), 7, self.xyz_dim))
+        P = x.shape[0]
+        if P == 0:
+            raise ValueError("MegaNeRF.forward_points: no points")
+        x = x.to(torch.float32).contiguous()
+        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
+        hard = self.boundary_margin == 1
+        weights, counts, begin, rows, slot = self.route(x)
+        n = counts.tolist()                                    # the one synchronisation: K ints size the ragged sub-model calls
+        total = sum(n)
+        if total == 0:
+            raise ValueError("MegaNeRF: no point belongs to a cell - the positions are not finite")
+        xin, nin = ops.cells_gather(x, rows, total, 0, noise)
+        rays = torch.cat([xin[:, :6], torch.zeros(total, 2, device=self.dev)], 1)      # o = xyz, near = far = 0 -> the sample IS the point
+        img = xin[:, 6].long()
+        sub_out = torch.empty(total, 4, dtype=torch.float32, device=self.dev)
+        cells, b = [], 0
+        for i, child in enumerate(self.sub_modules):
+            c = None
+            if n[i] > 0:                                       # (empty cells are skipped, :38; their gradient stays zero, :51-59)
+                sl = slice(b, b + n[i])
+                c = child.forward_rays(rays[sl].contiguous(), img[sl].contiguous(), 1, n[i], 0.0, None, None if nin is None else nin[sl],
+                                       training=True, tag=tag, composite=False)
+                sub_out[sl] = c["raw"]
+            cells.append(c)
+            b += n[i]
+        out = ops.cells_blend(weights, slot, begin, sub_out, hard)
+        return dict(out=out, weights=weights, rows=rows, begin=begin, slot=slot, cells=cells, counts=n, total=total, hard=hard, P=P, tag=tag)
+
+    def backward_points(self, ctx, d_out):
+        """Backward of forward_points given dL/d out [P, 4]: the blend's adjoint (ops.cells_blend_bwd), then every non-empty cell's
+        backward_net on its rows - accumulated into that cell's gradient (nothing is zeroed here)."""
+        self._need_joint("backward_points")
+        if tuple(d_out.shape) != (ctx["P"], 4):
+            raise ValueError(f"backward_points: d_out {tuple(d_out.shape)} for an output of [{ctx['P']}, 4]")
+        d_sub = ops.cells_blend_bwd(ctx["weights"], ctx["rows"], ctx["begin"], d_out.to(torch.float32).contiguous(), ctx["total"], ctx["hard"])
+        b = 0
+        for child, c, n in zip(self.sub_modules, ctx["cells"], ctx["counts"]):
+            if n > 0:
+                child.backward_net(c, d_sub[b:b + n], None)
+            b += n
+
+    def grad_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, fine_samples=0, fine_u=None,
+                  sigma_noise_fine=None):
+        """Forward + loss + backward of one training step (SwitchNeRF.grad_step's contract): zeroes every cell's gradient, fills it, and
+        returns the metrics.  The whole batch goes through the cells in one call: a MegaNeRF's output for a point does not depend on the
+        other points of its chunk, so there is no model_chunk_size loop.  fine_samples > 0: the sequence of SwitchNeRF.forward_hier
+        (coarse pass with weights, sample_pdf from the detached weights, fine pass under tag "f", sort-merge, compositing of the union)."""
+        self._need_joint("grad_step")
+        o = ops
+        N, S, F = rays.shape[0], int(n_samples), int(fine_samples)
+        rays = rays.to(torch.float32).contiguous()
+        for m in self.sub_modules:
+            m.grad.zero_()
+        lin = self.sub_modules[0]._linspace
+        if perturb != 0 and perturb_rand is None:
+            perturb_rand = torch.rand(N, S, device=self.dev)
+        z = o.sample_z(rays, lin(S), perturb_rand if perturb != 0 else None, perturb, S)
+        c = self.forward_points(_points(rays, z, image_indices), sigma_noise, "c")
+        raw = c["out"]
+        if F == 0:
+            cf = None
+            out = dict(raw=raw, z=z)
+            out["rgb"], out["depth"], out["depth_variance"], _ = o.composite_fwd(raw, z)
+        else:
+            _, _, _, w = o.composite_fwd(raw, z, want_weights=True)
+            if fine_u is None:                                 # det = (perturb == 0): linspace, else rand (rendering.py:605-609)
+                fine_u = lin(F).expand(N, F).contiguous() if perturb == 0 else torch.rand(N, F, device=self.dev)
+            z_fine = o.sample_pdf(z, w, fine_u, F)
+            cf = self.forward_points(_points(rays, z_fine, image_indices), sigma_noise_fine, "f")
+            zm, order, raw_m = o.merge_samples(z_fine, z, cf["out"], raw)
+            out = dict(raw=raw_m, z=zm, order=order, z_fine=z_fine)
+            out["rgb"], out["depth"], out["depth_variance"], _ = o.composite_fwd(raw_m, zm)
+        # a MegaNeRF returns a tensor: no gate loss (rendering.py:385-406) - a zero operand with weight 0
+        zero = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        out4, d_rgb, _, _ = o.step_loss(out["rgb"], rgbs.to(torch.float32).contiguous(), zero, None, 0.0, None)
+        d_raw = o.composite_bwd(out["raw"], out["z"], d_rgb)
+        if F == 0:
+            self.backward_points(c, d_raw)
+        else:
+            d_raw_f, d_raw_c = o.unmerge_grad(d_raw, out["order"], F, S)
+            self.backward_points(cf, d_raw_f)
+            self.backward_points(c, d_raw_c)
+        res = dict(loss=out4[2], photo_loss=out4[0], gate_loss=out4[1], psnr=out4[3], depth_variance=out["depth_variance"].mean(), ctx=c,
+                   rgb=out["rgb"], depth=out["depth"])
+        if cf is not None:
+            res["ctx_fine"] = cf
+        return res
+
+    def apply_step(self, grad_allreduce=None, optimizer_step=True):
+        """One Adam step on every cell with the model's one step count and learning rate.  A cell no point reached has a zero gradient,
+        not a missing one: its step count advances, its moments decay and it moves by momentum, like the reference's joint_training cells
+        under one torch.optim.Adam."""
+        self._need_joint("apply_step")
+        if grad_allreduce is not None:
+            raise NotImplementedError("MegaNeRF: data parallelism (a gradient all-reduce over the cells' buffers) is not built")
+        if not optimizer_step:
+            return
+        self.step_count += 1
+        for m in self.sub_modules:
+            m.step_count, m.lr = self.step_count, self.lr
+            ops.adam_step(m.flat, m.grad, m.m, m.v, None, self.step_count, self.lr)
+            m.refresh_compute_copies()
+
+    def train_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, optimizer_step=True,
+                   fine_samples=0, fine_u=None, sigma_noise_fine=None):
+        """grad_step + apply_step; result keys as SwitchNeRF.train_step (loss, photo_loss, psnr, rgb, depth, depth_variance; gate_loss 0)."""
+        res = self.grad_step(rgbs, rays, image_indices, n_samples, perturb, perturb_rand, sigma_noise, fine_samples, fine_u, sigma_noise_fine)
+        self.apply_step(None, optimizer_step)
+        return res
 
 
 # ---------------------------------------------------------------------------------------------- rendering
@@ -308,7 +517,9 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
     (rendering.py:385-406).
     bg_nerf: the xyz_real MegaNeRF of the same container (model_utils.py:89-96).  Every ray is clipped at the foreground bound
     (swn_fg_bounds); the rays that leave it continue through _render_background and are blended in with the foreground's leftover
-    transmittance (rendering.py:104-134), like background.BackgroundScene does for a dense background model."""
+    transmittance (rendering.py:104-134), like background.BackgroundScene does for a dense background model.
+    A model in training mode (joint_training, after train()) is refused: training runs through MegaNeRF.train_step, and the autograd
+    bridge that would let this function return differentiable tensors for a MegaNeRF is a later change."""
     from .rendering import _point_keys
     if not isinstance(nerf, MegaNeRF):
         raise NotImplementedError("a MegaNeRF background model behind a foreground model of another kind is not built")
@@ -327,7 +538,8 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
     if getattr(hparams, "device_noise_seed", None) is not None:
         raise NotImplementedError("device_noise_seed: MegaNeRF has no seeded device noise")
     if nerf.training or getattr(nerf, "graph_eval", False) or getattr(nerf, "graph_train", False):
-        raise NotImplementedError("MegaNeRF renders in evaluation mode without graph capture")
+        raise NotImplementedError("MegaNeRF renders in evaluation mode without graph capture (a joint_training model trains through "
+                                  "MegaNeRF.train_step; call eval() before rendering)")
     N, S, F = rays.shape[0], hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
     rays = rays.contiguous()
     dev = rays.device

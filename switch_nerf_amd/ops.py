@@ -1062,6 +1062,18 @@ def cells_blend(weights, slot, begin, sub_out, hard: bool):
     return out
 
 
+def cells_blend_bwd(weights, rows, begin, d_out, total: int, hard: bool):
+    """d_sub [total, C] = weights[rows[r], cell of r] * d_out[rows[r]] (swn_cells_blend_bwd): the adjoint of cells_blend with respect to
+    sub_out, C = d_out.shape[1] in {1, 4}; hard: the plain copy.  rows / begin: cells_pack's."""
+    P, K = weights.shape
+    Cn, total = d_out.shape[1], int(total)
+    assert weights.dtype == d_out.dtype == torch.float32 and rows.dtype == begin.dtype == torch.int32 and d_out.shape[0] == P
+    assert 0 <= total <= rows.numel() and begin.numel() == K + 1 and all(t.is_contiguous() for t in (weights, rows, begin, d_out))
+    d_sub = torch.empty(total, Cn, dtype=torch.float32, device=weights.device)
+    call("swn_cells_blend_bwd", _p(weights), _p(rows), _p(begin), _p(d_out), total, P, K, Cn, 1 if hard else 0, _p(d_sub), _stream())
+    return d_sub
+
+
 def cells_blend_sh(weights, slot, begin, sub_out, dirs, rows_per_group: int, deg: int, hard: bool, want_coef: bool = False):
     """cells_blend for sub-models with spherical-harmonics colour, fused with the evaluation (swn_cells_blend_sh): sub_out [total, 3 B + 1]
     (coefficients row-major [3, B], then sigma), dirs [P / rows_per_group, 3] f32 (not normalised) -> raw [P, 4] = (sigmoid(eval_sh of
