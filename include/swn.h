@@ -864,6 +864,40 @@ int swn_cells_blend_bwd(const float* weights, const int32_t* rows, const int32_t
 int swn_cells_blend_sh(const float* weights, const int32_t* slot, const int32_t* begin, const float* sub_out, long total, const float* dirs,
                        int rows_per_group, int deg, int n_points, int n_cells, int hard, float* raw, float* coef_out, void* stream);
 
+/* ---- training cells with spherical-harmonics colour (mega.py: MegaNeRF(.., joint_training=True, sh_training=True); sh.hip) ----------
+ * The reference blends the cells' raw rows and evaluates the basis on the blend, so with raw[p] = swn_cells_blend_sh's output the
+ * gradient of a cell's linear colour output is rank one: d_lin[r][c B + b] = q_c[r] Y_b(r), d_sigma_out[r] = q_3[r], with
+ *     q_c[r] = w_r d_raw[p][c] raw[p][c] (1 - raw[p][c])   c < 3   (deg 0: additionally s_c[r] (1 - s_c[r]), s = sub_out[r], the cell's
+ *     q_3[r] = w_r d_raw[p][3]                                       own sigmoid, models/nerf.py:140-141)
+ * p = rows[r], w_r = weights[p][i(r)] (hard != 0: 1; weights and begin may then be null), i(r) the cell with begin[i] <= r < begin[i + 1].
+ * swn_cells_blend_sh_bwd: the adjoint of swn_cells_blend_sh with respect to sub_out in that factored form.  q [total, 4],
+ *   dirs_packed [total, 3] = dirs[rows[r] / rows_per_group]; the [total, 3 B + 1] gradient is never written.  sub_out [total, 4] is read
+ *   at degree 0 only and may be null otherwise.  Every packed row is written exactly once, nothing at or past row `total` is touched;
+ *   total == 0 launches nothing.  fp32, no atomics, bit-deterministic.  Errors: n_cells outside 1..64, deg outside 0..4,
+ *   rows_per_group < 1 or not dividing n_points, a null pointer. */
+int swn_cells_blend_sh_bwd(const float* weights, const int32_t* rows, const int32_t* begin, const float* raw, const float* d_raw,
+                           const float* dirs, const float* sub_out, long total, int rows_per_group, int deg, int n_points, int n_cells,
+                           int hard, float* q, float* dirs_packed, void* stream);
+/* swn_heads_coef_fwd: a cell's heads over n_rows packed rows: out[r] = (h2[r] Wc^T + bc  [3 B], softplus(y[r] . w_sigma + b_sigma +
+ *   sigma_noise[r] - 1)) with a row stride of out_stride >= 3 B + 1 floats, so that `out` can be the cell's slice of the packed sub_out.
+ *   No basis, no fold, no per-ray unit; sigma path and sigma_noise (may be NULL) as swn_heads_sh_fwd.  inner_sigmoid != 0 (degree 0
+ *   only): the three colour outputs are sigmoid(lin).  (model_dim, h2_dim) pairs and dtypes: swn_heads_sh_fwd's. */
+int swn_heads_coef_fwd(const void* y, const void* h2, int dtype, const float* w_sigma, const float* b_sigma, const float* w_color,
+                       const float* b_color, const float* sigma_noise, int deg, int inner_sigmoid, int n_rows, int model_dim, int h2_dim,
+                       float* out, long out_stride, void* stream);
+/* swn_heads_coef_bwd: the backward of swn_heads_coef_fwd from q [n_rows, 4] and dirs [n_rows, 3] (one direction per row, not
+ *   normalised; swn_cells_blend_sh_bwd's outputs, a cell's slice) and the cell's own sigma output sigma[r * sigma_stride].  Outputs as
+ *   swn_heads_sh_bwd at rows_per_group = 1: dh2 = sum_k q_c Y_b Wc[c B + b] masked by h2 > 0, dsig = q_3 (1 - exp(-sigma)),
+ *   group_colsum [n_rows, h2_dim] (the dh2 rows as stored; may be NULL), and the four parameter gradients ACCUMULATED through block
+ *   partials and the ordered reduce: d_w_color[c B + b] += sum_r q_c[r] Y_b(r) h2[r], d_b_color likewise, d_w_sigma, d_b_sigma (the
+ *   compensated pair of swn_heads_sh_bwd).  fp32 on the vector pipe, no atomics, fixed order.  The workspace is sized by the (capped)
+ *   block counts: it does not grow with n_rows past the caps. */
+int swn_heads_coef_bwd_workspace_bytes(int n_rows, int model_dim, int h2_dim, int deg, size_t* bytes);
+int swn_heads_coef_bwd(const void* y, const void* h2, int dtype, const float* w_color, const float* q, const float* dirs,
+                       const float* sigma, long sigma_stride, int n_rows, int model_dim, int h2_dim, int deg, void* dh2, float* dsig,
+                       float* d_w_sigma, float* d_b_sigma, float* d_w_color, float* d_b_color, float* group_colsum, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -491,6 +491,428 @@ static ShWs sh_ws(int n_points, int model_dim, int h2_dim, int rows_per_group, i
   return w;
 }
 
+
+// ---- training Mega-NeRF cells with spherical-harmonics colour (mega.py, sh_training) --------------------------------------------------
+// The reference blends the cells' raw [3 B + 1] rows and evaluates the basis on the BLEND (rendering.py:344-347), so a cell's head emits
+// its coefficient row and the basis enters the backward only: with rgb = sigmoid(sum_b Y_b blended[c B + b]) the gradient of a cell's
+// linear colour output is rank one in (c, b), d_lin[r][c B + b] = q_c[r] Y_b(r).  swn_cells_blend_sh_bwd leaves q [total, 4] and one
+// direction per packed row; the wide gradient is never written.  A cell's packed rows are not whole rays, so nothing is folded per
+// ray here: the heads below work per row against Wc staged in LDS.
+
+// One thread per packed row (cells_blend_bwd_kernel's shape): the cell by bisection in the LDS copy of begin[] (soft margin only).
+__global__ __launch_bounds__(256) void cells_blend_sh_bwd_kernel(const float* __restrict__ weights, const int32_t* __restrict__ rows,
+                                                                const int32_t* __restrict__ begin, const float* __restrict__ raw,
+                                                                const float* __restrict__ d_raw, const float* __restrict__ dirs,
+                                                                const float* __restrict__ sub_out, long total, int rows_per_group, int K,
+                                                                int hard, int deg, long P, float* __restrict__ q,
+                                                                float* __restrict__ dirs_packed) {
+#pragma clang fp contract(off)
+  __shared__ int sb[BSH_MAX_CELLS + 1];
+  if (!hard) {
+    if ((int)threadIdx.x <= K) sb[threadIdx.x] = begin[threadIdx.x];
+    __syncthreads();
+  }
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= total) return;
+  const long p = rows[r];
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  float dx = 0.f, dy = 0.f, dz = 0.f;
+  if (p >= 0 && p < P) {                      // (never false for a row list of swn_cells_pack)
+    const float4 rr = *reinterpret_cast<const float4*>(raw + p * 4);
+    const float4 d = *reinterpret_cast<const float4*>(d_raw + p * 4);
+    o = d;
+    if (!hard) {
+      int lo = 0, hi = K - 1;                 // the first cell whose end lies past r
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)sb[mid + 1] > r) hi = mid; else lo = mid + 1;
+      }
+      const float wt = weights[p * K + lo];
+      o.x = wt * o.x, o.y = wt * o.y, o.z = wt * o.z, o.w = wt * o.w;
+    }
+    // (left to right, each product rounded once: w d_raw raw (1 - raw))
+    o.x = o.x * rr.x * (1.f - rr.x);
+    o.y = o.y * rr.y * (1.f - rr.y);
+    o.z = o.z * rr.z * (1.f - rr.z);
+    if (deg == 0) {                           // the cell's row holds s = sigmoid(lin) (models/nerf.py:140-141): its derivative here
+      const float4 s = *reinterpret_cast<const float4*>(sub_out + r * 4);
+      o.x = o.x * s.x * (1.f - s.x), o.y = o.y * s.y * (1.f - s.y), o.z = o.z * s.z * (1.f - s.z);
+    }
+    const float* dd = dirs + (p / rows_per_group) * 3;
+    dx = dd[0], dy = dd[1], dz = dd[2];
+  }
+  *reinterpret_cast<float4*>(q + r * 4) = o;
+  dirs_packed[r * 3 + 0] = dx;
+  dirs_packed[r * 3 + 1] = dy;
+  dirs_packed[r * 3 + 2] = dz;
+}
+
+constexpr int CF_KC = 25;                 // rows of Wc per LDS chunk (one colour at degree 4)
+constexpr int CF_RPG = 4;                 // rows per 16-lane group and tile: a chunk in LDS serves 64 rows
+constexpr int CF_TILE = 16 * CF_RPG;
+constexpr int CF_MAXK = 3 * SH_MAXB;
+
+// rows k0 .. k0 + nk of Wc [3 B, H2] into LDS in the 16-lane row layout (sh_fold's), by the whole block; the caller's barriers around it
+template <typename RH, int H2>
+__device__ __forceinline__ void coef_stage(const float* __restrict__ wc, int k0, int nk, float (*wl)[16][RH::VPL]) {
+  for (int e = threadIdx.x; e < nk * H2; e += 256) {
+    const int kk = e / H2, col = e - kk * H2;
+    const int chunk = col / RH::EPC, within = col - chunk * RH::EPC;      // the inverse of Row16::col
+    wl[kk][chunk & 15][(chunk >> 4) * RH::EPC + within] = wc[(long)(k0 + kk) * H2 + col];
+  }
+}
+
+static int coef_blocks(long n) {
+  const long t = (n + CF_TILE - 1) / CF_TILE;
+  return t > 1024 ? 1024 : (t < 1 ? 1 : (int)t);
+}
+
+// out[r] = (h2[r] Wc^T + bc  [3 B], softplus(y[r] . ws + bs + noise[r] - 1)) with row stride `stride` floats: a cell's slice of the packed
+// rows.  No basis, no fold.  A block walks tiles of 64 rows, a 16-lane group four of them; a linear output is the existing `coef`
+// expression (per-lane products in value order, sum16, + bias).  Lane k & 15 keeps output k: a group stores 16 outputs as one run.
+template <typename T_, int M, int H2>
+__global__ __launch_bounds__(256) void heads_coef_fwd_kernel(const T_* __restrict__ y, const T_* __restrict__ h2, const float* __restrict__ ws,
+                                                             const float* __restrict__ bs, const float* __restrict__ wc,
+                                                             const float* __restrict__ bc, const float* __restrict__ noise, int deg,
+                                                             int inner_sigmoid, long n, float* __restrict__ out, long stride) {
+  using RY = Row16<T_, M>;
+  using RH = Row16<T_, H2>;
+  __shared__ float wl[CF_KC][16][RH::VPL];
+  const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const int K3 = 3 * (deg + 1) * (deg + 1);
+  float wsv[RY::VPL];
+  RY::loadf(ws, j, wsv);
+  const float b_s = bs[0];
+  const long n_tiles = (n + CF_TILE - 1) / CF_TILE;
+  for (long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    float hv[CF_RPG][RH::VPL];
+    long ri[CF_RPG];
+#pragma unroll
+    for (int i = 0; i < CF_RPG; ++i) {
+      const long r = t * CF_TILE + grp + 16 * i;
+      ri[i] = r < n ? r : -1;
+      const long rc = r < n ? r : n - 1;      // (rows past the end: a valid row is read, nothing is stored)
+      float yv[RY::VPL];
+      RY::load(y + rc * M, j, yv);
+      RH::load(h2 + rc * H2, j, hv[i]);
+      float s = 0.f;
+#pragma unroll
+      for (int v = 0; v < RY::VPL; ++v) s += yv[v] * wsv[v];
+      s = sum16(s);
+      if (j == 0 && r < n) {
+        const float uu = s + b_s + (noise ? noise[r] : 0.f) - 1.f;      // ShiftedSoftplus, models/nerf.py:68-69
+        out[r * stride + K3] = uu > 20.f ? uu : log1pf(expf(uu));
+      }
+    }
+    for (int k0 = 0; k0 < K3; k0 += CF_KC) {
+      const int nk = K3 - k0 < CF_KC ? K3 - k0 : CF_KC;
+      __syncthreads();                        // (the previous chunk's readers are done)
+      coef_stage<RH, H2>(wc, k0, nk, wl);
+      __syncthreads();
+      float keep[CF_RPG];
+#pragma unroll
+      for (int i = 0; i < CF_RPG; ++i) keep[i] = 0.f;
+#pragma unroll 1
+      for (int kk = 0; kk < nk; ++kk) {
+        float wv[RH::VPL];
+#pragma unroll
+        for (int v = 0; v < RH::VPL; ++v) wv[v] = wl[kk][j][v];
+        const float bk = bc[k0 + kk];
+#pragma unroll
+        for (int i = 0; i < CF_RPG; ++i) {
+          float a = 0.f;
+#pragma unroll
+          for (int v = 0; v < RH::VPL; ++v) a += hv[i][v] * wv[v];
+          a = sum16(a) + bk;
+          if (inner_sigmoid) a = 1.f / (1.f + expf(-a));
+          if ((kk & 15) == j) keep[i] = a;
+        }
+        if ((kk & 15) == 15 || kk == nk - 1) {
+          const int kb = kk & ~15;
+          if (kb + j <= kk) {
+#pragma unroll
+            for (int i = 0; i < CF_RPG; ++i)
+              if (ri[i] >= 0) out[ri[i] * stride + k0 + kb + j] = keep[i];
+          }
+        }
+      }
+    }
+  }
+}
+
+// The data half of the backward per row: g[k = c B + b] = q_c Y_b(dirs[r]) (one thread per row of the tile, into LDS), then
+// dh2[r] = sum_k g[k] Wc[k] masked by h2 > 0 (the 16-lane layout, Wc in chunks like the forward), dsig = q_3 softplus'(u) from the
+// cell's own sigma output, group_colsum[r] = the dh2 row as stored.  The block's sums for d_w_sigma and d_b_sigma -> partial[block]
+// ([M | sum, rounding errors], heads_sh_bwd_kernel's format and its compensated pair: sh_bsig_reduce_kernel finishes it).
+template <typename T_, int M, int H2>
+__global__ __launch_bounds__(256) void heads_coef_bwd_kernel(const T_* __restrict__ y, const T_* __restrict__ h2, const float* __restrict__ wc,
+                                                             const float* __restrict__ q, const float* __restrict__ dirs,
+                                                             const float* __restrict__ sigma, long sigma_stride, long n, int deg,
+                                                             T_* __restrict__ dh2, float* __restrict__ dsig, float* __restrict__ colsum,
+                                                             float* __restrict__ partial) {
+  using RY = Row16<T_, M>;
+  using RH = Row16<T_, H2>;
+  __shared__ float wl[CF_KC][16][RH::VPL];
+  __shared__ float gl[CF_TILE][CF_MAXK + 1];
+  __shared__ float dsl[CF_TILE];
+  const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const int B = (deg + 1) * (deg + 1), K3 = 3 * B;
+  float aws[RY::VPL], abs_ = 0.f, abs_lo = 0.f;      // (the pair: threads 0 .. 63, one tile row each)
+#pragma unroll
+  for (int v = 0; v < RY::VPL; ++v) aws[v] = 0.f;
+  const long n_tiles = (n + CF_TILE - 1) / CF_TILE;
+  for (long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    if (threadIdx.x < CF_TILE) {
+      const long r = t * CF_TILE + threadIdx.x;
+      float4 qq = make_float4(0.f, 0.f, 0.f, 0.f);
+      float Y[SH_MAXB];
+      float dsp = 0.f;
+      if (r < n) {
+        qq = *(const float4*)(q + r * 4);
+        sh_basis(deg, dirs[r * 3], dirs[r * 3 + 1], dirs[r * 3 + 2], Y);
+        const float sg = sigma[r * sigma_stride];
+        dsp = qq.w * -expm1f(-sg);            // softplus'(u) = 1 - exp(-softplus(u))
+        dsig[r] = dsp;
+        // the bias term once more in double, carried as a compensated pair (heads_sh_bwd_kernel: signed terms that cancel)
+        const double t_ = (double)qq.w * (1.0 - exp(-(double)sg));
+        const float th_ = (float)t_;
+        float e_;
+        two_sum(abs_, th_, abs_, e_);
+        abs_lo += e_ + (float)(t_ - (double)th_);
+      } else {
+#pragma unroll
+        for (int b = 0; b < SH_MAXB; ++b) Y[b] = 0.f;
+      }
+#pragma unroll
+      for (int b = 0; b < SH_MAXB; ++b) {
+        if (b < B) {
+          gl[threadIdx.x][b] = qq.x * Y[b];
+          gl[threadIdx.x][B + b] = qq.y * Y[b];
+          gl[threadIdx.x][2 * B + b] = qq.z * Y[b];
+        }
+      }
+      dsl[threadIdx.x] = dsp;
+    }
+    __syncthreads();
+    float o[CF_RPG][RH::VPL];
+    unsigned pos[CF_RPG];
+#pragma unroll
+    for (int i = 0; i < CF_RPG; ++i) {
+      const int rr = grp + 16 * i;
+      const long r = t * CF_TILE + rr;
+      const long rc = r < n ? r : n - 1;
+      float yv[RY::VPL], hv[RH::VPL];
+      RY::load(y + rc * M, j, yv);
+      RH::load(h2 + rc * H2, j, hv);
+      const float dsp = dsl[rr];              // (0 for a row past the end)
+      pos[i] = 0u;
+#pragma unroll
+      for (int v = 0; v < RY::VPL; ++v) aws[v] += dsp * yv[v];
+#pragma unroll
+      for (int v = 0; v < RH::VPL; ++v) { o[i][v] = 0.f; pos[i] |= hv[v] > 0.f ? 1u << v : 0u; }
+    }
+    for (int k0 = 0; k0 < K3; k0 += CF_KC) {
+      const int nk = K3 - k0 < CF_KC ? K3 - k0 : CF_KC;
+      __syncthreads();                        // (the previous chunk's readers are done)
+      coef_stage<RH, H2>(wc, k0, nk, wl);
+      __syncthreads();
+#pragma unroll 1
+      for (int kk = 0; kk < nk; ++kk) {
+        float wv[RH::VPL];
+#pragma unroll
+        for (int v = 0; v < RH::VPL; ++v) wv[v] = wl[kk][j][v];
+#pragma unroll
+        for (int i = 0; i < CF_RPG; ++i) {
+          const float gk = gl[grp + 16 * i][k0 + kk];
+#pragma unroll
+          for (int v = 0; v < RH::VPL; ++v) o[i][v] = fmaf(gk, wv[v], o[i][v]);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < CF_RPG; ++i) {
+      const long r = t * CF_TILE + grp + 16 * i;
+      if (r >= n) continue;
+#pragma unroll
+      for (int v = 0; v < RH::VPL; ++v) o[i][v] = (pos[i] >> v) & 1u ? o[i][v] + 0.f : 0.f;      // (+ 0: no -0 from a zero gradient)
+      RH::store(dh2 + r * H2, j, o[i]);
+      if (colsum) {
+        float* cs = colsum + r * H2;
+        if constexpr (sizeof(T_) == 2) {
+#pragma unroll
+          for (int v = 0; v < RH::VPL; v += 2) {          // what the store kept: the values rounded to T_
+            const uint32_t pk = pack_bf16x2(o[i][v], o[i][v + 1]);
+            cs[RH::col(j, v)] = bf16_to_f32((bf16_t)(pk & 0xFFFF));
+            cs[RH::col(j, v + 1)] = bf16_to_f32((bf16_t)(pk >> 16));
+          }
+        } else {
+#pragma unroll
+          for (int v = 0; v < RH::VPL; ++v) cs[RH::col(j, v)] = o[i][v];
+        }
+      }
+    }
+    __syncthreads();                          // (the next tile overwrites gl and dsl)
+  }
+  // block-level reduction of the sigma head's sums, the 16 row groups one after the other, then the 64 pairs in thread order
+  __shared__ float red[M + 2];
+  __shared__ float ph[CF_TILE], pl[CF_TILE];
+  for (int t = threadIdx.x; t < M + 2; t += 256) red[t] = 0.f;
+  if (threadIdx.x < CF_TILE) { ph[threadIdx.x] = abs_; pl[threadIdx.x] = abs_lo; }
+  __syncthreads();
+  for (int gq = 0; gq < 16; ++gq) {
+    if (grp == gq) {
+#pragma unroll
+      for (int v = 0; v < RY::VPL; ++v) red[RY::col(j, v)] += aws[v];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    float S = 0.f, Cc = 0.f;
+    for (int l = 0; l < CF_TILE; ++l) {
+      float e_;
+      two_sum(S, ph[l], S, e_);
+      Cc += e_ + pl[l];
+    }
+    red[M] = S;
+    red[M + 1] = Cc;
+  }
+  __syncthreads();
+  float* part = partial + (size_t)blockIdx.x * (M + 2);
+  for (int t = threadIdx.x; t < M + 2; t += 256) part[t] = red[t];
+}
+
+// The parameter half: d_Wc[k] = sum_r g[r][k] h2[r], d_bc[k] = sum_r g[r][k].  A thread owns one column of h2 and a run of the 3 B
+// outputs k, its accumulators in registers over every tile the block walks (rows ascending); a tile's g rows and h2 rows meet in LDS.
+// partial[block] = [3 B x H2 | 3 B sums | 3 B rounding errors]; ordered_reduce_kernel adds the blocks' weight parts.  The bias sums are
+// few and each is one scalar over every row, signed terms that cancel: like d_b_sigma they are carried as compensated fp32 pairs from
+// the first add to the last (coef_bc_reduce_kernel).  fp32 on the vector pipe.
+constexpr int CW_TILE = 32;
+static int coef_wgrad_blocks(long n) {
+  const long t = (n + CW_TILE - 1) / CW_TILE;
+  return t > 512 ? 512 : (t < 1 ? 1 : (int)t);
+}
+
+template <typename T_, int H2, int DEG>
+__global__ __launch_bounds__(256) void heads_coef_wgrad_kernel(const T_* __restrict__ h2, const float* __restrict__ q,
+                                                               const float* __restrict__ dirs, long n, float* __restrict__ partial) {
+  constexpr int B = (DEG + 1) * (DEG + 1), K3 = 3 * B, KG = 256 / H2, NA = (K3 + KG - 1) / KG, GS = NA * KG;
+  constexpr int EPC = 16 / (int)sizeof(T_), CPR = H2 / EPC;
+  static_assert(KG >= 1 && KG * H2 == 256, "one column per thread");
+  __shared__ float hl[CW_TILE][H2];
+  __shared__ float gl[CW_TILE][GS];
+  const int col = threadIdx.x % H2, kg = threadIdx.x / H2;
+  float acc[NA], accb = 0.f, accb_lo = 0.f;
+#pragma unroll
+  for (int i = 0; i < NA; ++i) acc[i] = 0.f;
+  const long n_tiles = (n + CW_TILE - 1) / CW_TILE;
+  for (long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const long r0 = t * CW_TILE;
+    if (threadIdx.x < CW_TILE) {
+      const long r = r0 + threadIdx.x;
+      float4 qq = make_float4(0.f, 0.f, 0.f, 0.f);
+      float Y[SH_MAXB];
+      if (r < n) {
+        qq = *(const float4*)(q + r * 4);
+        sh_basis(DEG, dirs[r * 3], dirs[r * 3 + 1], dirs[r * 3 + 2], Y);
+      } else {
+#pragma unroll
+        for (int b = 0; b < SH_MAXB; ++b) Y[b] = 0.f;
+      }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        gl[threadIdx.x][b] = qq.x * Y[b];
+        gl[threadIdx.x][B + b] = qq.y * Y[b];
+        gl[threadIdx.x][2 * B + b] = qq.z * Y[b];
+      }
+#pragma unroll
+      for (int k = K3; k < GS; ++k) gl[threadIdx.x][k] = 0.f;
+    }
+    for (int ch = threadIdx.x; ch < CW_TILE * CPR; ch += 256) {
+      const int row = ch / CPR, cc = ch - row * CPR;
+      uint4 u = make_uint4(0u, 0u, 0u, 0u);                 // (rows past the end: zeros)
+      if (r0 + row < n) u = *(const uint4*)(h2 + (r0 + row) * H2 + cc * EPC);
+      float* dst = &hl[row][cc * EPC];
+      if constexpr (sizeof(T_) == 2) {
+        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          dst[2 * i] = bf16_to_f32((bf16_t)(w[i] & 0xFFFF));
+          dst[2 * i + 1] = bf16_to_f32((bf16_t)(w[i] >> 16));
+        }
+      } else {
+        dst[0] = __uint_as_float(u.x); dst[1] = __uint_as_float(u.y); dst[2] = __uint_as_float(u.z); dst[3] = __uint_as_float(u.w);
+      }
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int r = 0; r < CW_TILE; ++r) {
+      const float h = hl[r][col];
+      const float* g = &gl[r][kg * NA];
+#pragma unroll
+      for (int i = 0; i < NA; ++i) acc[i] = fmaf(g[i], h, acc[i]);
+    }
+    if ((int)threadIdx.x < K3) {
+      for (int r = 0; r < CW_TILE; ++r) {
+        float e_;
+        two_sum(accb, gl[r][threadIdx.x], accb, e_);
+        accb_lo += e_;
+      }
+    }
+    __syncthreads();                          // (the next tile overwrites both)
+  }
+  float* part = partial + (size_t)blockIdx.x * (K3 * H2 + 2 * K3);
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int k = kg * NA + i;
+    if (k < K3) part[k * H2 + col] = acc[i];
+  }
+  if ((int)threadIdx.x < K3) {
+    part[K3 * H2 + threadIdx.x] = accb;
+    part[K3 * H2 + K3 + threadIdx.x] = accb_lo;
+  }
+}
+
+// d_b_color[k] += the blocks' pairs (columns off + k and off + K3 + k of partial, row stride np), added in ascending order with two_sum:
+// sh_bsig_reduce_kernel's scheme, one workgroup of one wave per output.  Fixed order: the same bits every run.
+__global__ __launch_bounds__(64) void coef_bc_reduce_kernel(const float* __restrict__ partial, int n_blocks, int np, int off, int K3,
+                                                            float* __restrict__ d_bc) {
+  __shared__ float hi[64], lo[64];
+  const int k = blockIdx.x;
+  const int per = (n_blocks + 63) / 64, b0 = threadIdx.x * per, b1 = n_blocks < b0 + per ? n_blocks : b0 + per;
+  float s = 0.f, c = 0.f;
+  for (int b = b0; b < b1; ++b) {
+    const float* q = partial + (size_t)b * np + off + k;
+    float e_;
+    two_sum(s, q[0], s, e_);
+    c += e_ + q[K3];
+  }
+  hi[threadIdx.x] = s;
+  lo[threadIdx.x] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float S = 0.f, Cc = 0.f;
+    for (int l = 0; l < 64; ++l) {
+      float e_;
+      two_sum(S, hi[l], S, e_);
+      Cc += e_ + lo[l];
+    }
+    float e_;
+    two_sum(d_bc[k], S, S, e_);
+    d_bc[k] = S + (Cc + e_);
+  }
+}
+
+// the two parts of swn_heads_coef_bwd's workspace, each a multiple of 64 floats: sized by the block counts, which are capped
+struct CoefWs { size_t sig, wg; };
+static CoefWs coef_ws(long n, int model_dim, int h2_dim, int deg) {
+  const int B = (deg + 1) * (deg + 1);
+  auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+  CoefWs w;
+  w.sig = up((size_t)coef_blocks(n) * (size_t)(model_dim + 2));
+  w.wg = up((size_t)coef_wgrad_blocks(n) * (size_t)(3 * B * h2_dim + 6 * B));
+  return w;
+}
+
 }  // namespace swn
 
 using namespace swn;
@@ -596,6 +1018,108 @@ extern "C" int swn_cells_blend_sh(const float* weights, const int32_t* slot, con
     default: SWN_BSH(4); break;
   }
 #undef SWN_BSH
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cells_blend_sh_bwd(const float* weights, const int32_t* rows, const int32_t* begin, const float* raw, const float* d_raw,
+                                      const float* dirs, const float* sub_out, long total, int rows_per_group, int deg, int n_points,
+                                      int n_cells, int hard, float* q, float* dirs_packed, void* stream) {
+  SWN_CHECK(n_cells >= 1 && n_cells <= BSH_MAX_CELLS, "swn_cells_blend_sh_bwd: n_cells %d outside [1, %d]", n_cells, BSH_MAX_CELLS);
+  SWN_CHECK(deg >= 0 && deg <= 4, "swn_cells_blend_sh_bwd: deg %d outside 0..4", deg);
+  SWN_CHECK(rows_per_group >= 1, "swn_cells_blend_sh_bwd: rows_per_group %d < 1", rows_per_group);
+  SWN_CHECK(n_points >= 1 && total >= 0, "swn_cells_blend_sh_bwd: bad sizes (n_points %d, total %ld)", n_points, total);
+  SWN_CHECK(n_points % rows_per_group == 0, "swn_cells_blend_sh_bwd: n_points %d is no multiple of rows_per_group %d", n_points, rows_per_group);
+  SWN_CHECK(rows && raw && d_raw && dirs && q && dirs_packed && (hard || (weights && begin)) && (deg != 0 || sub_out),
+            "swn_cells_blend_sh_bwd: null pointer");      // (sub_out is read at degree 0 only)
+  if (total == 0) return 0;
+  SWN_CHECK(((((uintptr_t)raw) | ((uintptr_t)d_raw) | ((uintptr_t)q) | (deg == 0 ? (uintptr_t)sub_out : 0)) & 15) == 0,
+            "swn_cells_blend_sh_bwd: raw, d_raw, q (deg 0: sub_out too) must be 16-byte aligned");
+  SWN_CHECK(total <= 2147483647l * 256, "swn_cells_blend_sh_bwd: %ld rows exceed the grid", total);      // (cdiv returns an int)
+  hipLaunchKernelGGL(cells_blend_sh_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), weights, rows, begin, raw, d_raw,
+                     dirs, sub_out, total, rows_per_group, n_cells, hard, deg, (long)n_points, q, dirs_packed);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_heads_coef_fwd(const void* y, const void* h2, int dtype, const float* w_sigma, const float* b_sigma, const float* w_color,
+                                  const float* b_color, const float* sigma_noise, int deg, int inner_sigmoid, int n_rows, int model_dim,
+                                  int h2_dim, float* out, long out_stride, void* stream) {
+  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "swn_heads_coef_fwd: bad dtype");
+  SWN_CHECK((model_dim == 256 || model_dim == 512) && (h2_dim == 128 || h2_dim == 256),
+            "swn_heads_coef_fwd: model_dim in {256,512}, h2_dim in {128,256}");
+  SWN_CHECK(deg >= 0 && deg <= 4, "swn_heads_coef_fwd: deg %d outside 0..4", deg);
+  SWN_CHECK(!inner_sigmoid || deg == 0, "swn_heads_coef_fwd: the inner sigmoid belongs to degree 0 (rgb_dim == 3), not to deg %d", deg);
+  SWN_CHECK(n_rows >= 0 && out_stride >= 3 * (deg + 1) * (deg + 1) + 1, "swn_heads_coef_fwd: bad sizes (n_rows %d, out_stride %ld)", n_rows,
+            out_stride);
+  SWN_CHECK(y && h2 && w_sigma && b_sigma && w_color && b_color && out, "swn_heads_coef_fwd: null pointer");
+  if (n_rows == 0) return 0;
+  const int blocks = coef_blocks(n_rows);
+#define SWN_CFF(T_, M_, H_) hipLaunchKernelGGL((heads_coef_fwd_kernel<T_, M_, H_>), dim3(blocks), dim3(256), 0, as_stream(stream), (const T_*)y, \
+                                               (const T_*)h2, w_sigma, b_sigma, w_color, b_color, sigma_noise, deg, inner_sigmoid ? 1 : 0,       \
+                                               (long)n_rows, out, out_stride)
+  SWN_SH_DISPATCH(SWN_CFF);
+#undef SWN_CFF
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_heads_coef_bwd_workspace_bytes(int n_rows, int model_dim, int h2_dim, int deg, size_t* bytes) {
+  SWN_CHECK(bytes && n_rows >= 0 && deg >= 0 && deg <= 4 && model_dim > 0 && h2_dim > 0, "swn_heads_coef_bwd_workspace_bytes: bad arguments");
+  const CoefWs w = coef_ws(n_rows, model_dim, h2_dim, deg);
+  *bytes = (w.sig + w.wg) * sizeof(float);
+  return 0;
+}
+
+template <typename T_, int H2>
+static void coef_wgrad_launch(int deg, int blocks, hipStream_t s, const void* h2, const float* q, const float* dirs, long n, float* partial) {
+  switch (deg) {
+    case 0: hipLaunchKernelGGL((heads_coef_wgrad_kernel<T_, H2, 0>), dim3(blocks), dim3(256), 0, s, (const T_*)h2, q, dirs, n, partial); break;
+    case 1: hipLaunchKernelGGL((heads_coef_wgrad_kernel<T_, H2, 1>), dim3(blocks), dim3(256), 0, s, (const T_*)h2, q, dirs, n, partial); break;
+    case 2: hipLaunchKernelGGL((heads_coef_wgrad_kernel<T_, H2, 2>), dim3(blocks), dim3(256), 0, s, (const T_*)h2, q, dirs, n, partial); break;
+    case 3: hipLaunchKernelGGL((heads_coef_wgrad_kernel<T_, H2, 3>), dim3(blocks), dim3(256), 0, s, (const T_*)h2, q, dirs, n, partial); break;
+    default: hipLaunchKernelGGL((heads_coef_wgrad_kernel<T_, H2, 4>), dim3(blocks), dim3(256), 0, s, (const T_*)h2, q, dirs, n, partial); break;
+  }
+}
+
+extern "C" int swn_heads_coef_bwd(const void* y, const void* h2, int dtype, const float* w_color, const float* q, const float* dirs,
+                                  const float* sigma, long sigma_stride, int n_rows, int model_dim, int h2_dim, int deg, void* dh2,
+                                  float* dsig, float* d_w_sigma, float* d_b_sigma, float* d_w_color, float* d_b_color, float* group_colsum,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  SWN_CHECK(dtype == SWN_F32 || dtype == SWN_HALF, "swn_heads_coef_bwd: bad dtype");
+  SWN_CHECK((model_dim == 256 || model_dim == 512) && (h2_dim == 128 || h2_dim == 256),
+            "swn_heads_coef_bwd: model_dim in {256,512}, h2_dim in {128,256}");
+  SWN_CHECK(deg >= 0 && deg <= 4, "swn_heads_coef_bwd: deg %d outside 0..4", deg);
+  SWN_CHECK(n_rows >= 0 && sigma_stride >= 1, "swn_heads_coef_bwd: bad sizes (n_rows %d, sigma_stride %ld)", n_rows, sigma_stride);
+  SWN_CHECK(y && h2 && w_color && q && dirs && sigma && dh2 && dsig && d_w_sigma && d_b_sigma && d_w_color && d_b_color && workspace,
+            "swn_heads_coef_bwd: null pointer");      // (group_colsum may be NULL)
+  SWN_CHECK((((uintptr_t)q) & 15) == 0, "swn_heads_coef_bwd: q must be 16-byte aligned");
+  const CoefWs w = coef_ws(n_rows, model_dim, h2_dim, deg);
+  SWN_CHECK(workspace_bytes >= (w.sig + w.wg) * sizeof(float), "swn_heads_coef_bwd: workspace of %zu bytes, need %zu", workspace_bytes,
+            (w.sig + w.wg) * sizeof(float));
+  if (n_rows == 0) return 0;
+  const int B = (deg + 1) * (deg + 1), blocks = coef_blocks(n_rows), nb2 = coef_wgrad_blocks(n_rows);
+  float* p_sig = (float*)workspace;
+  float* p_wg = p_sig + w.sig;
+#define SWN_CFB(T_, M_, H_) hipLaunchKernelGGL((heads_coef_bwd_kernel<T_, M_, H_>), dim3(blocks), dim3(256), 0, as_stream(stream), (const T_*)y, \
+                                               (const T_*)h2, w_color, q, dirs, sigma, sigma_stride, (long)n_rows, deg, (T_*)dh2, dsig,          \
+                                               group_colsum, p_sig)
+  SWN_SH_DISPATCH(SWN_CFB);
+#undef SWN_CFB
+  OrdDst od{{d_w_sigma, nullptr, nullptr, nullptr}, {model_dim, 0, 0, 0}};      // (the two columns behind it go to no destination here)
+  ordered_reduce_async(p_sig, blocks, model_dim + 2, od, true, as_stream(stream));
+  hipLaunchKernelGGL(sh_bsig_reduce_kernel, dim3(1), dim3(64), 0, as_stream(stream), p_sig, blocks, model_dim, d_b_sigma);
+  if (dtype == SWN_HALF) {
+    if (h2_dim == 128) coef_wgrad_launch<bf16_t, 128>(deg, nb2, as_stream(stream), h2, q, dirs, n_rows, p_wg);
+    else coef_wgrad_launch<bf16_t, 256>(deg, nb2, as_stream(stream), h2, q, dirs, n_rows, p_wg);
+  } else {
+    if (h2_dim == 128) coef_wgrad_launch<float, 128>(deg, nb2, as_stream(stream), h2, q, dirs, n_rows, p_wg);
+    else coef_wgrad_launch<float, 256>(deg, nb2, as_stream(stream), h2, q, dirs, n_rows, p_wg);
+  }
+  OrdDst oc{{d_w_color, nullptr, nullptr, nullptr}, {3 * B * h2_dim, 0, 0, 0}};      // (the bias columns behind it go to no destination here)
+  ordered_reduce_async(p_wg, nb2, 3 * B * h2_dim + 6 * B, oc, true, as_stream(stream));
+  hipLaunchKernelGGL(coef_bc_reduce_kernel, dim3(3 * B), dim3(64), 0, as_stream(stream), p_wg, nb2, 3 * B * h2_dim + 6 * B, 3 * B * h2_dim,
+                     3 * B, d_b_color);
   SWN_LAUNCH_CHECK();
   return 0;
 }

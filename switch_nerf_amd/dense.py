@@ -193,7 +193,7 @@ class DenseNeRF(SwitchNeRF):
         W, L, H2, s = self.M, self.L, self.H2, self.skip_l
         c = dict(N=N, S=S, P=P, n_seg=max(1, P // seg_tokens), seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
         c["pe"], c["pe_dir"] = pe, pe_dir
-        if self.sh_deg is not None:
+        if self.sh_deg is not None and self._coef_out is None:      # (forward_coef: the basis enters behind the cells' blend, not here)
             d = self._sh_dirs
             if d is None or d.shape != (N, 3) or d.dtype != torch.float32:
                 raise NotImplementedError("sh_deg: the directions of this pass are missing - only forward_rays / forward_hier / __call__ "
@@ -231,7 +231,12 @@ class DenseNeRF(SwitchNeRF):
         S, P = c["S"], c["P"]
         W, L, H2, s = self.M, self.L, self.H2, self.skip_l
         g, acts, masks = self.g, c["acts"], c["masks"]
-        if self.sh_deg is not None:
+        if c.get("coef_rows") is not None:      # forward_coef's context: d_raw is q [P, 4], one direction per row in c["coef_dirs"]
+            if c.get("coef_dirs") is None:
+                raise RuntimeError("a forward_coef context needs c['coef_dirs'] [P, 3] (ops.cells_blend_sh_bwd's directions) for its backward")
+            dh2, dsig, dc_ray = o.heads_coef_bwd(c["y"], c["h2"], self.p["color.w"], d_raw, c["coef_dirs"], c["coef_rows"], g["sigma.w"],
+                                                 g["sigma.b"], g["color.w"], g["color.b"], self.sh_deg)
+        elif self.sh_deg is not None:
             dh2, dsig, dc_ray = o.heads_sh_bwd(c["y"], c["h2"], self.p["color.w"], self.p["color.b"], c["sh_dirs"], c["raw"], d_raw,
                                                g["sigma.w"], g["sigma.b"], g["color.w"], g["color.b"], S, self.sh_deg)
         else:
@@ -314,6 +319,31 @@ class DenseNeRF(SwitchNeRF):
         pe = torch.zeros(P, self.KP, dtype=self.dtype, device=self.dev)
         pe[:, : self.in_xyz] = enc.to(self.dtype)
         return pe
+
+    def forward_coef(self, x, sigma_noise, out, inner_sigmoid: bool = False, tag: str = "c"):
+        """The SAVING training forward of a spherical-harmonics model over explicit points, for a Mega-NeRF cell: x [n, 3 + 1] (position,
+        image index) -> ctx; the heads write the raw rows (3 B coefficients, sigma; swn_heads_coef_fwd) into `out` [n, 3 B + 1] fp32 (a
+        row-contiguous view, e.g. the cell's slice of the packed rows) - no basis is evaluated: the reference evaluates it on the blend
+        of the cells' rows.  inner_sigmoid (degree 0): sigmoid on the three colour outputs (models/nerf.py:140-141).  backward_net(ctx,
+        q) continues from ops.cells_blend_sh_bwd's q with ctx["coef_dirs"] set to its directions."""
+        if self.sh_deg is None:
+            raise NotImplementedError("forward_coef is the spherical-harmonics form (cfg['sh_deg'])")
+        if self.xyz_dim != 3 or self.dtype == torch.float16:
+            raise NotImplementedError("forward_coef: xyz_dim 3 and bfloat16 / float32 only")
+        if inner_sigmoid and self.sh_deg != 0:
+            raise ValueError("inner_sigmoid belongs to sh_deg 0 (rgb_dim == 3)")
+        if x.dim() != 2 or x.shape[1] != 4:
+            raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(tuple(x.shape), 4, self.xyz_dim))
+        n = x.shape[0]
+        xf = x.to(torch.float32)
+        rays = torch.cat([xf[:, :3], torch.zeros(n, 5, device=self.dev)], 1).contiguous()      # o = xyz, d = 0, z = 0 -> the sample IS the point
+        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
+        self._coef_out = (out, bool(inner_sigmoid))
+        try:
+            c = self.forward_rays(rays, xf[:, 3].long().contiguous(), 1, n, 0.0, None, noise, training=True, tag=tag, composite=False)
+        finally:
+            self._coef_out = None
+        return c
 
     _sh_want_coef = False    # inside _call_sh: the heads' launch also leaves the colour head's linear outputs (c["coef"])
 

@@ -32,9 +32,22 @@ the library's sampling, compositing, loss and Adam around it like SwitchNeRF.tra
 sort-merge).  A cell that no point reached in a step keeps a ZERO gradient, not a missing one (the reference's joint_training branch,
 mega_nerf.py:51-59), so Adam still advances it.  What training costs here and does not hide: every cell runs its own launch sequence, and
 a cell's rows are not whole rays, so the per-ray feature and the head backward run per point (rows_per_group 1).
-Not built for training (each raises NotImplementedError): spherical-harmonics cells (swn_cells_blend_sh has no backward), the xyz_real
-background half, fp16 cells (one loss scale over K models), seeded device noise, graph capture (counts.tolist() sizes the ragged calls),
-expert / data parallelism, and rendering.render_rays on a model in training mode (the autograd bridge for a MegaNeRF is a later change).
+
+Training cells with spherical-harmonics colour (--train_mega_nerf with --sh_deg: the cells that bake into an octree) is a second opt-in,
+MegaNeRF(..., joint_training=True, sh_training=True).  The reference blends the cells' raw [3 B + 1] rows and evaluates the basis on the
+blend (rendering.py:344-347), so the basis is no part of a cell:
+
+    c_i = sub_modules[i].forward_coef(rows of cell i, ..)      the heads write (3 B coefficients, sigma) into the cell's slice (swn_heads_coef_fwd)
+    out = ops.cells_blend_sh(weights, slot, begin, sub_out, dirs, rows_per_group, deg, hard)      the inference kernel: blend, eval_sh, sigmoid
+    q, dirs_packed = ops.cells_blend_sh_bwd(.., out, d_out, dirs, ..)                              its adjoint, factored: d_lin[c B + b] = q_c Y_b
+    sub_modules[i].backward_net(c_i, q[begin[i]:begin[i + 1]])                                     swn_heads_coef_bwd, then the cell's backward
+
+The [total, 3 B + 1] gradient is never written.  The points carry no direction columns ([P, 3 + 1]); one direction serves the
+rows_per_group samples of a ray.  At degree 0 a cell's row holds sigmoid(lin) and the blend's evaluation puts a second sigmoid on it,
+as in inference.
+Not built for training (each raises NotImplementedError): the xyz_real background half, fp16 cells (one loss scale over K models), seeded
+device noise, graph capture (counts.tolist() sizes the ragged calls), expert / data parallelism, and rendering.render_rays on a model in
+training mode (the autograd bridge for a MegaNeRF is a later change).
 """
 from __future__ import annotations
 
@@ -96,12 +109,14 @@ class MegaNeRF:
     is_mega_nerf = True      # what rendering.render_rays dispatches on (no import of this module on the other models' path)
 
     def __init__(self, sub_modules: Sequence[DenseNeRF], centroids, boundary_margin: float, xyz_real: bool, cluster_2d: bool,
-                 joint_training: bool = False):
+                 joint_training: bool = False, sh_training: bool = False):
         """sub_modules: one DenseNeRF per cell (xyz_dim 4 with xyz_real, the background model; 3 otherwise), all of one compute dtype;
         they are put into evaluation mode.  centroids [K, 3].  Attributes as rendering.py:52-53 reads them.
         joint_training (mega_nerf.py:9, the reference's last constructor argument): the model trains through its cells (forward_points /
         backward_points / train_step); model and cells then start in training mode like a fresh nn.Module, and train() / eval() switch
-        every cell.  The learning rate and the step count are the model's own (taken from the first cell), shared by every cell."""
+        every cell.  The learning rate and the step count are the model's own (taken from the first cell), shared by every cell.
+        sh_training: with joint_training, cells with spherical-harmonics colour train too (forward_points then takes the directions);
+        without it such cells are refused, as before."""
         assert boundary_margin >= 1                              # mega_nerf.py:11
         sub_modules = list(sub_modules)
         cen = centroids if torch.is_tensor(centroids) else torch.from_numpy(np.asarray(centroids))
@@ -130,6 +145,7 @@ class MegaNeRF:
         self.xyz_dim = xd
         self.cluster_dim_start = 1 if cluster_2d else 0
         self.joint_training = bool(joint_training)
+        self.sh_training = bool(sh_training)
         self.training = False
         self.moe_no_batch = False
         if self.joint_training:
@@ -142,9 +158,10 @@ class MegaNeRF:
 
     def _check_trainable(self):
         """What training through the cells does not build, named at construction."""
-        if self.sh_deg is not None:
-            raise NotImplementedError("joint_training with spherical-harmonics cells (sh_deg) is not built: their blend is "
-                                      "swn_cells_blend_sh, which has no backward")
+        if self.sh_deg is not None and not self.sh_training:
+            raise NotImplementedError("joint_training with spherical-harmonics cells (sh_deg) is opt-in - pass sh_training=True (the "
+                                      "cells then emit their coefficient rows, swn_heads_coef_fwd, and the blend swn_cells_blend_sh runs "
+                                      "backward through swn_cells_blend_sh_bwd; forward_points takes the ray directions)")
         if self.xyz_real:
             raise NotImplementedError("joint_training with xyz_real (the background half) is not built: it needs BackgroundScene's "
                                       "bounded compositing backward around the cells")
@@ -163,9 +180,10 @@ class MegaNeRF:
     # ------------------------------------------------------------------------------------------ construction
     @classmethod
     def from_state_dicts(cls, state_dicts, centroids, cfg: Optional[dict] = None, boundary_margin: float = 1.15, xyz_real: bool = False,
-                         cluster_2d: bool = False, dtype=torch.float32, device="cuda", joint_training: bool = False) -> "MegaNeRF":
+                         cluster_2d: bool = False, dtype=torch.float32, device="cuda", joint_training: bool = False,
+                         sh_training: bool = False) -> "MegaNeRF":
         """One DenseNeRF per reference-NeRF state_dict (DenseNeRF.load_state_dict takes that key layout); cfg None: derived from the
-        tensor shapes of each state_dict.  joint_training: the constructor's."""
+        tensor shapes of each state_dict.  joint_training, sh_training: the constructor's."""
         xd = 4 if xyz_real else 3
         subs = []
         for sd in state_dicts:
@@ -173,7 +191,7 @@ class MegaNeRF:
             m = DenseNeRF(c, dtype=dtype, device=device)
             m.load_state_dict(sd)
             subs.append(m)
-        return cls(subs, centroids, boundary_margin, xyz_real, cluster_2d, joint_training)
+        return cls(subs, centroids, boundary_margin, xyz_real, cluster_2d, joint_training, sh_training)
 
     @classmethod
     def from_container(cls, path, boundary_margin: float = 1.15, background: bool = False, dtype=torch.float32,
@@ -310,19 +328,32 @@ class MegaNeRF:
         return weights, slot, begin, sub_out, hard
 
     # ------------------------------------------------------------------------------------------ training through the cells
-    def forward_points(self, x, sigma_noise=None, tag: str = "c"):
+    def forward_points(self, x, sigma_noise=None, tag: str = "c", dirs=None, rows_per_group: int = 1):
         """The training form of __call__: x [P, 3 + 3 + 1] -> ctx with ctx["out"] [P, 4] and what backward_points needs.  Every non-empty
         cell runs a SAVING forward on its packed rows (DenseNeRF.forward_rays on one-sample rays, as DenseNeRF.__call__ does), so a cell
         holds ONE live context per tag: a second forward_points under the same tag overwrites the first one's saved activations (the
-        hierarchical step runs its fine pass under tag "f")."""
+        hierarchical step runs its fine pass under tag "f").
+        Cells with sh_deg (sh_training): x [P, 3 + 1] (no direction columns) and dirs [P / rows_per_group, 3], point p seen along
+        dirs[p // rows_per_group] (not normalised), the training form of call_rgb: ctx["out"] = (sigmoid(eval_sh(blended coefficients,
+        direction)), blended sigma)."""
         self._need_joint("forward_points")
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError("MegaNeRF: graph capture is not built - counts.tolist() sizes the ragged per-cell calls on the host")
-        if x.dim() != 2 or x.shape[1] != 7:
-            raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(tuple(x.shape), 7, self.xyz_dim))
+        sh = self.sh_deg is not None
+        width = 4 if sh else 7
+        if x.dim() != 2 or x.shape[1] != width:
+            raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(tuple(x.shape), width, self.xyz_dim))
         P = x.shape[0]
         if P == 0:
             raise ValueError("MegaNeRF.forward_points: no points")
+        if sh:
+            rpg = int(rows_per_group)
+            if dirs is None or rpg < 1 or P % rpg or tuple(dirs.shape) != (P // rpg, 3):
+                raise ValueError(f"forward_points: cells with sh_deg need dirs [{P} / rows_per_group, 3] (got "
+                                 f"{None if dirs is None else tuple(dirs.shape)}, rows_per_group {rows_per_group})")
+            dirs = dirs.to(torch.float32).contiguous()
+        elif dirs is not None:
+            raise ValueError("forward_points: dirs belong to cells with sh_deg; these points carry their direction columns")
         x = x.to(torch.float32).contiguous()
         noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
         hard = self.boundary_margin == 1
@@ -332,6 +363,8 @@ class MegaNeRF:
         if total == 0:
             raise ValueError("MegaNeRF: no point belongs to a cell - the positions are not finite")
         xin, nin = ops.cells_gather(x, rows, total, 0, noise)
+        if sh:
+            return self._forward_points_sh(xin, nin, dirs, rpg, weights, rows, begin, slot, n, total, hard, P, tag)
         rays = torch.cat([xin[:, :6], torch.zeros(total, 2, device=self.dev)], 1)      # o = xyz, near = far = 0 -> the sample IS the point
         img = xin[:, 6].long()
         sub_out = torch.empty(total, 4, dtype=torch.float32, device=self.dev)
@@ -348,12 +381,40 @@ class MegaNeRF:
         out = ops.cells_blend(weights, slot, begin, sub_out, hard)
         return dict(out=out, weights=weights, rows=rows, begin=begin, slot=slot, cells=cells, counts=n, total=total, hard=hard, P=P, tag=tag)
 
+    def _forward_points_sh(self, xin, nin, dirs, rpg, weights, rows, begin, slot, n, total, hard, P, tag):
+        """forward_points behind the gather for cells with sh_deg: each cell's heads write its slice of the packed rows, the inference
+        blend kernel evaluates the basis on the blend."""
+        deg = self.sh_deg
+        sub_out = torch.empty(total, self.n_out, dtype=torch.float32, device=self.dev)
+        cells, b = [], 0
+        for i, child in enumerate(self.sub_modules):
+            c = None
+            if n[i] > 0:
+                sl = slice(b, b + n[i])      # (degree 0: the reference NeRF's own sigmoid on its three outputs, as _sub_outputs)
+                c = child.forward_coef(xin[sl], None if nin is None else nin[sl], sub_out[sl], deg == 0, tag)
+            cells.append(c)
+            b += n[i]
+        out = ops.cells_blend_sh(weights, slot, begin, sub_out, dirs, rpg, deg, hard)
+        return dict(out=out, weights=weights, rows=rows, begin=begin, slot=slot, cells=cells, counts=n, total=total, hard=hard, P=P, tag=tag,
+                    sub_out=sub_out, dirs=dirs, rows_per_group=rpg)
+
     def backward_points(self, ctx, d_out):
         """Backward of forward_points given dL/d out [P, 4]: the blend's adjoint (ops.cells_blend_bwd), then every non-empty cell's
         backward_net on its rows - accumulated into that cell's gradient (nothing is zeroed here)."""
         self._need_joint("backward_points")
         if tuple(d_out.shape) != (ctx["P"], 4):
             raise ValueError(f"backward_points: d_out {tuple(d_out.shape)} for an output of [{ctx['P']}, 4]")
+        if self.sh_deg is not None:      # the factored adjoint: q [total, 4] and one direction per packed row cross to the cells
+            q, dp = ops.cells_blend_sh_bwd(ctx["weights"], ctx["rows"], ctx["begin"], ctx["out"], d_out.to(torch.float32).contiguous(),
+                                           ctx["dirs"], ctx["rows_per_group"], self.sh_deg, ctx["total"], ctx["hard"],
+                                           ctx["sub_out"] if self.sh_deg == 0 else None)
+            b = 0
+            for child, c, n in zip(self.sub_modules, ctx["cells"], ctx["counts"]):
+                if n > 0:
+                    c["coef_dirs"] = dp[b:b + n]
+                    child.backward_net(c, q[b:b + n], None)
+                b += n
+            return
         d_sub = ops.cells_blend_bwd(ctx["weights"], ctx["rows"], ctx["begin"], d_out.to(torch.float32).contiguous(), ctx["total"], ctx["hard"])
         b = 0
         for child, c, n in zip(self.sub_modules, ctx["cells"], ctx["counts"]):
@@ -377,7 +438,9 @@ class MegaNeRF:
         if perturb != 0 and perturb_rand is None:
             perturb_rand = torch.rand(N, S, device=self.dev)
         z = o.sample_z(rays, lin(S), perturb_rand if perturb != 0 else None, perturb, S)
-        c = self.forward_points(_points(rays, z, image_indices), sigma_noise, "c")
+        sh = self.sh_deg is not None          # (sh_deg: no direction columns, one direction per ray: rendering.py:316-330)
+        dirs = rays[:, 3:6].contiguous() if sh else None
+        c = self.forward_points(_points(rays, z, image_indices, not sh), sigma_noise, "c", dirs, S)
         raw = c["out"]
         if F == 0:
             cf = None
@@ -388,7 +451,7 @@ class MegaNeRF:
             if fine_u is None:                                 # det = (perturb == 0): linspace, else rand (rendering.py:605-609)
                 fine_u = lin(F).expand(N, F).contiguous() if perturb == 0 else torch.rand(N, F, device=self.dev)
             z_fine = o.sample_pdf(z, w, fine_u, F)
-            cf = self.forward_points(_points(rays, z_fine, image_indices), sigma_noise_fine, "f")
+            cf = self.forward_points(_points(rays, z_fine, image_indices, not sh), sigma_noise_fine, "f", dirs, F)
             zm, order, raw_m = o.merge_samples(z_fine, z, cf["out"], raw)
             out = dict(raw=raw_m, z=zm, order=order, z_fine=z_fine)
             out["rgb"], out["depth"], out["depth_variance"], _ = o.composite_fwd(raw_m, zm)

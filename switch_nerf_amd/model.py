@@ -507,6 +507,7 @@ class SwitchNeRF:
     # ------------------------------------------------------------------------------------------ buffers
     affine = False          # cfg["affine_appearance"]: the per-image affine colour transform (set by _configure)
     sh_deg = None           # cfg["sh_deg"]: spherical-harmonics colour of that degree (DenseNeRF only; set by its _configure)
+    _coef_out = None        # inside DenseNeRF.forward_coef: (the [n, 3 B + 1] rows the heads write, inner sigmoid)
     _saving = True          # False inside an inference forward: the chains skip the activation saves and ReLU masks
     hash = None             # multiresolution hash-grid input encoding (cfg["hash"]) or None
     _grow_bufs = False      # True: one buffer per name, grown to the largest row count seen (row counts that vary per step)
@@ -1048,6 +1049,9 @@ class SwitchNeRF:
         if self.affine:    # ---- heads + the per-image colour transform (models/nerf_moe.py:436-438) as their own launch
             c["raw"] = o.heads_affine_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                           sigma_noise, *c["aff_rows"])
+        elif self._coef_out is not None:   # ---- a Mega-NeRF cell training with sh_deg (DenseNeRF.forward_coef): the coefficient row itself
+            c["coef_rows"] = o.heads_coef_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
+                                              sigma_noise, self.sh_deg, *self._coef_out)
         elif self.sh_deg is not None:      # ---- heads + the spherical-harmonics contraction against the ray's direction (rendering.py:344-347)
             out = o.heads_sh_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                  sigma_noise, c["sh_dirs"], rows_per_bias, self.sh_deg, want_coef=self._sh_want_coef)

@@ -42,6 +42,12 @@ def _p(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr())
 
 
+def _pv(t: torch.Tensor):
+    """The address of a strided VIEW (the entry point takes its row stride): the caller has checked the layout."""
+    assert t.is_cuda
+    return C.c_void_p(t.data_ptr())
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -1091,6 +1097,68 @@ def cells_blend_sh(weights, slot, begin, sub_out, dirs, rows_per_group: int, deg
     call("swn_cells_blend_sh", _p(weights), _p(slot), _p(begin), _p(sub_out), total, _p(dirs), rows_per_group, deg, P, K,
          1 if hard else 0, _p(raw), _p(coef), _stream())
     return (raw, coef) if want_coef else raw
+
+
+def cells_blend_sh_bwd(weights, rows, begin, raw, d_raw, dirs, rows_per_group: int, deg: int, total: int, hard: bool, sub_out=None):
+    """The adjoint of cells_blend_sh with respect to sub_out, factored (swn_cells_blend_sh_bwd) -> (q [total, 4], dirs_packed [total, 3]):
+    d_lin[r][c B + b] = q[r][c] Y_b(dirs_packed[r]), d_sigma[r] = q[r][3].  raw: cells_blend_sh's output [P, 4]; sub_out [total, 4]: the
+    packed rows, needed at degree 0 (the cells' own sigmoid).  The library checks deg, rows_per_group and the sizes."""
+    P, K = weights.shape
+    total, rows_per_group, deg = int(total), int(rows_per_group), int(deg)
+    assert weights.dtype == raw.dtype == d_raw.dtype == dirs.dtype == torch.float32 and rows.dtype == begin.dtype == torch.int32
+    assert tuple(raw.shape) == tuple(d_raw.shape) == (P, 4) and 0 <= total <= rows.numel() and begin.numel() == K + 1
+    assert all(t.is_contiguous() for t in (weights, rows, begin, raw, d_raw, dirs))
+    if rows_per_group >= 1 and P % rows_per_group == 0:      # (otherwise: the library's error)
+        assert tuple(dirs.shape) == (P // rows_per_group, 3)
+    if sub_out is not None:
+        assert sub_out.dtype == torch.float32 and sub_out.is_contiguous() and (deg != 0 or tuple(sub_out.shape) == (total, 4))
+    q = torch.empty(total, 4, dtype=torch.float32, device=weights.device)
+    dp = torch.empty(total, 3, dtype=torch.float32, device=weights.device)
+    call("swn_cells_blend_sh_bwd", _p(weights), _p(rows), _p(begin), _p(raw), _p(d_raw), _p(dirs), _p(sub_out), total, rows_per_group, deg, P, K,
+         1 if hard else 0, _p(q), _p(dp), _stream())
+    return q, dp
+
+
+def heads_coef_fwd(y, h2, w_sigma, b_sigma, w_color, b_color, sigma_noise, deg: int, out, inner_sigmoid: bool = False):
+    """A cell's heads over packed rows (swn_heads_coef_fwd): out [n, 3 B + 1] f32 - a row-contiguous view, e.g. the cell's slice of the
+    packed sub_out - receives (h2 Wc^T + bc, softplus(..)); inner_sigmoid (degree 0): sigmoid on the three colour outputs.  -> out."""
+    n, M = y.shape
+    H2 = h2.shape[1]
+    B = (int(deg) + 1) ** 2
+    assert w_color.shape == (3 * B, H2) and b_color.numel() == 3 * B and all(t.dtype == torch.float32 and t.is_contiguous() for t in (w_color, b_color))
+    assert out.dtype == torch.float32 and tuple(out.shape) == (n, 3 * B + 1) and out.stride(1) == 1 and (n <= 1 or out.stride(0) >= 3 * B + 1)
+    assert sigma_noise is None or (sigma_noise.dtype == torch.float32 and sigma_noise.numel() == n and sigma_noise.is_contiguous())
+    call("swn_heads_coef_fwd", _p(y), _p(h2), _dt(y), _p(w_sigma), _p(b_sigma), _p(w_color), _p(b_color), _p(sigma_noise), int(deg),
+         1 if inner_sigmoid else 0, n, M, H2, _pv(out), out.stride(0) if n > 1 else 3 * B + 1, _stream())
+    return out
+
+
+def heads_coef_bwd_workspace_bytes(n: int, M: int, H2: int, deg: int) -> int:
+    nb = C.c_size_t(0)
+    call("swn_heads_coef_bwd_workspace_bytes", int(n), int(M), int(H2), int(deg), C.byref(nb))
+    return int(nb.value)
+
+
+def heads_coef_bwd(y, h2, w_color, q, dirs, rows_out, d_w_sigma, d_b_sigma, d_w_color, d_b_color, deg: int, want_colsum: bool = True):
+    """The backward of heads_coef_fwd (swn_heads_coef_bwd) from q [n, 4], dirs [n, 3] (cells_blend_sh_bwd's, a cell's slice) and rows_out
+    [n, 3 B + 1] = what heads_coef_fwd wrote (its sigma column is read) -> (dh2, dsig, colsum [n, H2] f32 or None); the four parameter
+    gradients are accumulated."""
+    n, H2 = h2.shape
+    M = d_w_sigma.numel()
+    B = (int(deg) + 1) ** 2
+    assert w_color.shape == (3 * B, H2) and w_color.dtype == torch.float32 and w_color.is_contiguous()
+    assert d_w_color.numel() == 3 * B * H2 and d_b_color.numel() == 3 * B and y is not None
+    assert q.dtype == dirs.dtype == rows_out.dtype == torch.float32 and tuple(q.shape) == (n, 4) and tuple(dirs.shape) == (n, 3)
+    assert q.is_contiguous() and dirs.is_contiguous() and tuple(rows_out.shape) == (n, 3 * B + 1) and rows_out.stride(1) == 1
+    dh2 = torch.empty_like(h2)
+    dsig = torch.empty(n, dtype=torch.float32, device=h2.device)
+    nb = heads_coef_bwd_workspace_bytes(n, M, H2, deg)
+    ws = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=h2.device)
+    cs = torch.empty(n, H2, dtype=torch.float32, device=h2.device) if want_colsum else None
+    sig = rows_out[:, 3 * B]
+    call("swn_heads_coef_bwd", _p(y), _p(h2), _dt(h2), _p(w_color), _p(q), _p(dirs), _pv(sig), rows_out.stride(0) if n > 1 else 3 * B + 1, n, M, H2,
+         int(deg), _p(dh2), _p(dsig), _p(d_w_sigma), _p(d_b_sigma), _p(d_w_color), _p(d_b_color), _p(cs), _p(ws), nb, _stream())
+    return dh2, dsig, cs
 
 
 def composite_bounded_fwd(raw, z, last_delta=None, flip=False, depth_real=None, want_weights=False, want_bg_lambda=False):
