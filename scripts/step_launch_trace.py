@@ -6,8 +6,15 @@ arguments in the same order.  Not covered: the side-stream sections and the prof
     python scripts/step_launch_trace.py OUT.json [ROOT]     record (ROOT: the checkout whose switch_nerf_amd is traced, default this one)
     python scripts/step_launch_trace.py --diff A.json B.json
 
-A pointer that is `tmp` on one side and a named buffer on the other is a freed temporary whose address a later buffer took, not a
-difference in the launch."""
+Every tensor whose address goes into a call is kept alive until its case ends, so no later buffer can take a freed temporary's address:
+a temporary always reads `tmp`, and two traces of one tree are equal.  A pointer that is `tmp` on one side and a named buffer on the other
+is therefore a buffer that one side keeps under a model or context key and the other does not.
+
+A host-resident model packs no compute copies (SwitchNeRF.refresh_compute_copies returns early off the GPU), so the script wraps that
+method: for the duration of the call the model's device reads as "cuda" and the (mocked) packing runs.  The mock returns zeros, so three
+host decisions get consistent fakes: fake_route (every token to expert 0), fake_fg_bounds (every second ray continues into the
+background) and fake_cells_assign / fake_cells_pack (point p in cell p % K).  A context's "head" record is not named: it holds no buffer
+of its own, only the caller's tensors, which the context also keeps under the keys the backward reads."""
 import ctypes as C
 import json
 import sys
@@ -68,29 +75,32 @@ def name_ptrs(obj, ranges):
     return obj
 
 
-def ranges_of(m, ctxs):
+def ranges_of(models, ctxs):
     r = []
+
     def add(t, n):
-        if torch.is_tensor(t) and t.numel():
-            r.append((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), n))
-    for k, t in m._bufs.items():
-        for i, x in enumerate(t if isinstance(t, tuple) else (t,)):
-            add(x, "buf%r.%d" % (k, i))
-    for k, t in m.wf.items():
-        add(t, "wf." + k)
-    for k, t in m.wb.items():
-        add(t, "wb." + k)
-    add(m.flat, "flat"); add(m.grad, "grad"); add(m.m, "adam_m"); add(m.v, "adam_v")
+        if torch.is_tensor(t):
+            if t.numel():
+                r.append((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), n))
+        elif isinstance(t, (list, tuple)):
+            for i, x in enumerate(t):
+                add(x, "%s.%d" % (n, i))
+        elif isinstance(t, dict):
+            for k, x in t.items():
+                if k != "head":
+                    add(x, "%s.%s" % (n, k))
+    for mi, m in enumerate(models if isinstance(models, (list, tuple)) else [models]):
+        pre = "m%d." % mi if mi else ""
+        for k, t in m._bufs.items():
+            for i, x in enumerate(t if isinstance(t, tuple) else (t,)):
+                add(x, pre + "buf%r.%d" % (k, i))
+        for k, t in m.wf.items():
+            add(t, pre + "wf." + k)
+        for k, t in m.wb.items():
+            add(t, pre + "wb." + k)
+        add(m.flat, pre + "flat"); add(m.grad, pre + "grad"); add(m.m, pre + "adam_m"); add(m.v, pre + "adam_v")
     for ci, c in enumerate(ctxs):
-        for k, t in c.items():
-            if isinstance(t, (list, tuple)):
-                for i, x in enumerate(t):
-                    add(x, "c%d.%s.%d" % (ci, k, i))
-            elif isinstance(t, dict):
-                for kk, x in t.items():
-                    add(x, "c%d.%s.%s" % (ci, k, kk))
-            else:
-                add(t, "c%d.%s" % (ci, k))
+        add(c, "c%d" % ci)
     return r
 
 
@@ -131,12 +141,21 @@ class _S:
 
 ops.call = fake_call
 ops._stream = lambda: C.c_void_p(0)
+_alive = []
+
+
 def _ptr(t):
     assert t is None or t.is_contiguous()
+    _alive.append(t)
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-ops._p = _ptr
+def _ptr_view(t):      # (the address of a strided view: heads_coef_fwd's output slice)
+    _alive.append(t)
+    return C.c_void_p(t.data_ptr())
+
+
+ops._p, ops._pv = _ptr, _ptr_view
 _lib.load = lambda: FakeLib()
 ops._lib.load = _lib.load
 _sched = torch.zeros(16, dtype=torch.int32)
@@ -167,6 +186,61 @@ ops.route_top1 = fake_route
 from switch_nerf_amd.model import SwitchNeRF  # noqa: E402
 from switch_nerf_amd.dense import DenseNeRF  # noqa: E402
 
+from switch_nerf_amd.background import BackgroundScene  # noqa: E402
+from switch_nerf_amd.mega import MegaNeRF  # noqa: E402
+
+_refresh = SwitchNeRF.refresh_compute_copies
+
+
+class _AsCuda:
+    type = "cuda"
+
+
+def refresh_on_host(self):
+    """refresh_compute_copies of a host-resident model: its device reads as "cuda" while the (mocked) packing runs"""
+    real = self.dev
+    self.dev = _AsCuda()
+    try:
+        _refresh(self)
+    finally:
+        self.dev = real
+
+
+SwitchNeRF.refresh_compute_copies = refresh_on_host
+_fg_bounds, _cells_assign, _cells_pack = ops.fg_bounds, ops.cells_assign, ops.cells_pack
+
+
+def fake_fg_bounds(rays, center, radius, n_out=None):
+    """a consistent bound for the zero-filled mock: the rays keep their far plane, every second one continues into the background"""
+    rays_fg, fg_far, last_delta, has_bg, n_out = _fg_bounds(rays, center, radius, n_out)
+    rays_fg.copy_(rays)
+    fg_far.copy_(rays[:, 7])
+    has_bg[::2] = 1
+    return rays_fg, fg_far, last_delta, has_bg, n_out
+
+
+def fake_cells_assign(x, centroids, dim_start, margin):
+    """point p belongs to cell p % K alone"""
+    weights, counts = _cells_assign(x, centroids, dim_start, margin)
+    P, K = weights.shape
+    weights[torch.arange(P), torch.arange(P) % K] = 1.0
+    counts.copy_(torch.bincount(torch.arange(P) % K, minlength=K))
+    return weights, counts
+
+
+def fake_cells_pack(weights, counts, rows_capacity=None):
+    """the packed row space of fake_cells_assign's membership"""
+    begin, rows, slot = _cells_pack(weights, counts, rows_capacity)
+    P, K = weights.shape
+    cell = torch.arange(P) % K
+    begin[1:] = torch.cumsum(counts, 0)
+    rows[:P] = torch.sort(cell, stable=True)[1].to(torch.int32)
+    slot.fill_(-1)
+    slot[torch.arange(P), cell] = (torch.arange(P) // K).to(torch.int32)
+    return begin, rows, slot
+
+
+ops.fg_bounds, ops.cells_assign, ops.cells_pack = fake_fg_bounds, fake_cells_assign, fake_cells_pack
 BF16, F32 = torch.bfloat16, torch.float32
 
 
@@ -223,12 +297,104 @@ CASES = {
     "dense": dict(dense=True, chunk=4096),
     "dense_fp32_infer": dict(dense=True, chunk=4096, dtype=F32),
 }
+
+
+SH2 = dict(synth.DENSE, pos_dir_dim=0, sh_deg=2)
+CELL = dict(layer_dim=64, layers=2, skip_layers=(1,), pos_xyz_dim=3, pos_dir_dim=2, appearance_dim=8, appearance_count=10, xyz_dim=3)
+CELL_SH = dict(CELL, pos_dir_dim=0, sh_deg=2)
+CEN = np.array([[-0.5, -0.4, 0.1], [0.5, -0.3, -0.2], [0.0, 0.5, 0.3]], np.float32)
+
+
+def dense_sh_train(N=8, S=8):
+    m = DenseNeRF(SH2, dtype=F32, device="cpu")
+    rays, img, rgbs = synth.make_rays(301, N)
+    g = torch.Generator().manual_seed(302)
+    st = m.grad_step(dev(rgbs), dev(rays), dev(img), S, N * S, perturb=1.0, perturb_rand=torch.rand(N, S, generator=g),
+                     sigma_noise=torch.randn(N * S, generator=g))
+    return m, [st["ctx"]]
+
+
+def points_call(cfg=synth.DENSE, sigma_only=False, xyz_dim=3, coef=False, training=False, P=40):
+    """DenseNeRF.__call__ / forward_coef on P explicit points; the context does not leave the call, so only the model's buffers are named"""
+    m = DenseNeRF(dict(cfg, xyz_dim=xyz_dim), dtype=F32, device="cpu")
+    m.train(training)
+    g = torch.Generator().manual_seed(303)
+    sh = cfg.get("sh_deg") is not None
+    x = torch.rand(P, xyz_dim if sigma_only else xyz_dim + (1 if sh else 4), generator=g)
+    noise = torch.randn(P, generator=g)
+    if coef:
+        return m, [m.forward_coef(x, noise, torch.zeros(P, 3 * 9 + 1))]
+    m(x, sigma_only, noise)
+    return m, []
+
+
+def bg_scene(fine=0, training=True, N=16, S=8):
+    m, b = DenseNeRF(synth.DENSE, dtype=F32, device="cpu"), DenseNeRF(synth.DENSE_BG, dtype=F32, device="cpu")
+    scene = BackgroundScene(m, b, synth.SPHERE_CENTER, synth.SPHERE_RADIUS)
+    rays, img, _ = synth.make_bg_rays(304, N)
+    g = torch.Generator().manual_seed(305)
+    Nb = (N + 1) // 2
+    more = {}
+    if fine:
+        more = dict(fine_samples=fine, fine_u=torch.rand(N, fine, generator=g), fine_u_bg=torch.rand(Nb, fine // 2, generator=g))
+    ctx = scene.forward(dev(rays), dev(img), S, N * S, perturb=1.0, perturb_rand=torch.rand(N, S, generator=g),
+                        perturb_rand_bg=torch.rand(Nb, S // 2, generator=g), training=training, **more)
+    return [m, b], [ctx]
+
+
+def mega(cfg=CELL, call=None, fine=0, N=12, S=4):
+    subs = [DenseNeRF(cfg, dtype=F32, device="cpu", seed=i) for i in range(3)]
+    sh = cfg.get("sh_deg") is not None
+    m = MegaNeRF(subs, CEN, 1.15, False, False, joint_training=call is None, sh_training=call is None and sh)
+    g = torch.Generator().manual_seed(306)
+    if call is not None:
+        P = N * S
+        x, noise = torch.rand(P, 4 if sh else 7, generator=g), torch.randn(P, generator=g)
+        if call == "rgb":
+            m.call_rgb(x, torch.rand(N, 3, generator=g), S, noise)
+        else:
+            m(x[:, :3] if call == "sigma_only" else x, call == "sigma_only", noise)
+        return subs, []
+    rays, img, rgbs = synth.make_rays(307, N)
+    more = {}
+    if fine:
+        more = dict(fine_samples=fine, fine_u=torch.rand(N, fine, generator=g), sigma_noise_fine=torch.randn(N * fine, generator=g))
+    st = m.train_step(dev(rgbs), dev(rays), dev(img), S, perturb=1.0, perturb_rand=torch.rand(N, S, generator=g),
+                      sigma_noise=torch.randn(N * S, generator=g), **more)
+    return subs, [st["ctx"]] + ([st["ctx_fine"]] if fine else [])
+
+
+MORE_CASES = {
+    "dense_sh_train": (dense_sh_train, dict()),
+    "call_dense": (points_call, dict()),
+    "call_dense_training_mode": (points_call, dict(training=True)),
+    "call_dense_sigma_only": (points_call, dict(sigma_only=True)),
+    "call_dense_xyz4": (points_call, dict(xyz_dim=4)),
+    "call_dense_xyz4_training_mode": (points_call, dict(xyz_dim=4, training=True)),
+    "call_sh": (points_call, dict(cfg=SH2)),
+    "call_sh_sigma_only": (points_call, dict(cfg=SH2, sigma_only=True)),
+    "call_sh_xyz4": (points_call, dict(cfg=SH2, xyz_dim=4)),
+    "call_sh_xyz4_sigma_only": (points_call, dict(cfg=SH2, xyz_dim=4, sigma_only=True)),
+    "forward_coef": (points_call, dict(cfg=SH2, coef=True)),
+    "bg_scene_train_coarse": (bg_scene, dict()),
+    "bg_scene_train_fine": (bg_scene, dict(fine=8)),
+    "bg_scene_eval_fine": (bg_scene, dict(fine=8, training=False)),
+    "mega_call": (mega, dict(call="all")),
+    "mega_call_sigma_only": (mega, dict(call="sigma_only")),
+    "mega_sh_call": (mega, dict(cfg=CELL_SH, call="all")),
+    "mega_sh_call_rgb": (mega, dict(cfg=CELL_SH, call="rgb")),
+    "mega_train_coarse": (mega, dict()),
+    "mega_train_fine": (mega, dict(fine=4)),
+    "mega_sh_train_coarse": (mega, dict(cfg=CELL_SH)),
+    "mega_sh_train_fine": (mega, dict(cfg=CELL_SH, fine=4)),
+}
 res = {}
-for name, kw in CASES.items():
+for name, (fn, kw) in list((k, (train, v)) for k, v in CASES.items()) + list(MORE_CASES.items()):
     trace.clear()
     ptr_ids.clear()
+    _alive.clear()
     try:
-        m, ctxs = train(**kw)
+        m, ctxs = fn(**kw)
         res[name] = name_ptrs(list(trace), ranges_of(m, ctxs))
     except Exception as e:  # noqa: BLE001
         res[name] = list(trace) + [["ERROR", repr(e)[:300]]]

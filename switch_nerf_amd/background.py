@@ -198,7 +198,6 @@ class BackgroundScene:
             ctx = dict(N=N, S=S, F=Fn, idx_bg=idx_bg, Nb=Nb, fg_far=fg_far, has_bg=has_bg)
         det_u = lambda n, k: torch.linspace(0, 1, k).expand(n, k).contiguous().to(self.dev) if perturb == 0 else torch.rand(n, k, device=self.dev)
         # ---- background first (the reference's order, and so the order of its random draws)
-        bg._saving = bool(training)          # (DenseNeRF._net_forward is called directly below; reset after the block)
         if Nb > 0:
             Sb = S // 2
             if not padded:
@@ -227,7 +226,7 @@ class BackgroundScene:
                 sigma_noise_bg = drawn["sigma_noise"] = draw(o.RNG_SIGMA, Sb, o.RNG_NORMAL, float(noise_std)).view(-1)
             if isinstance(sigma_noise_bg, str):
                 sigma_noise_bg = torch.randn(Nb * Sb, device=self.dev) * noise_std
-            cb = bg._net_forward(pe_b, pe_dir_b, img_b, Nb, Sb, Nb * Sb, sigma_noise_bg, None, False, "c")
+            cb = bg._net_forward(pe_b, pe_dir_b, img_b, Nb, Sb, Nb * Sb, sigma_noise_bg, None, False, "c", saving=bool(training))
             cb["z"], cb["depth_real"] = z_b, dreal_b
             rgb_b, depth_b, _, w_b, _ = o.composite_bounded_fwd(cb["raw"], z_b, None, True, dreal_b, want_weights=Fn > 0)
             b = dict(c=cb, raw=cb["raw"], z=z_b)
@@ -244,7 +243,7 @@ class BackgroundScene:
                 z_f = o.sample_pdf(z_b.flip(-1).contiguous(), w_b, fine_u_bg, Fb)        # ascending bins x flipped weights (see module doc)
                 _, dreal_f, pe_f = o.bg_sample_pe(rays_b, self.center, self.radius, Fb, bg.cfg["pos_xyz_dim"], bg.dtype, bg.KP,
                                                   z_in=z_f, pe_out=bg._buf("f:pe", (Nb * Fb, bg.KP), bg.dtype))
-                cfb = bg._net_forward(pe_f, pe_dir_b, img_b, Nb, Fb, Nb * Fb, sigma_noise_bg_fine, None, False, "f")
+                cfb = bg._net_forward(pe_f, pe_dir_b, img_b, Nb, Fb, Nb * Fb, sigma_noise_bg_fine, None, False, "f", saving=bool(training))
                 # descending sort of the union (:421 descending=flip) = ascending sort of the negated depths
                 zneg, order, raw_m = o.merge_samples((-z_f).contiguous(), (-z_b).contiguous(), cfb["raw"], cb["raw"])
                 z_m = -zneg
@@ -254,7 +253,6 @@ class BackgroundScene:
             b.update(rgb=rgb_b, depth=depth_b, **drawn)       # (the draws of this pass, for inspection; a supplied tensor is the caller's)
             ctx["bg"] = b
         # ---- foreground on the clipped rays
-        bg._saving = True
         std_fg = float(noise_std) if dn is not None else 0.0       # device noise: the foreground draws its own sigma noise (streams 1 / 3)
         c = nerf.forward_rays(rays_fg, image_indices, S, seg_tokens, perturb, perturb_rand, sigma_noise, training, None,
                               no_batch=no_batch, want_weights=Fn > 0, composite=Fn > 0, sigma_noise_std=std_fg)

@@ -19,7 +19,12 @@ sigma.*, rgb.*, embedding_a.weight), so checkpoints interchange.
 cfg["sh_deg"] = d (0..4; --sh_deg, opts.py:69): spherical-harmonics colour.  pos_dir_dim is 0 (nerf.py:82-83), so layer "2" sees
 [xyz_encoding_final, embedding] with NO direction block (in_dir = 0), the colour head has 3 (d + 1)^2 rows (nerf.py:137-143) and
 rendering.py:344-347 turns a point's coefficients into rgb with sigmoid(eval_sh(d, coef, ray direction)): the heads run as
-swn_heads_sh_fwd / swn_heads_sh_bwd (csrc/sh.hip) behind the unfused tail, like an affine model's.
+swn_heads_sh_fwd / swn_heads_sh_bwd (csrc/sh.hip) behind the unfused tail, like an affine model's.  Which heads a pass launches is
+the pass's `head` argument (model.ShHead: the contraction against that pass's ray directions, built by forward_rays; model.CoefHead: a
+Mega-NeRF cell's coefficient rows), carried in the context - nothing about a pass is kept on the model.
+
+The points entries (__call__, its sh_deg form, forward_coef) check their arguments and slice the result around ONE method,
+_points_forward: one-sample rays through forward_rays (xyz_dim 3), or host-encoded inverted-sphere points into _net_forward (xyz_dim 4).
 """
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .model import SwitchNeRF, _ceil_to
+from .model import CoefHead, ShHead, SwitchNeRF, _ceil_to
 
 # /root/reference/switch_nerf/opts.py defaults for the non-MoE model (layer_dim 256, 8 layers, skip at 4, appearance 48)
 DENSE = dict(layer_dim=256, layers=8, skip_layers=(4,), pos_xyz_dim=12, pos_dir_dim=4, appearance_dim=48,
@@ -177,24 +182,24 @@ class DenseNeRF(SwitchNeRF):
         raise NotImplementedError("the dense NeRF has no experts to shard")
 
     # ------------------------------------------------------------------------------------------ forward
-    _sh_dirs = None          # sh_deg: the fp32 directions rays[:, 3:6] of the pass being run (forward_rays -> _net_forward)
-
-    def forward_rays(self, rays, *args, **kw):
+    def forward_rays(self, rays, *args, head=None, **kw):
         if self.sh_deg is not None:
             if self._noise_scene is not None or self.xyz_dim != 3:
                 raise NotImplementedError("sh_deg: a background model / a scene with one is not built with spherical-harmonics colour")
-            self._sh_dirs = rays[:, 3:6].contiguous()
-        return super().forward_rays(rays, *args, **kw)
+            if head is None:      # the heads contract against the fp32 ray directions of THIS pass
+                head = ShHead(rays[:, 3:6].contiguous(), False)
+        return super().forward_rays(rays, *args, head=head, **kw)
 
-    def _net_forward(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag):
+    def _net_forward(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, *, saving, head=None):
         """NeRF.forward (nerf.py:143-190) over the N*S points whose encodings are in `pe` -> c["raw"] [N*S, 4]."""
         o, dt = ops, self.dtype
         P = N * S
         W, L, H2, s = self.M, self.L, self.H2, self.skip_l
-        c = dict(N=N, S=S, P=P, n_seg=max(1, P // seg_tokens), seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
+        c = dict(N=N, S=S, P=P, n_seg=max(1, P // seg_tokens), seg_tokens=seg_tokens, tag=tag, image_indices=image_indices,
+                 saving=bool(saving), head=head)
         c["pe"], c["pe_dir"] = pe, pe_dir
-        if self.sh_deg is not None and self._coef_out is None:      # (forward_coef: the basis enters behind the cells' blend, not here)
-            d = self._sh_dirs
+        if self.sh_deg is not None and not isinstance(head, CoefHead):      # (forward_coef: the basis enters behind the cells' blend, not here)
+            d = head.dirs if isinstance(head, ShHead) else None
             if d is None or d.shape != (N, 3) or d.dtype != torch.float32:
                 raise NotImplementedError("sh_deg: the directions of this pass are missing - only forward_rays / forward_hier / __call__ "
                                           "run a spherical-harmonics model (no background scene, no mip path)")
@@ -202,7 +207,7 @@ class DenseNeRF(SwitchNeRF):
         c["acts"] = [self._cbuf(c, f"act{i}", (P, W), dt) for i in range(L)]          # post-ReLU outputs; acts[L-1] = xyz_ (c["y"])
         mw = o.chain_mask_words(dt, 1, P, max(W, self.KP))
         c["masks"] = [self._cbuf(c, f"mask{i}", (mw,), torch.int32) for i in range(L)]
-        sv = self._saving
+        sv = c["saving"]
         c["no_grad"] = not sv
         layers = []
         for i in range(L):
@@ -292,23 +297,27 @@ class DenseNeRF(SwitchNeRF):
             raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(x.shape, expected, xd))
         P = x.shape[0]
         xf = x.to(torch.float32)
-        if sigma_only:
-            xf = torch.cat([xf, torch.zeros(P, 4, device=self.dev)], 1)
-            xf[:, xd + 2] = 1.0
-        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
-        img = xf[:, xd + 3].long().contiguous()
-        if xd == 3:
-            rays = torch.cat([xf[:, :6], torch.zeros(P, 2, device=self.dev)], 1).contiguous()
-            c = self.forward_rays(rays, img, 1, P, 0.0, None, noise, training=self.training, composite=False)
+        if sigma_only:      # (direction (0, 0, 1), image 0: neither reaches sigma)
+            dirs, img = torch.tensor([0.0, 0.0, 1.0], device=self.dev).expand(P, 3), torch.zeros(P, dtype=torch.long, device=self.dev)
         else:
-            pe = self._pe_points(xf[:, :xd])
-            rays = torch.cat([torch.zeros(P, 3, device=self.dev), xf[:, xd:xd + 3], torch.zeros(P, 2, device=self.dev)], 1).contiguous()
-            self._saving = bool(self.training)
-            try:
-                c = self._net_forward(pe, self._dir_pe(rays), img, P, 1, P, noise, None, False, "c")
-            finally:
-                self._saving = True
+            dirs, img = xf[:, xd:xd + 3], xf[:, xd + 3].long().contiguous()
+        c = self._points_forward(xf[:, :xd], img, dirs, sigma_noise, bool(self.training))
         return c["raw"][:, 3:4] if sigma_only else c["raw"]
+
+    def _points_forward(self, pts, img, dirs=None, sigma_noise=None, saving=False, head=None, tag="c"):
+        """The network over explicit points: pts [P, xyz_dim] fp32, img [P] int64, dirs [P, 3] or None (zeros), sigma_noise of P values
+        or None -> ctx.  xyz_dim 3: one-sample rays (o = xyz, near = far = 0 -> the sample IS the point) through forward_rays;
+        xyz_dim 4: the inverted-sphere points encoded on the host (_pe_points), then the network."""
+        P = pts.shape[0]
+        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
+        z = torch.zeros(P, 3, device=self.dev)
+        d = z if dirs is None else dirs
+        if self.xyz_dim == 3:
+            rays = torch.cat([pts, d, z[:, :2]], 1).contiguous()
+            return self.forward_rays(rays, img, 1, P, 0.0, None, noise, training=saving, tag=tag, composite=False, head=head)
+        self._sync_compute_copies()
+        rays = torch.cat([z, d, z[:, :2]], 1).contiguous()
+        return self._net_forward(self._pe_points(pts), self._dir_pe(rays), img, P, 1, P, noise, None, False, tag, saving=saving, head=head)
 
     def _pe_points(self, pts):
         """The positional encoding [P, KP] of explicit points [P, xyz_dim] (fp32), on the host."""
@@ -334,46 +343,24 @@ class DenseNeRF(SwitchNeRF):
             raise ValueError("inner_sigmoid belongs to sh_deg 0 (rgb_dim == 3)")
         if x.dim() != 2 or x.shape[1] != 4:
             raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(tuple(x.shape), 4, self.xyz_dim))
-        n = x.shape[0]
         xf = x.to(torch.float32)
-        rays = torch.cat([xf[:, :3], torch.zeros(n, 5, device=self.dev)], 1).contiguous()      # o = xyz, d = 0, z = 0 -> the sample IS the point
-        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
-        self._coef_out = (out, bool(inner_sigmoid))
-        try:
-            c = self.forward_rays(rays, xf[:, 3].long().contiguous(), 1, n, 0.0, None, noise, training=True, tag=tag, composite=False)
-        finally:
-            self._coef_out = None
-        return c
-
-    _sh_want_coef = False    # inside _call_sh: the heads' launch also leaves the colour head's linear outputs (c["coef"])
+        return self._points_forward(xf[:, :3], xf[:, 3].long().contiguous(), None, sigma_noise, True, CoefHead(out, bool(inner_sigmoid)), tag)
 
     def _call_sh(self, x, sigma_only, sigma_noise):
         """The sh_deg form of NeRF.forward (nerf.py:147-149, :191): x [P, xyz_dim + 1] = position, image index (no direction columns) ->
-        [P, 3 B + 1] = the raw coefficients (row-major [3, B] per point, no activation), then sigma; sigma_only: x [P, xyz_dim] -> [P, 1]."""
+        [P, 3 B + 1] = the raw coefficients (row-major [3, B] per point, no activation), then sigma; sigma_only: x [P, xyz_dim] -> [P, 1].
+        xyz_dim 4: the background half of a Mega-NeRF container, explicit inverted-sphere points."""
         xd = self.xyz_dim
         expected = xd if sigma_only else xd + 1
         if x.shape[1] != expected:
             raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(x.shape, expected, xd))
+        if xd != 3 and self.training:
+            raise NotImplementedError("sh_deg: a model with xyz_dim 4 is called on points in evaluation mode only")
         P = x.shape[0]
         xf = x.to(torch.float32)
         img = torch.zeros(P, dtype=torch.long, device=self.dev) if sigma_only else xf[:, xd].long().contiguous()
-        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
-        self._sh_want_coef = True
-        try:
-            if xd == 3:
-                rays = torch.cat([xf[:, :3], torch.zeros(P, 5, device=self.dev)], 1).contiguous()      # o = xyz, d = 0, z = 0 -> sample = xyz
-                c = self.forward_rays(rays, img, 1, P, 0.0, None, noise, training=self.training, composite=False)
-            else:       # the background half of a Mega-NeRF container: explicit inverted-sphere points, encoded like __call__ does
-                if self.training:
-                    raise NotImplementedError("sh_deg: a model with xyz_dim 4 is called on points in evaluation mode only")
-                self._sync_compute_copies()
-                rays = torch.zeros(P, 8, device=self.dev)
-                self._sh_dirs = rays[:, 3:6].contiguous()       # (the heads' own rgb is not returned: the caller evaluates the basis)
-                self._saving = False
-                try:
-                    c = self._net_forward(self._pe_points(xf[:, :xd]), self._dir_pe(rays), img, P, 1, P, noise, None, False, "c")
-                finally:
-                    self._saving = True
-        finally:
-            self._sh_want_coef = False
+        # the heads' launch also leaves the colour head's linear outputs (c["coef"]); its own rgb, against zero directions, is not
+        # returned: the caller evaluates the basis
+        head = ShHead(torch.zeros(P, 3, device=self.dev), True)
+        c = self._points_forward(xf[:, :xd], img, None, sigma_noise, bool(self.training), head)
         return c["raw"][:, 3:4] if sigma_only else torch.cat([c["coef"], c["raw"][:, 3:4]], 1)

@@ -16,6 +16,9 @@ Sub-models with spherical-harmonics colour (DenseNeRF cfg["sh_deg"], the workflo
 rows and the reference blends THOSE before rendering.py:344-347 applies sigmoid(eval_sh(...)).  ops.cells_blend_sh does the blend of the
 wide rows and the evaluation in one launch (call_rgb; render_rays), or leaves the blended rows (the module mirror, __call__).
 
+In the code the first four lines are _gather_cells (shared by inference and training) and the loop is _cells, the one iterator over
+the non-empty cells (index, sub-model, slice of the packed rows) that every forward and backward_points walks.
+
 Inside a cell the rows ascend by point index - the order x[cluster_mask] has in the reference, so sigma_noise[cluster_mask] lines up.
 render_rays() below is what rendering.render_rays runs for a MegaNeRF foreground (evaluation).
 
@@ -301,31 +304,41 @@ class MegaNeRF:
         expected = col0 + self.xyz_dim + (0 if sigma_only else (4 if self.sh_deg is None else 1))
         if x.dim() != 2 or x.shape[1] != expected:
             raise Exception("Unexpected input shape: {} (expected: {}, xyz_dim: {})".format(tuple(x.shape), expected, self.xyz_dim))
-        P, K = x.shape[0], len(self.sub_modules)
-        Cn = 1 if sigma_only else self.n_out
-        if P == 0:
+        if x.shape[0] == 0:
             return None
+        r, xin, nin = self._gather_cells(x, sigma_noise, col0)
+        sub_out = torch.empty(r["total"], 1 if sigma_only else self.n_out, dtype=torch.float32, device=self.dev)
+        for _i, child, sl in self._cells(r["counts"]):
+            sub_out[sl] = child(xin[sl], sigma_only, None if nin is None else nin[sl])
+        if self.sh_deg == 0 and not sigma_only:
+            # rgb_dim == 3: the reference's NeRF keeps its own nn.Sigmoid on the three outputs (models/nerf.py:140-141, :187-188), so
+            # at degree 0 a cell's row holds sigmoid(lin), and rendering.py:344-347 puts eval_sh and a second sigmoid on the blend.
+            # DenseNeRF's sh_deg call returns lin at every degree; the degenerate degree is squared with the reference here.
+            sub_out[:, :3] = torch.sigmoid(sub_out[:, :3])
+        return r["weights"], r["slot"], r["begin"], sub_out, r["hard"]
+
+    def _gather_cells(self, x, sigma_noise, col0=0):
+        """The prologue of every forward over the points x: route, the ONE device-to-host read, cells_gather from column col0 on ->
+        (routing, xin [total, ..], noise [total] or None); routing = {weights, rows, begin, slot, counts (a host list), total, hard, P}."""
         x = x.to(torch.float32).contiguous()
         noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
-        hard = self.boundary_margin == 1
         weights, counts, begin, rows, slot = self.route(x)
         n = counts.tolist()                                    # the one synchronisation: K ints size the ragged sub-model calls
         total = sum(n)
         if total == 0:      # only non-finite positions under a soft margin get here: their weights are NaN, so no cell counts as a member
             raise ValueError("MegaNeRF: no point belongs to a cell - the positions are not finite")
         xin, nin = ops.cells_gather(x, rows, total, col0, noise)
-        sub_out = torch.empty(total, Cn, dtype=torch.float32, device=self.dev)
+        return dict(weights=weights, rows=rows, begin=begin, slot=slot, counts=n, total=total, hard=self.boundary_margin == 1,
+                    P=x.shape[0]), xin, nin
+
+    def _cells(self, counts):
+        """(cell index, sub-model, its slice of the packed rows) of every non-empty cell (empty cells are skipped, mega_nerf.py:38; in
+        training their gradient stays zero, :51-59)."""
         b = 0
-        for i, child in enumerate(self.sub_modules):
-            if n[i] > 0:                                       # (empty cells are skipped, :38)
-                sub_out[b:b + n[i]] = child(xin[b:b + n[i]], sigma_only, None if nin is None else nin[b:b + n[i]])
-            b += n[i]
-        if self.sh_deg == 0 and not sigma_only:
-            # rgb_dim == 3: the reference's NeRF keeps its own nn.Sigmoid on the three outputs (models/nerf.py:140-141, :187-188), so
-            # at degree 0 a cell's row holds sigmoid(lin), and rendering.py:344-347 puts eval_sh and a second sigmoid on the blend.
-            # DenseNeRF's sh_deg call returns lin at every degree; the degenerate degree is squared with the reference here.
-            sub_out[:, :3] = torch.sigmoid(sub_out[:, :3])
-        return weights, slot, begin, sub_out, hard
+        for i, (child, n) in enumerate(zip(self.sub_modules, counts)):
+            if n > 0:
+                yield i, child, slice(b, b + n)
+            b += n
 
     # ------------------------------------------------------------------------------------------ training through the cells
     def forward_points(self, x, sigma_noise=None, tag: str = "c", dirs=None, rows_per_group: int = 1):
@@ -354,49 +367,25 @@ class MegaNeRF:
             dirs = dirs.to(torch.float32).contiguous()
         elif dirs is not None:
             raise ValueError("forward_points: dirs belong to cells with sh_deg; these points carry their direction columns")
-        x = x.to(torch.float32).contiguous()
-        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
-        hard = self.boundary_margin == 1
-        weights, counts, begin, rows, slot = self.route(x)
-        n = counts.tolist()                                    # the one synchronisation: K ints size the ragged sub-model calls
-        total = sum(n)
-        if total == 0:
-            raise ValueError("MegaNeRF: no point belongs to a cell - the positions are not finite")
-        xin, nin = ops.cells_gather(x, rows, total, 0, noise)
+        r, xin, nin = self._gather_cells(x, sigma_noise)
+        total, cells = r["total"], [None] * len(self.sub_modules)
         if sh:
-            return self._forward_points_sh(xin, nin, dirs, rpg, weights, rows, begin, slot, n, total, hard, P, tag)
+            # each cell's heads write its slice of the packed rows (degree 0: the reference NeRF's own sigmoid on its three outputs, as
+            # _sub_outputs); the inference blend kernel evaluates the basis on the blend
+            sub_out = torch.empty(total, self.n_out, dtype=torch.float32, device=self.dev)
+            for i, child, sl in self._cells(r["counts"]):
+                cells[i] = child.forward_coef(xin[sl], None if nin is None else nin[sl], sub_out[sl], self.sh_deg == 0, tag)
+            out = ops.cells_blend_sh(r["weights"], r["slot"], r["begin"], sub_out, dirs, rpg, self.sh_deg, r["hard"])
+            return dict(r, out=out, cells=cells, tag=tag, sub_out=sub_out, dirs=dirs, rows_per_group=rpg)
         rays = torch.cat([xin[:, :6], torch.zeros(total, 2, device=self.dev)], 1)      # o = xyz, near = far = 0 -> the sample IS the point
         img = xin[:, 6].long()
         sub_out = torch.empty(total, 4, dtype=torch.float32, device=self.dev)
-        cells, b = [], 0
-        for i, child in enumerate(self.sub_modules):
-            c = None
-            if n[i] > 0:                                       # (empty cells are skipped, :38; their gradient stays zero, :51-59)
-                sl = slice(b, b + n[i])
-                c = child.forward_rays(rays[sl].contiguous(), img[sl].contiguous(), 1, n[i], 0.0, None, None if nin is None else nin[sl],
-                                       training=True, tag=tag, composite=False)
-                sub_out[sl] = c["raw"]
-            cells.append(c)
-            b += n[i]
-        out = ops.cells_blend(weights, slot, begin, sub_out, hard)
-        return dict(out=out, weights=weights, rows=rows, begin=begin, slot=slot, cells=cells, counts=n, total=total, hard=hard, P=P, tag=tag)
-
-    def _forward_points_sh(self, xin, nin, dirs, rpg, weights, rows, begin, slot, n, total, hard, P, tag):
-        """forward_points behind the gather for cells with sh_deg: each cell's heads write its slice of the packed rows, the inference
-        blend kernel evaluates the basis on the blend."""
-        deg = self.sh_deg
-        sub_out = torch.empty(total, self.n_out, dtype=torch.float32, device=self.dev)
-        cells, b = [], 0
-        for i, child in enumerate(self.sub_modules):
-            c = None
-            if n[i] > 0:
-                sl = slice(b, b + n[i])      # (degree 0: the reference NeRF's own sigmoid on its three outputs, as _sub_outputs)
-                c = child.forward_coef(xin[sl], None if nin is None else nin[sl], sub_out[sl], deg == 0, tag)
-            cells.append(c)
-            b += n[i]
-        out = ops.cells_blend_sh(weights, slot, begin, sub_out, dirs, rpg, deg, hard)
-        return dict(out=out, weights=weights, rows=rows, begin=begin, slot=slot, cells=cells, counts=n, total=total, hard=hard, P=P, tag=tag,
-                    sub_out=sub_out, dirs=dirs, rows_per_group=rpg)
+        for i, child, sl in self._cells(r["counts"]):
+            c = cells[i] = child.forward_rays(rays[sl].contiguous(), img[sl].contiguous(), 1, sl.stop - sl.start, 0.0, None,
+                                              None if nin is None else nin[sl], training=True, tag=tag, composite=False)
+            sub_out[sl] = c["raw"]
+        out = ops.cells_blend(r["weights"], r["slot"], r["begin"], sub_out, r["hard"])
+        return dict(r, out=out, cells=cells, tag=tag)
 
     def backward_points(self, ctx, d_out):
         """Backward of forward_points given dL/d out [P, 4]: the blend's adjoint (ops.cells_blend_bwd), then every non-empty cell's
@@ -404,23 +393,17 @@ class MegaNeRF:
         self._need_joint("backward_points")
         if tuple(d_out.shape) != (ctx["P"], 4):
             raise ValueError(f"backward_points: d_out {tuple(d_out.shape)} for an output of [{ctx['P']}, 4]")
+        d_out = d_out.to(torch.float32).contiguous()
         if self.sh_deg is not None:      # the factored adjoint: q [total, 4] and one direction per packed row cross to the cells
-            q, dp = ops.cells_blend_sh_bwd(ctx["weights"], ctx["rows"], ctx["begin"], ctx["out"], d_out.to(torch.float32).contiguous(),
-                                           ctx["dirs"], ctx["rows_per_group"], self.sh_deg, ctx["total"], ctx["hard"],
-                                           ctx["sub_out"] if self.sh_deg == 0 else None)
-            b = 0
-            for child, c, n in zip(self.sub_modules, ctx["cells"], ctx["counts"]):
-                if n > 0:
-                    c["coef_dirs"] = dp[b:b + n]
-                    child.backward_net(c, q[b:b + n], None)
-                b += n
-            return
-        d_sub = ops.cells_blend_bwd(ctx["weights"], ctx["rows"], ctx["begin"], d_out.to(torch.float32).contiguous(), ctx["total"], ctx["hard"])
-        b = 0
-        for child, c, n in zip(self.sub_modules, ctx["cells"], ctx["counts"]):
-            if n > 0:
-                child.backward_net(c, d_sub[b:b + n], None)
-            b += n
+            d_sub, dp = ops.cells_blend_sh_bwd(ctx["weights"], ctx["rows"], ctx["begin"], ctx["out"], d_out, ctx["dirs"], ctx["rows_per_group"],
+                                               self.sh_deg, ctx["total"], ctx["hard"], ctx["sub_out"] if self.sh_deg == 0 else None)
+        else:
+            d_sub, dp = ops.cells_blend_bwd(ctx["weights"], ctx["rows"], ctx["begin"], d_out, ctx["total"], ctx["hard"]), None
+        for i, child, sl in self._cells(ctx["counts"]):
+            c = ctx["cells"][i]
+            if dp is not None:
+                c["coef_dirs"] = dp[sl]
+            child.backward_net(c, d_sub[sl], None)
 
     def grad_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, fine_samples=0, fine_u=None,
                   sigma_noise_fine=None):

@@ -24,6 +24,7 @@ from __future__ import annotations
 import contextlib
 import os
 import math
+from collections import namedtuple
 from typing import Dict, Optional
 
 import numpy as np
@@ -38,6 +39,10 @@ BUILDING = dict(model_dim=256, num_experts=8, expert_layers=7, skips=(3,), pos_x
 def _ceil_to(x, m):
     return (x + m - 1) // m * m
 
+
+# What a forward's heads launch instead of the model's own (fused, plain, affine) ones: _net_forward's `head`, kept in the context.
+ShHead = namedtuple("ShHead", "dirs want_coef")             # the spherical-harmonics contraction against dirs [groups, 3]; also c["coef"]
+CoefHead = namedtuple("CoefHead", "out inner_sigmoid")      # a Mega-NeRF cell's coefficient rows, written into out [n, 3 B + 1]
 
 _EXP_RECORD_STREAM = os.environ.get("SWN_EXP_RECORD_STREAM") == "1"      # see SwitchNeRF._join_side_outputs (read once, experiment only)
 
@@ -507,8 +512,6 @@ class SwitchNeRF:
     # ------------------------------------------------------------------------------------------ buffers
     affine = False          # cfg["affine_appearance"]: the per-image affine colour transform (set by _configure)
     sh_deg = None           # cfg["sh_deg"]: spherical-harmonics colour of that degree (DenseNeRF only; set by its _configure)
-    _coef_out = None        # inside DenseNeRF.forward_coef: (the [n, 3 B + 1] rows the heads write, inner sigmoid)
-    _saving = True          # False inside an inference forward: the chains skip the activation saves and ReLU masks
     hash = None             # multiresolution hash-grid input encoding (cfg["hash"]) or None
     _grow_bufs = False      # True: one buffer per name, grown to the largest row count seen (row counts that vary per step)
 
@@ -544,7 +547,7 @@ class SwitchNeRF:
     # ------------------------------------------------------------------------------------------ forward
     def forward_rays(self, rays, image_indices, n_samples, seg_tokens, perturb=0.0, perturb_rand=None, sigma_noise=None,
                      training=True, routing_override=None, no_batch=False, z_in=None, pe_dir=None, tag="c",
-                     want_weights=False, composite=True, sigma_noise_std=0.0):
+                     want_weights=False, composite=True, sigma_noise_std=0.0, head=None):
         """One pass of render_rays' _inference (rendering.py:277-494) over N rays x n_samples points: sampling (or the
         caller's depths z_in for the fine pass), positional encoding, the network, and (optionally) compositing.
         Returns a context dict holding every tensor the backward needs and the rendered results.
@@ -580,11 +583,9 @@ class SwitchNeRF:
             pe = o.pe_from_z(rays, z_in, self.cfg["pos_xyz_dim"], dt, self.KP)      # xyz_fine_fn, rendering.py:103
             if pe_dir is None:
                 pe_dir = self._dir_pe(rays)
-        self._saving = bool(training)      # inference: no activation saves / ReLU masks (nothing will run backward)
-        try:
-            c = self._net_forward(pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag)
-        finally:
-            self._saving = True
+        # (an inference pass saves no activations / ReLU masks: nothing will run backward)
+        c = self._net_forward(pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag,
+                              saving=bool(training), head=head)
         c["z"], c["rays"] = z, rays
         if drawn is not None:
             c["sigma_noise"] = drawn          # (the draw of this pass, for inspection; a supplied tensor is the caller's)
@@ -663,18 +664,21 @@ class SwitchNeRF:
                                      self.cfg["pos_dir_dim"], self.dtype, self.KP, self.DP)
         return pe_dir
 
-    def _net_forward(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag):
+    def _net_forward(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, *, saving, head=None):
         """NeRFMoE.forward over the N*S points whose encodings are in `pe`, evaluated in model chunks of seg_tokens points like
         the reference's loop (rendering.py:354-383): routing, capacity and l_aux are per chunk.  A ragged last chunk
         (N*S not a multiple of seg_tokens) is routed on its own with its own capacity, exactly as the reference does - in
-        evaluation and in training (backward_net walks the two parts)."""
+        evaluation and in training (backward_net walks the two parts).
+        saving: a training pass (the chains save activations and ReLU masks); head: None for the model's own heads, or a ShHead /
+        CoefHead record (DenseNeRF).  Both travel in the context (c["saving"], c["head"]), where every phase reads them."""
+        mode = dict(saving=saving, head=head)
         P = N * S
         seg_tokens = min(seg_tokens, P)
         if P % seg_tokens == 0:
-            return self._net_forward_rows(pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, None)
+            return self._net_forward_rows(pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, None, **mode)
         main = (P // seg_tokens) * seg_tokens
-        a = self._net_forward_rows(pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, (0, main))
-        b = self._net_forward_rows(pe, pe_dir, image_indices, N, S, P - main, sigma_noise, routing_override, no_batch, tag + "t", (main, P))
+        a = self._net_forward_rows(pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, (0, main), **mode)
+        b = self._net_forward_rows(pe, pe_dir, image_indices, N, S, P - main, sigma_noise, routing_override, no_batch, tag + "t", (main, P), **mode)
         c = dict(N=N, S=S, P=P, n_seg=a["n_seg"] + 1, seg_tokens=seg_tokens, tag=tag, image_indices=image_indices, ragged=True,
                  parts=(a, b), pe=pe, pe_dir=pe_dir)
         for k in ("raw", "l_aux", "idx", "gmax"):
@@ -737,7 +741,8 @@ class SwitchNeRF:
             kw["x_gather"] = c["perm"].view(-1)
         return kw
 
-    def _net_forward_rows(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, row_range):
+    def _net_forward_rows(self, pe, pe_dir, image_indices, N, S, seg_tokens, sigma_noise, routing_override, no_batch, tag, row_range, *, saving,
+                          head=None):
         """One or more whole model chunks: front chain, gate, routing, expert chain, tail chain, heads -> c["raw"] [P, 4].
         row_range = None: all N*S points; (r0, r1): that row range of the ray-major point grid (ragged evaluation)."""
         # The driver of the forward phases: _front_forward, _route (every row-space key of the context), _expert_forward_layers, ONE
@@ -754,7 +759,8 @@ class SwitchNeRF:
         cap = seg_tokens if no_batch else self.capacity(seg_tokens)
         if self.cf == 0 and not no_batch and self.ep is not None:
             raise ValueError(DYNCAP_EP_ERROR)
-        c = dict(N=N, S=S, P=P, n_seg=P // seg_tokens, cap=cap, seg_tokens=seg_tokens, tag=tag, image_indices=image_indices)
+        c = dict(N=N, S=S, P=P, n_seg=P // seg_tokens, cap=cap, seg_tokens=seg_tokens, tag=tag, image_indices=image_indices,
+                 saving=bool(saving), head=head)
         c["pe"], c["pe_dir"] = pe, pe_dir
         # the per-ray half of layer "2" (gather + a 75 x 128 GEMM per ray: one small launch) only needs the direction encoding: on the side
         # stream it runs under the front chain / the router instead of between the routing and the expert launch
@@ -766,7 +772,7 @@ class SwitchNeRF:
         owner = self._route(c, gnoise, routing_override, no_batch, row_range)
         layers = self._expert_forward_layers(c)
         # ---- the expert chain (gathers its rows through perm; ragged groups = (segment, expert)): ONE mode per forward
-        if no_batch and not self._saving and self.ep is not None:
+        if no_batch and not c["saving"] and self.ep is not None:
             self._experts_forward_ep_nobatch(c, layers)
         elif self.ep is None and c["tail_fused"]:
             return self._experts_forward_fused(c, layers, pe_dir, image_indices, sigma_noise, ray_feat_ev)
@@ -774,7 +780,7 @@ class SwitchNeRF:
             self._experts_forward_local(c, layers)
         elif owner:
             from . import ep_owner
-            return ep_owner.forward(self, c, layers, pe_dir, image_indices, sigma_noise, self._saving)
+            return ep_owner.forward(self, c, layers, pe_dir, image_indices, sigma_noise, c["saving"])
         else:
             self._experts_forward_ep(c, layers)
         # ---- per-ray part of layer "2"
@@ -799,7 +805,7 @@ class SwitchNeRF:
         c["a1"] = self._cbuf(c, "a1", (P, G), dt)
         c["g"] = self._cbuf(c, "g", (P, G), dt)
         c["m_a1"] = self._cbuf(c, "m_a1", (o.chain_mask_words(dt, 1, P, max(M, G, self.KP)),), torch.int32)
-        sv = self._saving
+        sv = c["saving"]
         c["no_grad"] = not sv
         # (the 64-row kernels re-stream the 320 KB of weights from L2 for every 64 rows - 11.8 GB of L2 reads per 2M-point launch against
         #  0.5 GB of input, the CU's L2 -> L1 path is what bounds them - the persistent 256-row geometry a quarter of that)
@@ -828,7 +834,7 @@ class SwitchNeRF:
         """Gate, routing override, the packed / dyn / want_drops decisions, routing; returns whether the step hands over to ep_owner.py."""
         # Fills EVERY row-space key of the context: idx, gmax, geom, tail_fused, dyn, loc, counts, perm, tok2row, l_aux, drop_begin / dropped,
         # group_begin, packed_rows, rows, ng, counts_flat.
-        o, dt, dev, sv = ops, self.dtype, self.dev, self._saving
+        o, dt, dev, sv = ops, self.dtype, self.dev, c["saving"]
         P, n_seg, cap, seg_tokens, M, E = c["P"], c["n_seg"], c["cap"], c["seg_tokens"], self.M, self.E
         c["gates"], c["idx"], c["gmax"], c["stats"] = o.gate_fwd(c["g"], self.p["ln.w"], self.p["ln.b"], self.p["wg"], noise=gnoise,
                                                                  noise_scale=self.gate_noise / E)
@@ -879,7 +885,7 @@ class SwitchNeRF:
 
     def _expert_forward_layers(self, c):
         """The expert chain's save / mask / output buffers of the context's row space and its forward layer list (this rank's experts)."""
-        o, dt, sv, L, M = ops, self.dtype, self._saving, self.L, self.M
+        o, dt, sv, L, M = ops, self.dtype, c["saving"], self.L, self.M
         P, n_seg, cap, rows, ng = c["P"], c["n_seg"], c["cap"], c["rows"], c["ng"]
         c["saves"] = [self._cbuf(c, f"save{l}", (rows, M), dt) if sv else None for l in range(L - 1)]
         if c["packed_rows"]:
@@ -919,7 +925,7 @@ class SwitchNeRF:
         # and h2 are saved in TOKEN order for the backward (a training forward), raw is written in token order; the tokens no expert
         # kept enter at layer "1" as zero rows (swn_route_dropped).  Replaces: the expert output's round trip through memory, the
         # 64-row tail chain (which re-streams its 192 KiB of weights from L2 for every 64 rows) and its launch.
-        o, dt, sv = ops, self.dtype, self._saving
+        o, dt, sv = ops, self.dtype, c["saving"]
         P, S, M, H2, L = c["P"], c["S"], self.M, self.H2, self.L
         c["row_of_tok"] = c["tok2row"]
         if ray_feat_ev is not None:
@@ -1031,7 +1037,7 @@ class SwitchNeRF:
         # the gate value, ReLU'd (dropped tokens -> zero rows) and saved as y;  then layer "1" -> layer "2" (+ per-ray bias)
         # The sigma / colour heads run inside that launch (swn.h: heads_raw): sigma from the staged y tile, colour from the h2 tile.  A
         # training forward still writes y, h1 and h2 (the backward reads them); an inference forward writes nothing but raw.
-        o, dt, sv = ops, self.dtype, self._saving
+        o, dt, sv, head = ops, self.dtype, c["saving"], c["head"]
         P, M, H2 = c["P"], self.M, self.H2
         fused = self._heads_fused()
         keep = sv or not fused
@@ -1049,13 +1055,13 @@ class SwitchNeRF:
         if self.affine:    # ---- heads + the per-image colour transform (models/nerf_moe.py:436-438) as their own launch
             c["raw"] = o.heads_affine_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                           sigma_noise, *c["aff_rows"])
-        elif self._coef_out is not None:   # ---- a Mega-NeRF cell training with sh_deg (DenseNeRF.forward_coef): the coefficient row itself
+        elif isinstance(head, CoefHead):   # ---- a Mega-NeRF cell training with sh_deg (DenseNeRF.forward_coef): the coefficient row itself
             c["coef_rows"] = o.heads_coef_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
-                                              sigma_noise, self.sh_deg, *self._coef_out)
-        elif self.sh_deg is not None:      # ---- heads + the spherical-harmonics contraction against the ray's direction (rendering.py:344-347)
+                                              sigma_noise, self.sh_deg, *head)
+        elif isinstance(head, ShHead):     # ---- heads + the spherical-harmonics contraction against the ray's direction (rendering.py:344-347)
             out = o.heads_sh_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
-                                 sigma_noise, c["sh_dirs"], rows_per_bias, self.sh_deg, want_coef=self._sh_want_coef)
-            c["raw"], c["coef"] = out if self._sh_want_coef else (out, None)
+                                 sigma_noise, head.dirs, rows_per_bias, self.sh_deg, want_coef=head.want_coef)
+            c["raw"], c["coef"] = out if head.want_coef else (out, None)
         elif not fused:    # ---- heads as their own launch (SWN_NO_FUSED_HEADS=1: rounds 1-2)
             c["raw"] = o.heads_fwd(c["y"], c["h2"], self.p["sigma.w"], self.p["sigma.b"], self.p["color.w"], self.p["color.b"],
                                    sigma_noise)
@@ -1509,11 +1515,7 @@ class SwitchNeRF:
         if training and self._noise is not None and sigma_noise is None and sigma_noise_std > 0:      # one value per interval
             sigma_noise = drawn = self._draw(ops.RNG_SIGMA if tag == "c" else ops.RNG_SIGMA_FINE, N * S1, self._noise["ray_base"] * S1,
                                      ops.RNG_NORMAL, float(sigma_noise_std))
-        self._saving = bool(training)      # inference: no activation saves / ReLU masks (like forward_rays)
-        try:
-            c = self._net_forward(pe, pe_dir, image_indices, N, S1, seg, sigma_noise, None, no_batch, tag)
-        finally:
-            self._saving = True
+        c = self._net_forward(pe, pe_dir, image_indices, N, S1, seg, sigma_noise, None, no_batch, tag, saving=bool(training))
         c["z_edges"] = z
         if drawn is not None:
             c["sigma_noise"] = drawn
