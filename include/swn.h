@@ -99,6 +99,13 @@ int swn_merge_samples(const float* z_fine, const float* z_coarse, const float* r
 int swn_unmerge_grad(const float* d_raw, const int32_t* order, int n_rays, int n_fine, int n_coarse, float* d_fine,
                      float* d_coarse, void* stream);
 
+/* The fine level's depths of the two-network cascade (rendering.py:237-244 with use_cascade) in one launch, one workgroup per ray:
+ *   z_fine[N,F]    (optional out) the draws of swn_sample_pdf, bit for bit, in their own order;
+ *   z_union[N,S+F] = sort(cat[z_coarse, z_fine]) on values (:244; z_coarse ascending).
+ * u[N,F] as in swn_sample_pdf (NULL = linspace).  3 <= S, 2 <= F, S + F <= 1024.  The encoding of z_union is swn_pe_from_z's.    */
+int swn_cascade_resample(const float* z_coarse, const float* weights, const float* u, int n_rays, int n_coarse, int n_fine,
+                         float* z_union, float* z_fine, void* stream);
+
 /* ---- gate: LayerNorm + fp32 router GEMV + softmax + top-1 ----------------------------------------------------
  * replaces nn.LayerNorm (models/nerf_moe.py:370-372), TopKGate logits/softmax
  * (modules/tutel_moe_ext/tutel_moe_layer_nobatch.py:105-126) and topk/gates_s (tutel_fast_dispatch.py:177-182).
@@ -747,6 +754,15 @@ int swn_ray_feat_fwd(const void* pe_dir, int dtype, int dir_stride, int in_dir, 
 int swn_step_loss(const float* rgb, const float* target, int n_values, const float* l_aux_a, int n_a, const float* l_aux_b, int n_b,
                   float l_aux_weight, const float* loss_scale_dev, float* d_rgb, float* d_l_aux_a, float* d_l_aux_b, float* out4,
                   void* stream);
+/* The loss of a two-network cascade step (runner.py:1195-1211) and its gradient seeds in one launch, summed in swn_step_loss's order:
+ *   photo = mse(rgb_fine), coarse = mse(rgb_coarse) over n_values = 3 N_rays;  loss = (photo + coarse) / 2 if coarse_photo else photo;
+ *   gate = (mean(l_aux_fine) + mean(l_aux_coarse)) / 2 (a vector with n_x = 0 counts as 0);  loss += l_aux_weight * gate;
+ *   psnr = -10 log10(photo)                                     -> out5 = {photo, coarse, gate, loss, psnr} (device, 5 floats)
+ *   d_rgb_fine / d_rgb_coarse = d loss / d rgb * s (d_rgb_coarse exact zeros without coarse_photo), d_l_aux_x = l_aux_weight / 2 / n_x * s,
+ *   s = *loss_scale_dev or 1.                                                                                               */
+int swn_cascade_loss(const float* rgb_fine, const float* rgb_coarse, const float* target, int n_values, const float* l_aux_fine, int n_fine,
+                     const float* l_aux_coarse, int n_coarse, float l_aux_weight, int coarse_photo, const float* loss_scale_dev,
+                     float* d_rgb_fine, float* d_rgb_coarse, float* d_l_aux_fine, float* d_l_aux_coarse, float* out5, void* stream);
 /* d_emb[n_images, app_dim] f32 += the rows d_feat[n] (n-th ray, leading dimension ld) of the rays with image_indices[n] == row, added in
  * ascending ray order with a fixed association: nn.Embedding's backward (models/nerf_moe.py:215-222) with run-to-run identical bits. */
 int swn_emb_grad(const float* d_feat, int ld, const void* image_indices, int indices_are_int64, int n_rays, int app_dim,

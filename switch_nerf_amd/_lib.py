@@ -73,6 +73,7 @@ SIGNATURES = {
     "swn_rng_advance": [vp, vp],
     "swn_pe_from_z": [vp, vp, i32, i32, i32, i32, vp, i32, vp],
     "swn_sample_pdf": [vp, vp, vp, i32, i32, i32, vp, vp],
+    "swn_cascade_resample": [vp, vp, vp, i32, i32, i32, vp, vp, vp],
     "swn_merge_samples": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "swn_unmerge_grad": [vp, vp, i32, i32, i32, vp, vp, vp],
     "swn_gate_fwd": [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp],
@@ -144,6 +145,7 @@ SIGNATURES = {
     "swn_wgrad": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, sz, vp],
     "swn_ray_feat_fwd": [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp],
     "swn_step_loss": [vp, vp, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, vp, vp],
+    "swn_cascade_loss": [vp, vp, vp, i32, vp, i32, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp],
     "swn_emb_grad": [vp, i32, vp, i32, i32, i32, i32, vp, vp],
     "swn_ray_feat_wgrad": [vp, vp, i32, i32, i32, vp, vp, vp, sz, vp],
     "swn_affine_ray_fwd": [vp, i32, vp, i32, vp, vp, i32, vp, vp],

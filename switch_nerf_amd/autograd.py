@@ -88,3 +88,34 @@ class RenderRaysFunction(torch.autograd.Function):
             nerf.backward(c, d_rgb, d_laux_c.to(torch.float32).contiguous())
         ctx.state = None
         return (nerf.grad.clone(),) + (None,) * 10
+
+
+class CascadeRenderFunction(torch.autograd.Function):
+    """The two-network cascade (cascade.Cascade) under autograd, over the two flat_param leaves:
+    (flat_coarse, flat_fine, cascade, rays, image_indices, S, F, chunk, perturb, perturb_rand, sigma_noise, sigma_noise_fine)
+    -> (rgb_fine [N,3], rgb_coarse [N,3], gate_loss_coarse [n_seg], gate_loss_fine [n_seg_f], depth_fine [N], depth_variance_fine [N]).
+    The backward runs each level's HIP backward into its own half's gradient buffer and hands each leaf its flat gradient, so the
+    reference's Runner loop (loss.backward() + torch.optim.Adam over both leaves) drives the cascade.  No gradient crosses the levels:
+    the fine depths come from the detached coarse weights (rendering.py:240)."""
+
+    @staticmethod
+    def forward(ctx, flat_coarse, flat_fine, cascade, rays, image_indices, S, F, chunk, perturb, perturb_rand, sigma_noise, sigma_noise_fine):
+        c, cf = cascade.forward_cascade(rays, image_indices, S, F, chunk, perturb, perturb_rand, None, sigma_noise, sigma_noise_fine,
+                                        no_batch=cascade.moe_no_batch, training=True)
+        ctx.cascade, ctx.state = cascade, (c, cf)
+        cascade._last_ctx = ctx.state
+        res = (cf["rgb"], c["rgb"], c["l_aux"], cf["l_aux"], cf["depth"], cf["depth_variance"])
+        ctx.mark_non_differentiable(res[4], res[5])
+        return res
+
+    @staticmethod
+    def backward(ctx, d_rgb_f, d_rgb_c, d_laux_c, d_laux_f, _d_depth, _d_var):
+        c, cf = ctx.state
+        f32 = lambda t: t.to(torch.float32).contiguous()
+        grads = []
+        for half, lvl, d_rgb, d_laux in ((ctx.cascade.coarse, c, d_rgb_c, d_laux_c), (ctx.cascade.fine, cf, d_rgb_f, d_laux_f)):
+            half.grad.zero_()
+            half.backward(lvl, f32(d_rgb), f32(d_laux))
+            grads.append(half.grad.clone())
+        ctx.state = None
+        return (grads[0], grads[1]) + (None,) * 10

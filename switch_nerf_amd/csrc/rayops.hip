@@ -71,6 +71,58 @@ __global__ __launch_bounds__(1024) void step_loss_kernel(const float* __restrict
   }
 }
 
+// The loss of a two-network cascade step (runner.py:1195-1211) in ONE block, reduced in step_loss_kernel's order (per-thread strided
+// double sums, tree from 512): photo = mse(rgb_fine), coarse = mse(rgb_coarse), loss = (photo + coarse) / 2 with coarse_photo, else photo;
+// gate = (mean(gl_f) + mean(gl_c)) / 2 (a null vector counts as 0), loss += wt * gate, psnr from photo.
+// out5 = {photo, coarse, gate, loss, psnr}; d_rgb_f / d_rgb_c the seeds (d_rgb_c exact zeros without coarse_photo), d_gl_* = wt / 2 / n * scale.
+__global__ __launch_bounds__(1024) void cascade_loss_kernel(const float* __restrict__ rgb_f, const float* __restrict__ rgb_c,
+                                                            const float* __restrict__ target, int n_vals, const float* __restrict__ glf, int nf,
+                                                            const float* __restrict__ glc, int nc, float wt, int coarse_photo,
+                                                            const float* __restrict__ scale_dev, float* __restrict__ d_rgb_f,
+                                                            float* __restrict__ d_rgb_c, float* __restrict__ d_glf, float* __restrict__ d_glc,
+                                                            float* __restrict__ out5) {
+  __shared__ double red[1024];
+  __shared__ double red_c[1024];
+  const float sc = scale_dev ? scale_dev[0] : 1.f;
+  const float k = 2.0f / (float)n_vals * sc;
+  const float kf = coarse_photo ? 0.5f * k : k, kc = coarse_photo ? 0.5f * k : 0.f;
+  double s = 0.0, s_c = 0.0;
+  for (int i = threadIdx.x; i < n_vals; i += 1024) {
+    const float t = target[i];
+    const float d = rgb_f[i] - t, e = rgb_c[i] - t;
+    s += (double)d * (double)d;
+    s_c += (double)e * (double)e;
+    d_rgb_f[i] = d * kf;
+    d_rgb_c[i] = coarse_photo ? e * kc : 0.f;
+  }
+  red[threadIdx.x] = s;
+  red_c[threadIdx.x] = s_c;
+  __syncthreads();
+  for (int o = 512; o >= 1; o >>= 1) {
+    if (threadIdx.x < o) {
+      red[threadIdx.x] += red[threadIdx.x + o];
+      red_c[threadIdx.x] += red_c[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < nf; i += 1024) d_glf[i] = wt * 0.5f / (float)nf * sc;
+  for (int i = threadIdx.x; i < nc; i += 1024) d_glc[i] = wt * 0.5f / (float)nc * sc;
+  if (threadIdx.x == 0) {
+    const float photo = (float)(red[0] / (double)n_vals);
+    const float coarse = (float)(red_c[0] / (double)n_vals);
+    double gf = 0.0, gc = 0.0;
+    for (int i = 0; i < nf; ++i) gf += glf[i];
+    for (int i = 0; i < nc; ++i) gc += glc[i];
+    const float mf = nf > 0 ? (float)(gf / (double)nf) : 0.f, mc = nc > 0 ? (float)(gc / (double)nc) : 0.f;
+    const float gate = 0.5f * (mf + mc);
+    out5[0] = photo;
+    out5[1] = coarse;
+    out5[2] = gate;
+    out5[3] = (coarse_photo ? 0.5f * (photo + coarse) : photo) + wt * gate;
+    out5[4] = -10.0f * log10f(photo);
+  }
+}
+
 // d_emb[a][:] += sum over the rays n with image_indices[n] == a, in ascending n, of d_feat[n][:]   (the appearance embedding's gradient,
 // nn.Embedding's backward: models/nerf_moe.py:215-222).  One block per embedding row: the block walks the ray indices in tiles of 1024,
 // compacts the matching rays IN ORDER (wave scan of the per-thread match counts), and sums their rows with a fixed association
@@ -210,6 +262,20 @@ extern "C" int swn_step_loss(const float* rgb, const float* target, int n_values
   SWN_CHECK(n_values > 0 && n_a > 0 && n_b >= 0 && (n_b == 0 || (l_aux_b && d_l_aux_b)), "swn_step_loss: bad sizes");
   hipLaunchKernelGGL(step_loss_kernel, dim3(1), dim3(1024), 0, as_stream(stream), rgb, target, n_values, l_aux_a, n_a, l_aux_b, n_b,
                      l_aux_weight, loss_scale_dev, d_rgb, d_l_aux_a, d_l_aux_b, out4);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cascade_loss(const float* rgb_fine, const float* rgb_coarse, const float* target, int n_values, const float* l_aux_fine,
+                                int n_fine, const float* l_aux_coarse, int n_coarse, float l_aux_weight, int coarse_photo,
+                                const float* loss_scale_dev, float* d_rgb_fine, float* d_rgb_coarse, float* d_l_aux_fine,
+                                float* d_l_aux_coarse, float* out5, void* stream) {
+  SWN_CHECK(rgb_fine && rgb_coarse && target && d_rgb_fine && d_rgb_coarse && out5, "swn_cascade_loss: null pointer");
+  SWN_CHECK(n_values > 0 && n_fine >= 0 && n_coarse >= 0 && (n_fine == 0 || (l_aux_fine && d_l_aux_fine)) &&
+                (n_coarse == 0 || (l_aux_coarse && d_l_aux_coarse)), "swn_cascade_loss: bad sizes");
+  hipLaunchKernelGGL(cascade_loss_kernel, dim3(1), dim3(1024), 0, as_stream(stream), rgb_fine, rgb_coarse, target, n_values, l_aux_fine,
+                     n_fine, l_aux_coarse, n_coarse, l_aux_weight, coarse_photo, loss_scale_dev, d_rgb_fine, d_rgb_coarse, d_l_aux_fine,
+                     d_l_aux_coarse, out5);
   SWN_LAUNCH_CHECK();
   return 0;
 }

@@ -2,6 +2,7 @@
 //   swn_sample_pdf    - _sample_pdf / _sample_cdf          (/root/reference/switch_nerf/rendering.py:587-637)
 //   swn_merge_samples - sort(cat[z_fine, z_coarse]) + gather of the raw (rgb, sigma) outputs   (rendering.py:419-433)
 //   swn_unmerge_grad  - backward of that gather
+//   swn_cascade_resample - the cascade's fine level: draws + sort(cat[z_coarse, z_fine])   (rendering.py:237-244)
 // One workgroup per ray; the per-ray arrays (<= 1024 floats) live in LDS.
 #include "common.hpp"
 
@@ -9,15 +10,12 @@ namespace swn {
 
 // pdf = (w + 1e-8) / sum; cdf = [0, cumsum(pdf)]; inds = searchsorted(cdf, u, right=True); lerp inside the bin.
 // z [N,S] coarse depths, w [N,S] coarse weights: bins = mid points of z (S-1), weights used = w[1:-1] (S-2).
-__global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict__ z, const float* __restrict__ w,
-                                                         const float* __restrict__ u_in, int N, int S, int F,
-                                                         float* __restrict__ z_fine) {
-  __shared__ float bins[1024];
-  __shared__ float cdf[1024];
-  __shared__ float red[256];
-  const int ray = blockIdx.x, t = threadIdx.x;
-  const float* zr = z + (long)ray * S;
-  const float* wr = w + (long)ray * S;
+// One ray's draws by a block of 256 threads: zr / wr its S coarse depths / weights, ur its F uniforms (null: the linspace), out[0, F)
+// the fine depths (global memory or LDS).  Shared by swn_sample_pdf and swn_cascade_resample, which therefore draw the same bits.
+// bins / cdf: 1024 floats, red: 256.
+__device__ __forceinline__ void sample_pdf_ray(const float* __restrict__ zr, const float* __restrict__ wr, const float* __restrict__ ur,
+                                               int S, int F, float* bins, float* cdf, float* red, float* out) {
+  const int t = threadIdx.x;
   const int nb = S - 1;   // bins
   const int nw = S - 2;   // weights
   for (int i = t; i < nb; i += 256) bins[i] = 0.5f * (zr[i] + zr[i + 1]);          // rendering.py:238
@@ -42,7 +40,7 @@ __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict
   for (int j = t; j < F; j += 256) {
     // det: torch.linspace(0, 1, F) (symmetric formula of torch: start + i*step for the first half, end - (F-1-i)*step after)
     float u;
-    if (u_in) u = u_in[(long)ray * F + j];
+    if (ur) u = ur[j];
     else {
       const float step = 1.f / (float)(F - 1);
       u = (j < F / 2) ? (float)j * step : 1.f - (float)(F - 1 - j) * step;
@@ -58,8 +56,73 @@ __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict
     const float bb = bins[below], ba = bins[above];
     float denom = ca - cb;
     if (denom < 1e-8f) denom = 1.f;                                                    // :631
-    z_fine[(long)ray * F + j] = bb + (u - cb) / denom * (ba - bb);                     // :636
+    out[j] = bb + (u - cb) / denom * (ba - bb);                                        // :636
   }
+}
+
+__global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict__ z, const float* __restrict__ w,
+                                                         const float* __restrict__ u_in, int N, int S, int F,
+                                                         float* __restrict__ z_fine) {
+  __shared__ float bins[1024];
+  __shared__ float cdf[1024];
+  __shared__ float red[256];
+  const long ray = blockIdx.x;
+  sample_pdf_ray(z + ray * S, w + ray * S, u_in ? u_in + ray * F : nullptr, S, F, bins, cdf, red, z_fine + ray * F);
+}
+
+// The fine level's depths of the two-network cascade in one launch (rendering.py:237-244 with use_cascade): the F draws of
+// sample_pdf_ray and their ascending union with the S coarse depths (:244, sort(cat) on values).  One workgroup of 256 threads per ray.
+// The coarse depths arrive sorted, so only the F draws are sorted (bitonic, keys only, padded with +inf to n_pad) and the two runs are
+// merged by rank: coarse i goes to i + #{fine < it}, fine j (sorted) to j + #{coarse <= it} - a permutation of [0, S + F) whatever the
+// ties.  No atomics; every order is fixed.  LDS: 17 KiB per workgroup (bins / coarse, cdf, fine, union, 256 partial sums).
+__global__ __launch_bounds__(256) void cascade_resample_kernel(const float* __restrict__ z, const float* __restrict__ w,
+                                                               const float* __restrict__ u_in, int N, int S, int F, int n_pad,
+                                                               float* __restrict__ z_union, float* __restrict__ z_fine) {
+  constexpr int NT = 256;
+  __shared__ float bins[1024];      // the pdf's bins, then the coarse depths
+  __shared__ float cdf[1024];
+  __shared__ float red[256];
+  __shared__ float fine[1024];
+  __shared__ float uni[1024];
+  const long ray = blockIdx.x;
+  const int t = threadIdx.x, U = S + F;
+  const float* zr = z + ray * S;
+  sample_pdf_ray(zr, w + ray * S, u_in ? u_in + ray * F : nullptr, S, F, bins, cdf, red, fine);
+  for (int i = F + t; i < n_pad; i += NT) fine[i] = __builtin_inff();
+  __syncthreads();                  // (every search of bins / cdf is done: bins is free)
+  float* zc = bins;
+  for (int i = t; i < S; i += NT) zc[i] = zr[i];
+  if (z_fine)
+    for (int j = t; j < F; j += NT) z_fine[ray * F + j] = fine[j];
+  __syncthreads();                  // (the draws are read out in their own order before the sort moves them)
+  for (int size = 2; size <= n_pad; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = t; i < n_pad / 2; i += NT) {
+        const int lo = (i / stride) * stride * 2 + (i % stride), hi = lo + stride;
+        const bool up = ((lo & size) == 0);
+        const float a = fine[lo], b = fine[hi];
+        if ((a > b) == up) { fine[lo] = b; fine[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = t; i < U; i += NT) {
+    const bool coarse = i < S;
+    const int own = coarse ? i : i - S, n_other = coarse ? F : S;
+    const float* other = coarse ? fine : zc;
+    const float k = coarse ? zc[own] : fine[own];
+    int lo = 0, hi = n_other;       // coarse: the first fine >= k (lower bound); fine: the first coarse > k (upper bound)
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      const float o = other[mid];
+      if (coarse ? (o < k) : (o <= k)) lo = mid + 1; else hi = mid;
+    }
+    uni[own + lo] = k;              // own < its run's length and lo <= the other's: own + lo < S + F
+  }
+  // (NaN weights give NaN draws: the ranks then form no permutation and z_union keeps stale LDS in the slots never written - every
+  //  write stays in bounds)
+  __syncthreads();
+  for (int i = t; i < U; i += NT) z_union[ray * U + i] = uni[i];
 }
 
 // Bitonic sort of (key, index) pairs in LDS, ascending; n_pad = power of two >= n, padded with +inf.
@@ -124,6 +187,20 @@ extern "C" int swn_sample_pdf(const float* z_coarse, const float* weights, const
   SWN_CHECK(n_coarse >= 3 && n_coarse <= 1024 && n_fine >= 2, "swn_sample_pdf: 3 <= coarse samples <= 1024, fine >= 2");
   hipLaunchKernelGGL(sample_pdf_kernel, dim3(n_rays), dim3(256), 0, as_stream(stream), z_coarse, weights, u, n_rays, n_coarse,
                      n_fine, z_fine);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cascade_resample(const float* z_coarse, const float* weights, const float* u, int n_rays, int n_coarse, int n_fine,
+                                    float* z_union, float* z_fine, void* stream) {
+  SWN_CHECK(z_coarse && weights && z_union, "swn_cascade_resample: null pointer");
+  SWN_CHECK(n_rays >= 0 && n_coarse >= 3 && n_fine >= 2 && (long)n_coarse + n_fine <= 1024,
+            "swn_cascade_resample: coarse samples >= 3, fine >= 2, coarse + fine <= 1024 (got %d + %d)", n_coarse, n_fine);
+  if (n_rays == 0) return 0;
+  int n_pad = 2;
+  while (n_pad < n_fine) n_pad <<= 1;
+  hipLaunchKernelGGL(cascade_resample_kernel, dim3(n_rays), dim3(256), 0, as_stream(stream), z_coarse, weights, u, n_rays, n_coarse,
+                     n_fine, n_pad, z_union, z_fine);
   SWN_LAUNCH_CHECK();
   return 0;
 }

@@ -18,6 +18,8 @@ def _refuse_sh(model, who: str):
     """Graph capture of a spherical-harmonics model is not built (its per-pass directions are handed over on the host side)."""
     if getattr(model, "sh_deg", None) is not None:
         raise NotImplementedError(f"{who}: graph capture of an sh_deg model is not built; run it eagerly")
+    if getattr(model, "is_cascade", False):      # (cascade.Cascade: two models, two optimizer states)
+        raise NotImplementedError(f"{who}: graph capture of a two-network Cascade is not built; run it eagerly")
 
 
 def cached_graph(cache: dict, key, make):

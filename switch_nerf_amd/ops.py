@@ -175,6 +175,16 @@ def sample_pdf(z_coarse, weights, u, n_fine: int):
     return zf
 
 
+def cascade_resample(z_coarse, weights, u, n_fine: int, want_z_fine=False):
+    """The cascade's fine depths in one launch (swn_cascade_resample) -> (z_union [N, S+F], z_fine [N, F] or None)."""
+    n, S = z_coarse.shape
+    dev = z_coarse.device
+    zu = torch.empty(n, S + n_fine, dtype=torch.float32, device=dev)
+    zf = torch.empty(n, n_fine, dtype=torch.float32, device=dev) if want_z_fine else None
+    call("swn_cascade_resample", _p(z_coarse), _p(weights), _p(u), n, S, n_fine, _p(zu), _p(zf), _stream())
+    return zu, zf
+
+
 def merge_samples(z_fine, z_coarse, raw_fine, raw_coarse):
     n, F = z_fine.shape
     S = z_coarse.shape[1]
@@ -779,6 +789,19 @@ def step_loss(rgb, target, l_aux_a, l_aux_b, wt: float, loss_scale_dev=None):
     call("swn_step_loss", _p(rgb), _p(target), rgb.numel(), _p(l_aux_a), l_aux_a.numel(), _p(l_aux_b), 0 if l_aux_b is None else l_aux_b.numel(),
          float(wt), _p(loss_scale_dev), _p(d_rgb), _p(d_a), _p(d_b), _p(out4), _stream())
     return out4, d_rgb, d_a, d_b
+
+
+def cascade_loss(rgb_fine, rgb_coarse, target, l_aux_fine, l_aux_coarse, wt: float, coarse_photo: bool = True, loss_scale_dev=None):
+    """-> (out5 = [photo, coarse_loss, gate_loss, loss, psnr] on the device, d_rgb_fine, d_rgb_coarse, d_l_aux_fine or None,
+    d_l_aux_coarse or None): the loss of a cascade step (swn_cascade_loss); either gate-loss vector may be None."""
+    d_f, d_c = torch.empty_like(rgb_fine), torch.empty_like(rgb_coarse)
+    d_lf = torch.empty_like(l_aux_fine) if l_aux_fine is not None else None
+    d_lc = torch.empty_like(l_aux_coarse) if l_aux_coarse is not None else None
+    out5 = torch.empty(5, dtype=torch.float32, device=rgb_fine.device)
+    call("swn_cascade_loss", _p(rgb_fine), _p(rgb_coarse), _p(target), rgb_fine.numel(), _p(l_aux_fine),
+         0 if l_aux_fine is None else l_aux_fine.numel(), _p(l_aux_coarse), 0 if l_aux_coarse is None else l_aux_coarse.numel(), float(wt),
+         int(bool(coarse_photo)), _p(loss_scale_dev), _p(d_f), _p(d_c), _p(d_lf), _p(d_lc), _p(out5), _stream())
+    return out5, d_f, d_c, d_lf, d_lc
 
 
 def sample_z(rays, t_steps, perturb_rand, perturb: float, n_samples: int):

@@ -1,5 +1,6 @@
 """Mirror of the reference's rendering.render_rays (/root/reference/switch_nerf/rendering.py:15-196): SwitchNeRF (or
-DenseNeRF) model, optional dense background model behind the foreground bound (background.py), no cascade;
+DenseNeRF) model, optional dense background model behind the foreground bound (background.py), or a two-network cascade.Cascade
+(hparams.use_cascade: _render_rays_cascade);
 fine_samples = 0 (coarse pass composited) or fine_samples > 0 (hierarchical: coarse weights -> importance samples -> fine
 pass -> merged compositing).
 
@@ -107,8 +108,9 @@ def _check_sh(nerf, bg_nerf, hparams):
 def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch.Tensor], hparams, sphere_center=None,
                 sphere_radius=None, get_depth: bool = True, get_depth_variance: bool = True,
                 get_bg_fg_rgb: bool = False) -> Tuple[Dict[str, torch.Tensor], bool]:
-    if getattr(hparams, "use_cascade", False):
-        raise NotImplementedError("use_cascade is outside the hot path")
+    is_mega = getattr(nerf, "is_mega_nerf", False) or getattr(bg_nerf, "is_mega_nerf", False)      # (mega.render_rays refuses use_cascade itself)
+    if getattr(nerf, "is_cascade", False) or (getattr(hparams, "use_cascade", False) and not is_mega):      # the two-network cascade: cascade.py
+        return _render_rays_cascade(nerf, bg_nerf, rays, image_indices, hparams, get_depth, get_depth_variance), False
     if getattr(nerf, "is_mega_nerf", False) or getattr(bg_nerf, "is_mega_nerf", False):      # the spatial-cell model (--container_path): mega.py
         from . import mega
         return mega.render_rays(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, sphere_radius, get_depth,
@@ -207,6 +209,73 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
         res["sigma_coarse"] = c["raw"][:, 3].view(N, S)
     _point_keys(res, hparams, "coarse", rays, c["raw"], c["z"], c["raw"])
     return res, False
+
+
+def _render_rays_cascade(nerf, bg_nerf, rays, image_indices, hparams, get_depth, get_depth_variance):
+    """hparams.use_cascade (rendering.py:227-268, :333-342): nerf is a cascade.Cascade.  Result keys are the reference's: rgb_coarse,
+    gate_loss_coarse and, with fine_samples > 0, rgb_fine, depth_fine, depth_variance_fine, gate_loss_fine (sigma_fine in the [N, S + F]
+    shape); with fine_samples == 0 the coarse keys only, depth_coarse / depth_variance_coarse among them."""
+    if not getattr(nerf, "is_cascade", False):
+        raise NotImplementedError("hparams.use_cascade needs the two-network model: wrap the coarse and the fine model in "
+                                  "switch_nerf_amd.cascade.Cascade(coarse, fine)")
+    if not getattr(hparams, "use_cascade", False):
+        raise NotImplementedError("the model is a Cascade but hparams.use_cascade is off: a Cascade renders with use_cascade only")
+    if bg_nerf is not None:
+        raise NotImplementedError("Cascade: a background model (bg_nerf) is not built for the two-network cascade")
+    if _want_points(hparams):
+        raise NotImplementedError("Cascade: the per-sample point outputs (return_pts*) are not built for the two-network cascade")
+    if getattr(hparams, "device_noise_seed", None) is not None:
+        raise NotImplementedError("Cascade: seeded device noise (device_noise_seed) is not built for the two-network cascade")
+    for h in nerf.halves():
+        _check_affine(h, hparams)
+        _check_sh(h, None, hparams)
+    N, S, F = rays.shape[0], hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
+    training = nerf.training
+    chunk = min(hparams.model_chunk_size, N * S)
+    perturb = hparams.perturb if training else 0
+    use_noise = bool(getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and training)
+    if image_indices is None:
+        image_indices = torch.zeros(N, dtype=torch.long, device=rays.device)
+    pr = torch.rand(N, S, device=rays.device) if perturb > 0 else None
+    noise = torch.randn(N * S, device=rays.device) * hparams.sigma_noise_std if use_noise else None
+    noise_f = torch.randn(N * (S + F), device=rays.device) * hparams.sigma_noise_std if (use_noise and F > 0) else None
+    rays = rays.contiguous()
+    nerf._check_runtime()
+    if training and torch.is_grad_enabled() and any(getattr(h, "hash", None) is not None for h in nerf.halves()):
+        raise NotImplementedError("Cascade: training hash-grid halves under autograd is not built (the autograd bridge carries no table "
+                                  "gradient); use Cascade.train_step, or render under torch.no_grad()")
+    if F > 0 and nerf.fine is None:
+        raise ValueError("Cascade: fine_samples > 0 needs a fine half")
+    if training and torch.is_grad_enabled():
+        # training under autograd (autograd.py): one node over both levels' HIP forward; its backward fills each half's flat_param.grad
+        from .autograd import CascadeRenderFunction, RenderRaysFunction
+        if F > 0:
+            rgb_f, rgb_c, gl_c, gl_f, depth, dvar = CascadeRenderFunction.apply(nerf.coarse.flat_param, nerf.fine.flat_param, nerf, rays,
+                                                                                image_indices, S, F, chunk, float(perturb), pr, noise, noise_f)
+            c, cf = nerf._last_ctx
+        else:
+            rgb_c, gl_c, _, depth, dvar = RenderRaysFunction.apply(nerf.coarse.flat_param, nerf.coarse, rays, image_indices, S, 0, chunk,
+                                                                   float(perturb), pr, noise, None)
+            (c,), cf = nerf.coarse._last_ctx, None
+    else:
+        c, cf = nerf.forward_cascade(rays, image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
+                                     no_batch=nerf.moe_no_batch, training=training)
+        rgb_c, gl_c = c["rgb"], c["l_aux"]
+        top = cf if cf is not None else c
+        rgb_f, gl_f, depth, dvar = top["rgb"], top["l_aux"], top["depth"], top["depth_variance"]
+    res = {"rgb_coarse": rgb_c, "gate_loss_coarse": gl_c}
+    typ = "fine" if F > 0 else "coarse"
+    if F > 0:
+        res["rgb_fine"], res["gate_loss_fine"] = rgb_f, gl_f
+    if get_depth:
+        res[f"depth_{typ}"] = depth
+    if get_depth_variance:
+        res[f"depth_variance_{typ}"] = dvar
+    if getattr(hparams, "return_sigma", False):
+        res["sigma_coarse"] = c["raw"][:, 3].view(N, S)
+        if F > 0:
+            res["sigma_fine"] = cf["raw"][:, 3].view(N, S + F)
+    return res
 
 
 def _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get_depth, get_depth_variance):
