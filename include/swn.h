@@ -831,6 +831,18 @@ int swn_heads_sh_bwd(const void* y, const void* h2, int dtype, const float* w_co
  * (1/world_size after a sum all-reduce).  Also refreshes the compute copies: shadow (dtype) same layout.         */
 int swn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow, int dtype,
                   long n, float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);
+/* Gradient accumulation (--accumulation_steps, runner.py:677-690).  swn_grad_accum: acc[i] = acc[i] + grad[i] * scale over n >= 1
+ * fp32 elements, the product and the sum rounded separately (no FMA) - the result is fp32 `acc + grad * scale`, bit for bit.
+ * swn_adam_accum_step: the last micro-step of a window in one pass.  Per element total = grad ? acc + grad * accum_scale : acc
+ * (rounded as in swn_grad_accum), then exactly swn_adam_step's update with total * grad_scale as the gradient (same arithmetic, same
+ * bits as swn_grad_accum followed by swn_adam_step on acc), then acc[i] = 0: the last gradient is never written to acc, acc is read
+ * once and leaves cleared for the next window.  grad may be NULL (acc already holds the whole window, e.g. after an all-reduce).
+ * Both take any 4-byte-aligned pointers (slices of the flat buffers): 16-byte accesses where every buffer of the call is 16-byte
+ * aligned at the same element, single elements before and after that body - or throughout, when the buffers' offsets differ.  */
+int swn_grad_accum(float* acc, const float* grad, long n, float scale, void* stream);
+int swn_adam_accum_step(float* param, float* acc, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow, int dtype,
+                        long n, float lr, float beta1, float beta2, float eps, int step, float accum_scale, float grad_scale,
+                        void* stream);
 int swn_cast(const float* in, void* out, int dtype, long n, void* stream);
 /* out[b][c][r] = in[b][r][c]  (fp32 master -> dtype compute copy, transposed) */
 int swn_cast_transpose(const float* in, void* out, int dtype, int batch, int rows, int cols, void* stream);

@@ -169,6 +169,8 @@ SIGNATURES = {
     "swn_heads_coef_bwd_workspace_bytes": [i32, i32, i32, i32, C.POINTER(sz)],
     "swn_heads_coef_bwd": [vp, vp, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
     "swn_adam_step": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, f32, vp],
+    "swn_grad_accum": [vp, vp, i64, f32, vp],
+    "swn_adam_accum_step": [vp, vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, f32, f32, vp],
     "swn_cast": [vp, vp, i32, i64, vp],
     "swn_cast_transpose": [vp, vp, i32, i32, i32, i32, vp],
 }

@@ -325,12 +325,86 @@ class BackgroundScene:
     _UNBOUNDED = "Not all your cameras are bounded by the unit sphere; please make sure the cameras are normalized properly!"
 
     def train_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, optimizer_step=True, grad_allreduce=None,
-                   fine_samples=0, bg_capacity=None, **kw):
+                   fine_samples=0, bg_capacity=None, should_accumulate=None, **kw):
         """Runner._training_step with a background model (runner.py:1077-1123): loss = mse(rgb) + wt * gate loss of the
         foreground MoE (the dense background model has none); both models take an Adam step (runner.py:305-318 builds one
-        optimizer over the parameters of both).  = grad_step + apply_step.  bg_capacity: the padded form (module doc)."""
+        optimizer over the parameters of both).  = grad_step + apply_step.  bg_capacity: the padded form (module doc).
+        should_accumulate: with gradient accumulation on (set_accumulation), see apply_step."""
+        if self.accum_steps > 1 and bg_capacity is not None:
+            raise NotImplementedError(self._ACCUM_PADDED)
         res = self.grad_step(rgbs, rays, image_indices, n_samples, seg_tokens, perturb, fine_samples, bg_capacity, **kw)
-        return self.apply_step(res, optimizer_step, grad_allreduce)
+        return self.apply_step(res, optimizer_step, grad_allreduce, should_accumulate=should_accumulate)
+
+    # ------------------------------------------------------------------------------------------ gradient accumulation
+    _ACCUM_PADDED = ("BackgroundScene: gradient accumulation (set_accumulation) is built for the compact eager step only, not for the "
+                     "padded form (bg_capacity=) or GraphedBackgroundStep")
+
+    @property
+    def accum_steps(self) -> int:
+        return self.nerf.accum_steps
+
+    def set_accumulation(self, steps: int):
+        """SwitchNeRF.set_accumulation on both models: one window over the two, each with its own buffer."""
+        for m in (self.nerf, self.bg):
+            m.set_accumulation(steps)
+
+    def _apply_step_accum(self, res, optimizer_step, grad_allreduce, should_accumulate):
+        """apply_step with accumulation on, compact form (runner.py:677-690).  The window is the foreground model's.  An accumulating
+        micro-step adds both gradients, divided by A, into the models' buffers (the background's only when the batch had background
+        rays: its gradient is zero otherwise).  On the last micro-step the reference's rule is kept exactly: THAT batch's
+        bg_nerf_rays_present decides whether the background optimizer steps (runner.py:683); if it does not, the window's
+        accumulated background gradient is discarded, because zero_grad follows anyway (:689-690)."""
+        nerf, bg = self.nerf, self.bg
+        ctx = res["ctx"]
+        if ctx.get("C") is not None:
+            raise NotImplementedError(self._ACCUM_PADDED)
+        import torch.distributed as dist
+        distributed = grad_allreduce is not None or (dist.is_available() and dist.is_initialized())
+        bg_present = True if distributed else ctx["Nb"] > 0
+        inv = 1.0 / nerf.accum_steps
+        accumulates = nerf._accumulates(should_accumulate) or not optimizer_step
+        bg._micro = nerf._micro
+        stepped = False
+        if accumulates:
+            ops.grad_accum(nerf.accum, nerf.grad, inv)
+            if ctx["Nb"] > 0:
+                ops.grad_accum(bg.accum, bg.grad, inv)
+        elif grad_allreduce is None and self.loss_scaler is None:
+            for m in [nerf] + ([bg] if bg_present else []):
+                m.step_count += 1
+                ops.adam_accum_step(m.flat, m.accum, m.grad, m.m, m.v, None, m.step_count, m.lr, accum_scale=inv)
+                m.refresh_compute_copies()
+            if not bg_present:
+                bg.accum.zero_()
+            stepped = True
+        else:
+            models = [nerf] + ([bg] if bg_present else [])
+            scale = {}
+            for m in (nerf, bg):
+                ops.grad_accum(m.accum, m.grad, inv)
+                scale[id(m)] = grad_allreduce(m._allreduce_view()) if grad_allreduce is not None else 1.0
+            found = {id(m): False for m in (nerf, bg)}
+            if self.loss_scaler is not None:               # (the shared scaler: apply_step)
+                for m in models:
+                    found[id(m)] = m._found_inf()
+                self.loss_scaler.update(any(found.values()))
+                for m in (nerf, bg):
+                    m._loss_scale_tensor()
+            for m in (nerf, bg):
+                if m in models and not found[id(m)]:
+                    sc = scale[id(m)]
+                    if self.loss_scaler is not None:
+                        sc /= m._applied_loss_scale
+                    m.step_count += 1
+                    ops.adam_accum_step(m.flat, m.accum, None, m.m, m.v, None, m.step_count, m.lr, grad_scale=sc)
+                    m.refresh_compute_copies()
+                    stepped = True
+                else:
+                    m.accum.zero_()
+        self._noise_advance()
+        res["bg_nerf_rays_present"] = bg_present
+        res["optimizer_stepped"] = stepped
+        return res
 
     def grad_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, fine_samples=0, bg_capacity=None, **kw):
         """Forward + loss + backward of both models: fills both gradients (zeroed first) and returns train_step's dict without
@@ -378,7 +452,7 @@ class BackgroundScene:
                                f"{ctx['C']}: the step was computed without the surplus rays and is not applied; raise bg_capacity "
                                f"(at most the batch's {ctx['N']} rays)")
 
-    def apply_step(self, res, optimizer_step=True, grad_allreduce=None, refresh=None, advance=True):
+    def apply_step(self, res, optimizer_step=True, grad_allreduce=None, refresh=None, advance=True, should_accumulate=None):
         """The tail both forms of the step share: gradient all-reduce, the shared loss scaler, both Adam steps under the bg_present
         rule, the advance of the noise counter.  -> res with "bg_nerf_rays_present".
         Padded form: starts with the noise advance (advance=False: it was captured with the step) and the readback of (n_bg, n_out);
@@ -386,6 +460,10 @@ class BackgroundScene:
         (the noise counter has advanced: that step's draws are skipped).
         refresh: a replacement for BOTH models' refresh_compute_copies (the replay of their captured graph), run once."""
         nerf, bg = self.nerf, self.bg
+        if self.accum_steps > 1:             # gradient accumulation (set_accumulation): the compact eager form only
+            if refresh is not None or not advance:
+                raise NotImplementedError(self._ACCUM_PADDED)
+            return self._apply_step_accum(res, optimizer_step, grad_allreduce, should_accumulate)
         ctx = res["ctx"]
         padded = ctx.get("C") is not None
         if padded:

@@ -205,11 +205,57 @@ class Cascade:
         return dict(loss=out5[3], photo_loss=out5[0], coarse_loss=out5[1], gate_loss=out5[2], psnr=out5[4],
                     depth_variance=cf["depth_variance"].mean(), ctx=c, ctx_fine=cf, rgb=cf["rgb"], rgb_coarse=c["rgb"], depth=cf["depth"])
 
-    def apply_step(self, grad_allreduce=None, optimizer_step=True):
+    @property
+    def accum_steps(self) -> int:
+        return self.coarse.accum_steps
+
+    def set_accumulation(self, steps: int):
+        """SwitchNeRF.set_accumulation on both halves: ONE window (the coarse half's micro-step index) and one scale over the two,
+        each half with its own buffer."""
+        for h in self.halves():
+            h.set_accumulation(steps)
+
+    def _apply_step_accum(self, optimizer_step, should_accumulate) -> bool:
+        """apply_step with accumulation on (SwitchNeRF._apply_step_accum over the two halves) -> whether the optimizers stepped."""
+        halves = self.halves()
+        inv = 1.0 / self.accum_steps
+        accumulates = self.coarse._accumulates(should_accumulate) or not optimizer_step
+        for h in halves:
+            h._micro = self.coarse._micro
+        if accumulates:
+            for h in halves:
+                ops.grad_accum(h.accum, h.grad, inv)
+            return False
+        if self.loss_scaler is None:
+            for h in halves:
+                h.step_count += 1
+                ops.adam_accum_step(h.flat, h.accum, h.grad, h.m, h.v, None, h.step_count, h.lr, accum_scale=inv)
+                h.refresh_compute_copies()
+            return True
+        for h in halves:
+            ops.grad_accum(h.accum, h.grad, inv)
+        bad = any([h._found_inf() for h in halves])          # (on the buffers; each records the scale its backwards used)
+        self.loss_scaler.update(bad)
+        for h in halves:
+            h._loss_scale_tensor()
+        for h in halves:
+            if bad:
+                h.accum.zero_()
+            else:
+                h.step_count += 1
+                ops.adam_accum_step(h.flat, h.accum, None, h.m, h.v, None, h.step_count, h.lr,
+                                    grad_scale=1.0 / self.coarse._applied_loss_scale)
+                h.refresh_compute_copies()
+        return not bad
+
+    def apply_step(self, grad_allreduce=None, optimizer_step=True, should_accumulate=None):
         """One Adam step per half, each with its own step count.  fp16: found-inf is the OR over the halves, the one scaler is updated
-        once and both halves skip - or take - the step together."""
+        once and both halves skip - or take - the step together.  With gradient accumulation on (set_accumulation) -> whether the
+        optimizers stepped (should_accumulate: SwitchNeRF.apply_step)."""
         if grad_allreduce is not None:
             _refuse("expert or data parallelism (grad_allreduce)")
+        if self.accum_steps > 1:
+            return self._apply_step_accum(optimizer_step, should_accumulate)
         if not optimizer_step:
             return
         scale = 1.0
@@ -229,14 +275,16 @@ class Cascade:
 
     def train_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, perturb_rand=None, sigma_noise=None,
                    optimizer_step=True, routing_override=None, grad_allreduce=None, fine_samples=0, fine_u=None, sigma_noise_fine=None,
-                   sigma_noise_std=0.0, coarse_photo=True):
+                   sigma_noise_std=0.0, coarse_photo=True, should_accumulate=None):
         if fine_samples <= 0:
             if grad_allreduce is not None:
                 _refuse("expert or data parallelism (grad_allreduce)")
             self._check_runtime()
             return self.coarse.train_step(rgbs, rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise,
-                                          optimizer_step)
+                                          optimizer_step, should_accumulate=should_accumulate)
         res = self.grad_step(rgbs, rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise, routing_override,
                              fine_samples, fine_u, sigma_noise_fine, sigma_noise_std=sigma_noise_std, coarse_photo=coarse_photo)
-        self.apply_step(grad_allreduce, optimizer_step)
+        stepped = self.apply_step(grad_allreduce, optimizer_step, should_accumulate=should_accumulate)
+        if self.accum_steps > 1:
+            res["optimizer_stepped"] = stepped
         return res

@@ -3,6 +3,7 @@
 // Adam.  One 64-lane wave per token/ray row, 16-byte accesses, wave shuffles for the reductions.
 #include <stdarg.h>
 #include "common.hpp"
+#include "adam.hpp"
 #include "pe_store.hpp"
 #include "philox.hpp"
 #include "row16.hpp"
@@ -971,13 +972,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float* __restrict__ v, T* __restrict__ shadow, long n, float lr, float b1,
                                                    float b2, float eps, float bc1, float bc2s, float gscale) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    const float pi = adam_update(g[i], gscale, p[i], mi, vi, lr, b1, b2, eps, bc1, bc2s);   // adam.hpp: shared with swn_adam_accum_step
     m[i] = mi;
     v[i] = vi;
-    const float denom = sqrtf(vi) / bc2s + eps;  // torch.optim.Adam: (sqrt(v) / sqrt(bias_correction2)) + eps
-    const float pi = p[i] - (lr / bc1) * (mi / denom);
     p[i] = pi;
     if (shadow) ElemIO<T>::st(shadow + i, pi);
   }

@@ -108,7 +108,9 @@ class GraphedTrainStep:
             model.refresh_compute_copies()
         model.profile = was_profile
 
-    def __call__(self, rgbs=None, rays=None, image_indices=None, grad_allreduce=None, optimizer_step=True):
+    def __call__(self, rgbs=None, rays=None, image_indices=None, grad_allreduce=None, optimizer_step=True, should_accumulate=None):
+        """should_accumulate: gradient accumulation (SwitchNeRF.set_accumulation) - passed to apply_step; the captured graphs are the
+        same, the accumulate launch and the fused last step run eagerly behind the replay."""
         m = self.model
         if rgbs is not None:
             self.rgbs.copy_(rgbs)
@@ -119,13 +121,15 @@ class GraphedTrainStep:
         self.graph.replay()
         ar = grad_allreduce
         if self.graph_b is not None:
-            if ar is not None and hasattr(ar, "begin"):
+            if ar is not None and hasattr(ar, "begin") and m.accum_steps == 1:      # (accumulating: ONE all-reduce, of the buffer, in apply_step)
                 ar.begin(m.grad[m.n_dense:], m.side)       # the expert block is final: it travels under the second backward graph
                 ar = lambda _view, f=grad_allreduce: f.finish(m.grad[: m.n_dense])
             self.graph_b.replay()
         # all-reduce, loss-scale handling (fp16: inf check, skipped step, scale update - the captured step reads the scale from a
         # device scalar), Adam and the refresh of the compute copies (a second small graph): SwitchNeRF.apply_step
-        m.apply_step(ar, optimizer_step, refresh=self.copies.replay)
+        stepped = m.apply_step(ar, optimizer_step, refresh=self.copies.replay, should_accumulate=should_accumulate)
+        if m.accum_steps > 1:
+            self.res["optimizer_stepped"] = stepped
         return self.res
 
 
@@ -308,6 +312,8 @@ class GraphedBackgroundStep:
                 raise ValueError("GraphedBackgroundStep: the expert-parallel foreground step with unequal splits reads their sizes on the "
                                  "host and cannot be captured; use BackgroundScene.train_step, or ExpertParallel(..., padded=True)")
         scene._check_noise_sources()
+        if scene.accum_steps > 1:
+            raise NotImplementedError(scene._ACCUM_PADDED)
         self.scene = scene
         dev = scene.dev
         C = self.bg_capacity = N if bg_capacity is None else int(bg_capacity)

@@ -454,11 +454,21 @@ class MegaNeRF:
             res["ctx_fine"] = cf
         return res
 
+    def set_accumulation(self, steps: int):
+        """Gradient accumulation (SwitchNeRF.set_accumulation) is not built for joint training through the cells: only 1 is taken."""
+        if int(steps) < 1:
+            raise ValueError(f"set_accumulation: accumulation steps must be >= 1, got {steps}")
+        if int(steps) > 1:
+            raise NotImplementedError("MegaNeRF: gradient accumulation (set_accumulation) is not built for joint training: a window "
+                                      "would span every cell model's buffer under the container's one step count")
+
     def apply_step(self, grad_allreduce=None, optimizer_step=True):
         """One Adam step on every cell with the model's one step count and learning rate.  A cell no point reached has a zero gradient,
         not a missing one: its step count advances, its moments decay and it moves by momentum, like the reference's joint_training cells
         under one torch.optim.Adam."""
         self._need_joint("apply_step")
+        if any(getattr(m, "accum_steps", 1) > 1 for m in self.sub_modules):
+            raise NotImplementedError("MegaNeRF: gradient accumulation (set_accumulation on a cell model) is not built for joint training")
         if grad_allreduce is not None:
             raise NotImplementedError("MegaNeRF: data parallelism (a gradient all-reduce over the cells' buffers) is not built")
         if not optimizer_step:

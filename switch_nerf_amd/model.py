@@ -107,6 +107,14 @@ class LossScaler:
 
 DYNCAP_EP_ERROR = ("capacity_factor = 0 (dynamic capacity, nothing dropped) is not supported with expert parallelism: the exchange "
                    "buffers are sized by a static capacity; use capacity_factor > 0, or < 0 (the dynamic capacity clamped at the static one)")
+ACCUM_OWNER_TAIL_ERROR = ("gradient accumulation (set_accumulation) is not built for expert parallelism with owner_tail=True: the tail's "
+                          "gradient is summed on the experts' ranks inside the step")
+
+
+def accumulation_rule(iteration: int, steps: int) -> bool:
+    """The reference's should_accumulate (runner.py:589): iteration `iteration` (0-based) of a run with `steps` accumulation steps
+    only accumulates; the optimizer steps on every steps-th iteration."""
+    return (int(iteration) + 1) % int(steps) != 0
 
 
 class SwitchNeRF:
@@ -466,6 +474,8 @@ class SwitchNeRF:
                                       "colour transform runs in the local tail only")
         if ep is not None and self.cf == 0:
             raise ValueError(DYNCAP_EP_ERROR)
+        if ep is not None and getattr(ep, "owner_tail", False) and self.accum_steps > 1:
+            raise NotImplementedError(ACCUM_OWNER_TAIL_ERROR)
         if ep is None and self.ep is not None:       # leaving expert parallelism: every rank needs every expert's trained weights
             self.gather_expert_shards()
         self.ep = ep
@@ -1362,13 +1372,51 @@ class SwitchNeRF:
     # ------------------------------------------------------------------------------------------ training step
     def train_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, perturb_rand=None,
                    sigma_noise=None, optimizer_step=True, routing_override=None, grad_allreduce=None, fine_samples=0,
-                   fine_u=None, sigma_noise_fine=None, sigma_noise_std=0.0):
+                   fine_u=None, sigma_noise_fine=None, sigma_noise_std=0.0, should_accumulate=None):
         """Runner._training_step + loss assembly + backward + Adam (runner.py:1077-1123, 646-686) = grad_step + apply_step.
-        sigma_noise_std: with device noise on (set_device_noise) the std of the sigma noise the step draws itself where none is supplied."""
+        sigma_noise_std: with device noise on (set_device_noise) the std of the sigma noise the step draws itself where none is supplied.
+        should_accumulate: with gradient accumulation on (set_accumulation), see apply_step; the result then says whether the optimizer
+        stepped (res["optimizer_stepped"]).  The metrics are the micro-batch's own, undivided (the reference's `metrics`)."""
         res = self.grad_step(rgbs, rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise, routing_override,
                              fine_samples, fine_u, sigma_noise_fine, sigma_noise_std=sigma_noise_std)
-        self.apply_step(grad_allreduce, optimizer_step)
+        stepped = self.apply_step(grad_allreduce, optimizer_step, should_accumulate=should_accumulate)
+        if self.accum_steps > 1:
+            res["optimizer_stepped"] = stepped
         return res
+
+    # ------------------------------------------------------------------------------------------ gradient accumulation
+    accum_steps = 1                   # A of --accumulation_steps (runner.py:589); 1 = off: no buffer, no extra launch
+    accum = None                      # the window's fp32 sum of micro-gradients / A, shaped like self.grad (A > 1 only)
+    _micro = 0                        # micro-steps seen since set_accumulation: the reference's train_iterations in its window rule
+
+    def set_accumulation(self, steps: int):
+        """Gradient accumulation over `steps` micro-batches (--accumulation_steps, runner.py:589, 657, 677-690): each micro-step's
+        gradient is added, divided by `steps`, into self.accum, and the all-reduce, the loss-scale handling, Adam and the refresh of
+        the compute copies run on the window's last micro-step only.  Restarts the window (buffer zeroed, micro-step index 0).
+        steps = 1 switches accumulation off and frees the buffer."""
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f"set_accumulation: accumulation steps must be >= 1, got {steps}")
+        if steps > 1 and self.ep is not None and getattr(self.ep, "owner_tail", False):
+            raise NotImplementedError(ACCUM_OWNER_TAIL_ERROR)
+        self.accum_steps, self._micro = steps, 0
+        if steps == 1:
+            self.accum = None
+        elif self.accum is None:
+            self.accum = torch.zeros_like(self.grad)
+        else:
+            self.accum.zero_()
+
+    def _accumulates(self, should_accumulate=None) -> bool:
+        """Whether this micro-step only accumulates - the reference's rule `(train_iterations + 1) % A != 0` (runner.py:589) on the
+        model's own micro-step index, or the caller's bool (a run resumed from a checkpoint derives it from its iteration) - and the
+        advance of that index."""
+        k, self._micro = self._micro, self._micro + 1
+        return accumulation_rule(k, self.accum_steps) if should_accumulate is None else bool(should_accumulate)
+
+    def _step_grad(self):
+        """The gradient the optimizer step consumes: the flat gradient, or the accumulation buffer while accumulation is on."""
+        return self.accum if self.accum_steps > 1 else self.grad
 
     def grad_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, perturb_rand=None, sigma_noise=None,
                   routing_override=None, fine_samples=0, fine_u=None, sigma_noise_fine=None, split=False, sigma_noise_std=0.0):
@@ -1416,9 +1464,15 @@ class SwitchNeRF:
         self._noise_advance()              # device noise: the next step draws at step + 1 (the last launch of the captured step)
         return res
 
-    def apply_step(self, grad_allreduce=None, optimizer_step=True, refresh=None):
+    def apply_step(self, grad_allreduce=None, optimizer_step=True, refresh=None, should_accumulate=None):
         """Gradient all-reduce (N > 1) + Adam (runner.py:486, 686) + refresh of the compute copies of the weights (`refresh`: a
-        replacement for refresh_compute_copies, e.g. the replay of its captured graph)."""
+        replacement for refresh_compute_copies, e.g. the replay of its captured graph).
+        With gradient accumulation on (set_accumulation(A > 1)) -> whether the optimizer stepped; should_accumulate: None = the
+        model's window rule, a bool = the caller's decision for this micro-step (_apply_step_accum)."""
+        if self.accum_steps > 1:
+            return self._apply_step_accum(grad_allreduce, optimizer_step, refresh, should_accumulate)
+        if should_accumulate:
+            raise ValueError("should_accumulate=True without gradient accumulation: call set_accumulation(steps > 1) first")
         scale = 1.0
         if grad_allreduce is not None:
             scale = grad_allreduce(self._allreduce_view())
@@ -1428,6 +1482,38 @@ class SwitchNeRF:
             self.step_count += 1
             ops.adam_step(self.flat, self.grad, self.m, self.v, None, self.step_count, self.lr, grad_scale=scale)
             (refresh or self.refresh_compute_copies)()
+
+    def _apply_step_accum(self, grad_allreduce, optimizer_step, refresh, should_accumulate) -> bool:
+        """apply_step with accumulation on (runner.py:677-690).  An accumulating micro-step adds grad / A into the window's buffer
+        and does nothing else: no all-reduce (DDP's no_sync), no inf check, no Adam, no refresh.  The last micro-step without a
+        loss scaler and without an all-reduce is ONE launch (swn_adam_accum_step: the last gradient never reaches the buffer, which
+        leaves cleared).  Otherwise: add, one all-reduce of the buffer, the inf check on it - the loss scale changes only here, so
+        every micro-gradient of a window carried the same scale (GradScaler's accumulation rule) - then Adam from the buffer; a
+        skipped step clears the buffer (zero_grad).  optimizer_step=False accumulates like should_accumulate=True."""
+        if self.ep is not None and getattr(self.ep, "owner_tail", False):
+            raise NotImplementedError(ACCUM_OWNER_TAIL_ERROR)
+        inv = 1.0 / self.accum_steps
+        if self._accumulates(should_accumulate) or not optimizer_step:
+            ops.grad_accum(self.accum, self.grad, inv)
+            return False
+        if grad_allreduce is None and self.loss_scaler is None:
+            self.step_count += 1
+            ops.adam_accum_step(self.flat, self.accum, self.grad, self.m, self.v, None, self.step_count, self.lr, accum_scale=inv)
+            (refresh or self.refresh_compute_copies)()
+            return True
+        ops.grad_accum(self.accum, self.grad, inv)
+        scale = 1.0
+        if grad_allreduce is not None:
+            scale = grad_allreduce(self._allreduce_view())
+        if not self._unscale_ok():
+            self.accum.zero_()
+            return False
+        if self.loss_scaler is not None:
+            scale /= self._applied_loss_scale
+        self.step_count += 1
+        ops.adam_accum_step(self.flat, self.accum, None, self.m, self.v, None, self.step_count, self.lr, grad_scale=scale)
+        (refresh or self.refresh_compute_copies)()
+        return True
 
     _ls_dev = None
     _ls_dev_val = None
@@ -1449,7 +1535,7 @@ class SwitchNeRF:
         rank-local (never all-reduced), so the flag is agreed over the ranks (MAX): every rank skips - or takes - the same steps and
         holds the same scale."""
         self._applied_loss_scale = self._ls_dev_val if self._ls_dev_val is not None else self.loss_scaler.scale   # what the backward used
-        bad = (~torch.isfinite(self.grad).all()).to(torch.float32).view(1)
+        bad = (~torch.isfinite(self._step_grad()).all()).to(torch.float32).view(1)
         if self.ep is not None and not self.ep.local:
             import torch.distributed as dist
             dist.all_reduce(bad, op=dist.ReduceOp.MAX, group=self.ep.group)
@@ -1468,9 +1554,10 @@ class SwitchNeRF:
     def _allreduce_view(self):
         """What the data-parallel all-reduce sums: the whole flat gradient, or - experts sharded over the ranks - its dense
         prefix (a local expert's gradient already holds the contributions of every rank's rows)."""
+        g = self._step_grad()           # (the accumulation buffer while accumulation is on: one all-reduce per window)
         if self.ep is not None and not self.ep.local:
-            return self.grad[: self.n_dense]
-        return self.grad
+            return g[: self.n_dense]
+        return g
 
     def forward_hier(self, rays, image_indices, n_samples, fine_samples, seg_tokens, perturb=0.0, perturb_rand=None,
                      fine_u=None, sigma_noise=None, sigma_noise_fine=None, routing_override=None, no_batch=False, training=True,
@@ -1561,6 +1648,8 @@ class SwitchNeRF:
                        rgb_padding=0.001, resample_padding=0.01, sigma_noise_std=0.0):
         """Runner._training_step_mip (runner.py:1126-1167): loss = (mse(rgb_fine) + mse(rgb_coarse)) / 2
         + wt * (mean(gate_loss_fine) + mean(gate_loss_coarse)) / 2, backward through both levels, Adam."""
+        if self.accum_steps > 1:
+            raise NotImplementedError("train_step_mip: gradient accumulation (set_accumulation) is not built for the mip step")
         self.grad.zero_()
         c, cf = self.forward_mip(rays, radii, image_indices, n_samples, n_fine, seg_tokens, perturb, perturb_rand, fine_u,
                                  sigma_noise, sigma_noise_fine, False, rgb_padding, resample_padding, sigma_noise_std=sigma_noise_std)

@@ -1579,6 +1579,24 @@ def adam_step(param, grad, m, v, shadow, step: int, lr: float, beta1=0.9, beta2=
          float(lr), float(beta1), float(beta2), float(eps), int(step), float(grad_scale), _stream())
 
 
+def grad_accum(acc, grad, scale: float):
+    """acc += grad * scale (fp32; product and sum rounded separately): one micro-step's gradient into the accumulation window."""
+    n = acc.numel()
+    assert grad.numel() == n and acc.dtype == grad.dtype == torch.float32 and acc.is_contiguous() and grad.is_contiguous()
+    call("swn_grad_accum", _p(acc), _p(grad), n, float(scale), _stream())
+    return acc
+
+
+def adam_accum_step(param, acc, grad, m, v, shadow, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, accum_scale=1.0,
+                    grad_scale=1.0):
+    """The last micro-step of an accumulation window: Adam on (acc + grad * accum_scale) * grad_scale - grad None: on acc * grad_scale -
+    and acc cleared, in one pass (the bits of grad_accum followed by adam_step)."""
+    n = param.numel()
+    assert acc.numel() == n and (grad is None or grad.numel() == n)
+    call("swn_adam_accum_step", _p(param), _p(acc), _p(grad), _p(m), _p(v), _p(shadow), _dt(shadow) if shadow is not None else F32, n,
+         float(lr), float(beta1), float(beta2), float(eps), int(step), float(accum_scale), float(grad_scale), _stream())
+
+
 def cast(src, dst):
     call("swn_cast", _p(src), _p(dst), _dt(dst), src.numel(), _stream())
     return dst
