@@ -14,7 +14,11 @@ A host-resident model packs no compute copies (SwitchNeRF.refresh_compute_copies
 method: for the duration of the call the model's device reads as "cuda" and the (mocked) packing runs.  The mock returns zeros, so three
 host decisions get consistent fakes: fake_route (every token to expert 0), fake_fg_bounds (every second ray continues into the
 background) and fake_cells_assign / fake_cells_pack (point p in cell p % K).  A context's "head" record is not named: it holds no buffer
-of its own, only the caller's tensors, which the context also keeps under the keys the backward reads."""
+of its own, only the caller's tensors, which the context also keeps under the keys the backward reads.
+
+The `tail_*` cases trace apply_step alone, over every owner (model, cascade, scene, cells), with a loss scaler attached by hand to the
+fp32 host models; the torch calls of the tail (the inf check, accum.zero_(), the device scalar's fill_) are no library calls and do
+not show here: tests/test_optim_tail_cpu.py pins what they leave behind."""
 import ctypes as C
 import json
 import sys
@@ -99,6 +103,7 @@ def ranges_of(models, ctxs):
         for k, t in m.wb.items():
             add(t, pre + "wb." + k)
         add(m.flat, pre + "flat"); add(m.grad, pre + "grad"); add(m.m, pre + "adam_m"); add(m.v, pre + "adam_v")
+        add(getattr(m, "accum", None), pre + "accum")
     for ci, c in enumerate(ctxs):
         add(c, "c%d" % ci)
     return r
@@ -364,7 +369,18 @@ def mega(cfg=CELL, call=None, fine=0, N=12, S=4):
     return subs, [st["ctx"]] + ([st["ctx_fine"]] if fine else [])
 
 
+def tail(group, kind="dense", A=1, scaler=False, calls=()):
+    """The step's tail alone (apply_step: all-reduce stub, inf check, accumulation window, Adam, refresh of the compute copies) on a
+    gradient of ones: the cases of tests/test_optim_tail_cpu.py, which pins the host state this trace cannot see."""
+    owner, models = tail_cases._build(group, kind, scaler)
+    tail_cases.drive(group, owner, models, A, scaler, calls, lambda view: 0.5, lambda: [m.refresh_compute_copies() for m in models])
+    return models, []
+
+
+import test_optim_tail_cpu as tail_cases  # noqa: E402
+
 MORE_CASES = {
+    **{"tail_" + k: (tail, v) for k, v in tail_cases.CASES.items()},
     "dense_sh_train": (dense_sh_train, dict()),
     "call_dense": (points_call, dict()),
     "call_dense_training_mode": (points_call, dict(training=True)),

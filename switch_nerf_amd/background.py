@@ -33,7 +33,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import ops, optim
 
 
 class BackgroundScene:
@@ -348,64 +348,6 @@ class BackgroundScene:
         for m in (self.nerf, self.bg):
             m.set_accumulation(steps)
 
-    def _apply_step_accum(self, res, optimizer_step, grad_allreduce, should_accumulate):
-        """apply_step with accumulation on, compact form (runner.py:677-690).  The window is the foreground model's.  An accumulating
-        micro-step adds both gradients, divided by A, into the models' buffers (the background's only when the batch had background
-        rays: its gradient is zero otherwise).  On the last micro-step the reference's rule is kept exactly: THAT batch's
-        bg_nerf_rays_present decides whether the background optimizer steps (runner.py:683); if it does not, the window's
-        accumulated background gradient is discarded, because zero_grad follows anyway (:689-690)."""
-        nerf, bg = self.nerf, self.bg
-        ctx = res["ctx"]
-        if ctx.get("C") is not None:
-            raise NotImplementedError(self._ACCUM_PADDED)
-        import torch.distributed as dist
-        distributed = grad_allreduce is not None or (dist.is_available() and dist.is_initialized())
-        bg_present = True if distributed else ctx["Nb"] > 0
-        inv = 1.0 / nerf.accum_steps
-        accumulates = nerf._accumulates(should_accumulate) or not optimizer_step
-        bg._micro = nerf._micro
-        stepped = False
-        if accumulates:
-            ops.grad_accum(nerf.accum, nerf.grad, inv)
-            if ctx["Nb"] > 0:
-                ops.grad_accum(bg.accum, bg.grad, inv)
-        elif grad_allreduce is None and self.loss_scaler is None:
-            for m in [nerf] + ([bg] if bg_present else []):
-                m.step_count += 1
-                ops.adam_accum_step(m.flat, m.accum, m.grad, m.m, m.v, None, m.step_count, m.lr, accum_scale=inv)
-                m.refresh_compute_copies()
-            if not bg_present:
-                bg.accum.zero_()
-            stepped = True
-        else:
-            models = [nerf] + ([bg] if bg_present else [])
-            scale = {}
-            for m in (nerf, bg):
-                ops.grad_accum(m.accum, m.grad, inv)
-                scale[id(m)] = grad_allreduce(m._allreduce_view()) if grad_allreduce is not None else 1.0
-            found = {id(m): False for m in (nerf, bg)}
-            if self.loss_scaler is not None:               # (the shared scaler: apply_step)
-                for m in models:
-                    found[id(m)] = m._found_inf()
-                self.loss_scaler.update(any(found.values()))
-                for m in (nerf, bg):
-                    m._loss_scale_tensor()
-            for m in (nerf, bg):
-                if m in models and not found[id(m)]:
-                    sc = scale[id(m)]
-                    if self.loss_scaler is not None:
-                        sc /= m._applied_loss_scale
-                    m.step_count += 1
-                    ops.adam_accum_step(m.flat, m.accum, None, m.m, m.v, None, m.step_count, m.lr, grad_scale=sc)
-                    m.refresh_compute_copies()
-                    stepped = True
-                else:
-                    m.accum.zero_()
-        self._noise_advance()
-        res["bg_nerf_rays_present"] = bg_present
-        res["optimizer_stepped"] = stepped
-        return res
-
     def grad_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, fine_samples=0, bg_capacity=None, **kw):
         """Forward + loss + backward of both models: fills both gradients (zeroed first) and returns train_step's dict without
         "bg_nerf_rays_present".  In the padded form nothing here reads the host - the loss scale reaches the backward through the
@@ -425,8 +367,7 @@ class BackgroundScene:
         # scaler - multiplies the loss gradient; both models unscale by it, and a non-finite gradient in either skips that model's step
         ls, ls_dev = 1.0, None
         if self.loss_scaler is not None:
-            for m in (nerf, bg):
-                m._loss_scale_tensor()                    # (records the scale this backward uses: _found_inf divides by it)
+            optim.sync_loss_scale((nerf, bg))             # (records the scale this backward uses: _found_inf divides by it)
             if bg_capacity is None:
                 ls = float(self.loss_scaler.scale)
             else:
@@ -454,18 +395,21 @@ class BackgroundScene:
 
     def apply_step(self, res, optimizer_step=True, grad_allreduce=None, refresh=None, advance=True, should_accumulate=None):
         """The tail both forms of the step share: gradient all-reduce, the shared loss scaler, both Adam steps under the bg_present
-        rule, the advance of the noise counter.  -> res with "bg_nerf_rays_present".
+        rule (optim.apply_tail over the two models), the advance of the noise counter.  -> res with "bg_nerf_rays_present".
         Padded form: starts with the noise advance (advance=False: it was captured with the step) and the readback of (n_bg, n_out);
         a batch with cameras outside the bound or with n_bg > bg_capacity raises before any parameter of either model is touched
         (the noise counter has advanced: that step's draws are skipped).
-        refresh: a replacement for BOTH models' refresh_compute_copies (the replay of their captured graph), run once."""
+        refresh: a replacement for BOTH models' refresh_compute_copies (the replay of their captured graph), run once.
+        With gradient accumulation on (set_accumulation; the compact eager form only) -> res also holds "optimizer_stepped".  The window
+        is the foreground model's.  An accumulating micro-step adds the background's gradient only when the batch had background rays
+        (it is zero otherwise).  On the last micro-step the reference's rule is kept exactly: THAT batch's bg_nerf_rays_present decides
+        whether the background optimizer steps (runner.py:683); if it does not, the window's accumulated background gradient is
+        discarded, because zero_grad follows anyway (:689-690)."""
         nerf, bg = self.nerf, self.bg
-        if self.accum_steps > 1:             # gradient accumulation (set_accumulation): the compact eager form only
-            if refresh is not None or not advance:
-                raise NotImplementedError(self._ACCUM_PADDED)
-            return self._apply_step_accum(res, optimizer_step, grad_allreduce, should_accumulate)
         ctx = res["ctx"]
         padded = ctx.get("C") is not None
+        if self.accum_steps > 1 and (refresh is not None or not advance or padded):
+            raise NotImplementedError(self._ACCUM_PADDED)
         if padded:
             if advance:
                 self._noise_advance()
@@ -478,32 +422,15 @@ class BackgroundScene:
         import torch.distributed as dist
         distributed = grad_allreduce is not None or (dist.is_available() and dist.is_initialized())
         bg_present = True if distributed else ctx["Nb"] > 0
-        models = [nerf] + ([bg] if bg_present else [])
-        scale = {id(m): (grad_allreduce(m._allreduce_view()) if grad_allreduce is not None else 1.0) for m in (nerf, bg)}
         # fp16: the reference holds ONE GradScaler over both optimizers (runner.py:483, 686-690).  GradScaler.step skips an optimizer on
         # ITS OWN non-finite gradient; GradScaler.update backs the shared scale off when EITHER optimizer found one (and only then
         # resets the growth tracker).  The foreground model's LossScaler is that shared scaler; the background's mirrors its scale.
-        found = {id(m): False for m in (nerf, bg)}
-        if optimizer_step and self.loss_scaler is not None:
-            for m in models:
-                found[id(m)] = m._found_inf()
-            self.loss_scaler.update(any(found.values()))
-            for m in (nerf, bg):
-                m._loss_scale_tensor()
-        stepped = False
-        for m in models:
-            if optimizer_step and not found[id(m)]:
-                sc = scale[id(m)]
-                if self.loss_scaler is not None:         # fp16: the gradient carries the loss scale (backward above)
-                    sc /= m._applied_loss_scale
-                m.step_count += 1
-                ops.adam_step(m.flat, m.grad, m.m, m.v, None, m.step_count, m.lr, grad_scale=sc)
-                if refresh is None:
-                    m.refresh_compute_copies()
-                stepped = True
-        if stepped and refresh is not None:
-            refresh()
+        stepped = optim.apply_tail([nerf, bg], stepping=[nerf, bg] if bg_present else [nerf], zero_grad=() if ctx["Nb"] > 0 else (bg,),
+                                   grad_allreduce=grad_allreduce, optimizer_step=optimizer_step, refresh=refresh,
+                                   should_accumulate=should_accumulate)
         if not padded and advance:
             self._noise_advance()          # device noise: ONE advance per step, with or without background rays / a background Adam step
         res["bg_nerf_rays_present"] = bg_present
+        if self.accum_steps > 1:
+            res["optimizer_stepped"] = stepped
         return res

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import ops, optim
 from .dense import DenseNeRF
 from .model import SwitchNeRF
 
@@ -195,9 +195,7 @@ class Cascade:
         fm.grad.zero_()
         c, cf = self.forward_cascade(rays, image_indices, n_samples, fine_samples, seg_tokens, perturb, perturb_rand, fine_u, sigma_noise,
                                      sigma_noise_fine, training=True, sigma_noise_std=sigma_noise_std)
-        ls = cm._loss_scale_tensor() if self.loss_scaler is not None else None
-        if ls is not None:
-            fm._loss_scale_tensor()       # (its record of the scale the backward used: what its Adam step divides by)
+        ls = optim.sync_loss_scale((cm, fm))      # (each half's record of the scale the backward uses: what its Adam step divides by)
         out5, d_f, d_c, d_lf, d_lc = ops.cascade_loss(cf["rgb"], c["rgb"], rgbs.to(torch.float32).contiguous(), cf["l_aux"], c["l_aux"],
                                                       cm.wt, coarse_photo, ls)
         fm.backward(cf, d_f, d_lf)
@@ -215,63 +213,14 @@ class Cascade:
         for h in self.halves():
             h.set_accumulation(steps)
 
-    def _apply_step_accum(self, optimizer_step, should_accumulate) -> bool:
-        """apply_step with accumulation on (SwitchNeRF._apply_step_accum over the two halves) -> whether the optimizers stepped."""
-        halves = self.halves()
-        inv = 1.0 / self.accum_steps
-        accumulates = self.coarse._accumulates(should_accumulate) or not optimizer_step
-        for h in halves:
-            h._micro = self.coarse._micro
-        if accumulates:
-            for h in halves:
-                ops.grad_accum(h.accum, h.grad, inv)
-            return False
-        if self.loss_scaler is None:
-            for h in halves:
-                h.step_count += 1
-                ops.adam_accum_step(h.flat, h.accum, h.grad, h.m, h.v, None, h.step_count, h.lr, accum_scale=inv)
-                h.refresh_compute_copies()
-            return True
-        for h in halves:
-            ops.grad_accum(h.accum, h.grad, inv)
-        bad = any([h._found_inf() for h in halves])          # (on the buffers; each records the scale its backwards used)
-        self.loss_scaler.update(bad)
-        for h in halves:
-            h._loss_scale_tensor()
-        for h in halves:
-            if bad:
-                h.accum.zero_()
-            else:
-                h.step_count += 1
-                ops.adam_accum_step(h.flat, h.accum, None, h.m, h.v, None, h.step_count, h.lr,
-                                    grad_scale=1.0 / self.coarse._applied_loss_scale)
-                h.refresh_compute_copies()
-        return not bad
-
     def apply_step(self, grad_allreduce=None, optimizer_step=True, should_accumulate=None):
-        """One Adam step per half, each with its own step count.  fp16: found-inf is the OR over the halves, the one scaler is updated
-        once and both halves skip - or take - the step together.  With gradient accumulation on (set_accumulation) -> whether the
-        optimizers stepped (should_accumulate: SwitchNeRF.apply_step)."""
+        """One Adam step per half, each with its own step count (optim.apply_tail over the halves).  fp16: found-inf is the OR over
+        the halves, the one scaler is updated once and both halves skip - or take - the step together.  With gradient accumulation on
+        (set_accumulation) -> whether the optimizers stepped (should_accumulate: SwitchNeRF.apply_step)."""
         if grad_allreduce is not None:
             _refuse("expert or data parallelism (grad_allreduce)")
-        if self.accum_steps > 1:
-            return self._apply_step_accum(optimizer_step, should_accumulate)
-        if not optimizer_step:
-            return
-        scale = 1.0
-        if self.loss_scaler is not None:
-            found = [h._found_inf() for h in self.halves()]      # (each records the scale its backward used)
-            bad = any(found)
-            self.loss_scaler.update(bad)
-            for h in self.halves():
-                h._loss_scale_tensor()
-            if bad:
-                return
-            scale = 1.0 / self.coarse._applied_loss_scale
-        for h in self.halves():
-            h.step_count += 1
-            ops.adam_step(h.flat, h.grad, h.m, h.v, None, h.step_count, h.lr, grad_scale=scale)
-            h.refresh_compute_copies()
+        stepped = optim.apply_tail(self.halves(), skip_together=True, optimizer_step=optimizer_step, should_accumulate=should_accumulate)
+        return stepped if self.accum_steps > 1 else None
 
     def train_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, perturb_rand=None, sigma_noise=None,
                    optimizer_step=True, routing_override=None, grad_allreduce=None, fine_samples=0, fine_u=None, sigma_noise_fine=None,

@@ -59,7 +59,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, optim
 from .dense import DenseNeRF
 
 MAX_CELLS = 64      # swn_cells_*: the centroids live in LDS, a point's membership in one 64-bit mask
@@ -473,11 +473,10 @@ class MegaNeRF:
             raise NotImplementedError("MegaNeRF: data parallelism (a gradient all-reduce over the cells' buffers) is not built")
         if not optimizer_step:
             return
-        self.step_count += 1
         for m in self.sub_modules:
-            m.step_count, m.lr = self.step_count, self.lr
-            ops.adam_step(m.flat, m.grad, m.m, m.v, None, self.step_count, self.lr)
-            m.refresh_compute_copies()
+            m.step_count, m.lr = self.step_count, self.lr      # (the tail advances each cell's count, like the model's here)
+        self.step_count += 1
+        optim.apply_tail(self.sub_modules)
 
     def train_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, optimizer_step=True,
                    fine_samples=0, fine_u=None, sigma_noise_fine=None):
