@@ -10,15 +10,15 @@ Every tensor whose address goes into a call is kept alive until its case ends, s
 a temporary always reads `tmp`, and two traces of one tree are equal.  A pointer that is `tmp` on one side and a named buffer on the other
 is therefore a buffer that one side keeps under a model or context key and the other does not.
 
-A host-resident model packs no compute copies (SwitchNeRF.refresh_compute_copies returns early off the GPU), so the script wraps that
-method: for the duration of the call the model's device reads as "cuda" and the (mocked) packing runs.  The mock returns zeros, so three
-host decisions get consistent fakes: fake_route (every token to expert 0), fake_fg_bounds (every second ray continues into the
-background) and fake_cells_assign / fake_cells_pack (point p in cell p % K).  A context's "head" record is not named: it holds no buffer
-of its own, only the caller's tensors, which the context also keeps under the keys the backward reads.
+The mock is install_mock of tests/test_render_results_cpu.py (zeros for every output, consistent fakes for the routing, the foreground
+bound and the cell membership, refresh_compute_copies run as if on the device) with a recording call.  A context's "head" record is not
+named: it holds no buffer of its own, only the caller's tensors, which the context also keeps under the keys the backward reads.
 
 The `tail_*` cases trace apply_step alone, over every owner (model, cascade, scene, cells), with a loss scaler attached by hand to the
 fp32 host models; the torch calls of the tail (the inf check, accum.zero_(), the device scalar's fill_) are no library calls and do
-not show here: tests/test_optim_tail_cpu.py pins what they leave behind."""
+not show here: tests/test_optim_tail_cpu.py pins what they leave behind.  The `render_*` cases are the calls of
+tests/test_render_results_cpu.py through rendering.render_rays / render_rays_mip (autograd cases with their loss.backward()); that file
+pins the result dictionaries and the framework generator's consumption.  Captured-graph paths need a device and are not traced."""
 import ctypes as C
 import json
 import sys
@@ -52,10 +52,7 @@ out_path, root = sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else HERE
 sys.path.insert(0, root)
 sys.path.insert(0, os.path.join(HERE, "tests"))
 import synth  # noqa: E402
-from switch_nerf_amd import _lib, ops  # noqa: E402
 
-torch.empty = torch.zeros
-torch.empty_like = torch.zeros_like
 trace, ptr_ids = [], {}
 
 
@@ -135,17 +132,6 @@ def fake_call(name, *args):
     trace.append([name, s])
 
 
-class FakeLib:
-    def __getattr__(self, k):
-        return lambda *a: 4096
-
-
-class _S:
-    cuda_stream = 0
-
-
-ops.call = fake_call
-ops._stream = lambda: C.c_void_p(0)
 _alive = []
 
 
@@ -160,92 +146,15 @@ def _ptr_view(t):      # (the address of a strided view: heads_coef_fwd's output
     return C.c_void_p(t.data_ptr())
 
 
-ops._p, ops._pv = _ptr, _ptr_view
-_lib.load = lambda: FakeLib()
-ops._lib.load = _lib.load
-_sched = torch.zeros(16, dtype=torch.int32)
-ops.chain_sched = lambda dev, key: _sched
-torch.cuda.current_stream = lambda *a: _S()
+import test_render_results_cpu as render_cases  # noqa: E402
 
-_route = ops.route_top1
-
-
-def fake_route(idx, gmax, gates, seg_tokens, n_experts, capacity, bpr, want_perm=True, want_drops=False, **kw):
-    """a consistent routing for the zero-filled mock: every token of a segment goes to expert 0"""
-    r = list(_route(idx, gmax, gates, seg_tokens, n_experts, capacity, bpr, want_perm=want_perm, want_drops=want_drops, **kw))
-    P = idx.shape[0]
-    n_seg = P // seg_tokens
-    loc, counts = r[0], r[1]
-    loc.copy_(torch.arange(P, dtype=loc.dtype) % seg_tokens)
-    counts.zero_()
-    counts.view(n_seg, n_experts)[:, 0] = seg_tokens
-    if want_drops:
-        nd = max(seg_tokens - capacity, 0)
-        r[5].copy_((torch.arange(n_seg * n_experts + 1) > 0).to(torch.int32) * 0 + torch.clamp(torch.arange(n_seg * n_experts + 1) + n_experts - 1, min=0) // n_experts * nd)
-        tok = torch.arange(P).view(n_seg, seg_tokens)[:, capacity:].reshape(-1).to(torch.int32)
-        r[6][: tok.numel()] = tok
-    return tuple(r)
-
-
-ops.route_top1 = fake_route
+render_cases.install_mock(setattr, fake_call, _ptr, _ptr_view)      # (the mock of tests/test_render_results_cpu.py, with the recording call)
 from switch_nerf_amd.model import SwitchNeRF  # noqa: E402
 from switch_nerf_amd.dense import DenseNeRF  # noqa: E402
 
 from switch_nerf_amd.background import BackgroundScene  # noqa: E402
 from switch_nerf_amd.mega import MegaNeRF  # noqa: E402
 
-_refresh = SwitchNeRF.refresh_compute_copies
-
-
-class _AsCuda:
-    type = "cuda"
-
-
-def refresh_on_host(self):
-    """refresh_compute_copies of a host-resident model: its device reads as "cuda" while the (mocked) packing runs"""
-    real = self.dev
-    self.dev = _AsCuda()
-    try:
-        _refresh(self)
-    finally:
-        self.dev = real
-
-
-SwitchNeRF.refresh_compute_copies = refresh_on_host
-_fg_bounds, _cells_assign, _cells_pack = ops.fg_bounds, ops.cells_assign, ops.cells_pack
-
-
-def fake_fg_bounds(rays, center, radius, n_out=None):
-    """a consistent bound for the zero-filled mock: the rays keep their far plane, every second one continues into the background"""
-    rays_fg, fg_far, last_delta, has_bg, n_out = _fg_bounds(rays, center, radius, n_out)
-    rays_fg.copy_(rays)
-    fg_far.copy_(rays[:, 7])
-    has_bg[::2] = 1
-    return rays_fg, fg_far, last_delta, has_bg, n_out
-
-
-def fake_cells_assign(x, centroids, dim_start, margin):
-    """point p belongs to cell p % K alone"""
-    weights, counts = _cells_assign(x, centroids, dim_start, margin)
-    P, K = weights.shape
-    weights[torch.arange(P), torch.arange(P) % K] = 1.0
-    counts.copy_(torch.bincount(torch.arange(P) % K, minlength=K))
-    return weights, counts
-
-
-def fake_cells_pack(weights, counts, rows_capacity=None):
-    """the packed row space of fake_cells_assign's membership"""
-    begin, rows, slot = _cells_pack(weights, counts, rows_capacity)
-    P, K = weights.shape
-    cell = torch.arange(P) % K
-    begin[1:] = torch.cumsum(counts, 0)
-    rows[:P] = torch.sort(cell, stable=True)[1].to(torch.int32)
-    slot.fill_(-1)
-    slot[torch.arange(P), cell] = (torch.arange(P) // K).to(torch.int32)
-    return begin, rows, slot
-
-
-ops.fg_bounds, ops.cells_assign, ops.cells_pack = fake_fg_bounds, fake_cells_assign, fake_cells_pack
 BF16, F32 = torch.bfloat16, torch.float32
 
 
@@ -377,9 +286,14 @@ def tail(group, kind="dense", A=1, scaler=False, calls=()):
     return models, []
 
 
+def render(**kw):
+    return render_cases.run_case(**kw)[2], []
+
+
 import test_optim_tail_cpu as tail_cases  # noqa: E402
 
 MORE_CASES = {
+    **{"render_" + k: (render, v) for k, v in render_cases.CASES.items()},
     **{"tail_" + k: (tail, v) for k, v in tail_cases.CASES.items()},
     "dense_sh_train": (dense_sh_train, dict()),
     "call_dense": (points_call, dict()),

@@ -14,7 +14,12 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+
+def render_outputs(c, cf, out):
+    """What a render pass (SwitchNeRF.render_forward) hands to autograd: rgb, both gate losses (the fine one empty for one level), depth,
+    depth variance."""
+    gl_f = cf["l_aux"] if cf is not None else torch.zeros(0, device=out["rgb"].device)
+    return out["rgb"], c["l_aux"], gl_f, out["depth"], out["depth_variance"]
 
 
 class RenderRaysFunction(torch.autograd.Function):
@@ -28,7 +33,7 @@ class RenderRaysFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flat_param, nerf, rays, image_indices, S, F, chunk, perturb, perturb_rand, sigma_noise, sigma_noise_fine):
         nerf._sync_compute_copies()
-        ctx.nerf, ctx.fine = nerf, F > 0
+        ctx.nerf = nerf
         ctx.graph = None
         std = 0.0
         if isinstance(sigma_noise, float) and perturb_rand is None:      # the model's seeded device noise is on (set_device_noise): the std
@@ -47,18 +52,11 @@ class RenderRaysFunction(torch.autograd.Function):
             state, outs = g.forward(rays, image_indices)
             ctx.graph, ctx.state, ctx.generation = g, state, g.generation
             res = (outs[0].clone(), outs[1].clone(), outs[2].clone(), outs[3].clone(), outs[4].clone())
-        elif F > 0:
-            c, cf, out = nerf.forward_hier(rays, image_indices, S, F, chunk, perturb, perturb_rand, None, sigma_noise, sigma_noise_fine,
-                                           no_batch=nerf.moe_no_batch, training=True, sigma_noise_std=std)
-            nerf._noise_advance()
-            ctx.state = (c, cf, out, S, F)
-            res = (out["rgb"], c["l_aux"], cf["l_aux"], out["depth"], out["depth_variance"])
         else:
-            c = nerf.forward_rays(rays, image_indices, S, chunk, perturb, perturb_rand, sigma_noise, training=True, no_batch=nerf.moe_no_batch,
-                                  sigma_noise_std=std)
+            ctx.state = nerf.render_forward(rays, image_indices, S, F, chunk, perturb, perturb_rand, None, sigma_noise, sigma_noise_fine,
+                                            training=True, no_batch=nerf.moe_no_batch, sigma_noise_std=std)
             nerf._noise_advance()
-            ctx.state = (c,)
-            res = (c["rgb"], c["l_aux"], torch.zeros(0, device=rays.device), c["depth"], c["depth_variance"])
+            res = render_outputs(*ctx.state)
         ctx.mark_non_differentiable(res[3], res[4])
         nerf._last_ctx = ctx.state
         return res
@@ -76,16 +74,8 @@ class RenderRaysFunction(torch.autograd.Function):
             ctx.state = None
             return (g.clone(),) + (None,) * 10
         nerf.grad.zero_()
-        d_rgb = d_rgb.to(torch.float32).contiguous()
-        if ctx.fine:
-            c, cf, out, S, F = ctx.state
-            d_raw_m = ops.composite_bwd(out["raw"], out["z"], d_rgb)
-            d_raw_f, d_raw_c = ops.unmerge_grad(d_raw_m, out["order"], F, S)
-            nerf.backward_net(cf, d_raw_f, d_laux_f.to(torch.float32).contiguous())
-            nerf.backward_net(c, d_raw_c, d_laux_c.to(torch.float32).contiguous())
-        else:
-            (c,) = ctx.state
-            nerf.backward(c, d_rgb, d_laux_c.to(torch.float32).contiguous())
+        f32 = lambda t: t.to(torch.float32).contiguous()
+        nerf.render_backward(*ctx.state, f32(d_rgb), f32(d_laux_c), f32(d_laux_f))
         ctx.state = None
         return (nerf.grad.clone(),) + (None,) * 10
 

@@ -33,7 +33,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops, optim
+from . import hier, ops, optim
 
 
 class BackgroundScene:
@@ -196,7 +196,6 @@ class BackgroundScene:
                 raise Exception(self._UNBOUNDED)
             Nb = idx_bg.numel()
             ctx = dict(N=N, S=S, F=Fn, idx_bg=idx_bg, Nb=Nb, fg_far=fg_far, has_bg=has_bg)
-        det_u = lambda n, k: torch.linspace(0, 1, k).expand(n, k).contiguous().to(self.dev) if perturb == 0 else torch.rand(n, k, device=self.dev)
         # ---- background first (the reference's order, and so the order of its random draws)
         if Nb > 0:
             Sb = S // 2
@@ -235,7 +234,7 @@ class BackgroundScene:
                 if dn is not None and fine_u_bg is None and perturb != 0:
                     fine_u_bg = drawn["fine_u"] = draw(o.RNG_FINE_U, Fb, o.RNG_UNIFORM)
                 if fine_u_bg is None:
-                    fine_u_bg = det_u(Nb, Fb)
+                    fine_u_bg = hier.default_fine_u(bg._linspace, Nb, Fb, perturb, self.dev)
                 if dn is not None and noise_std > 0 and (sigma_noise_bg_fine is None or isinstance(sigma_noise_bg_fine, str)):
                     sigma_noise_bg_fine = drawn["sigma_noise_fine"] = draw(o.RNG_SIGMA_FINE, Fb, o.RNG_NORMAL, float(noise_std)).view(-1)
                 if isinstance(sigma_noise_bg_fine, str):
@@ -244,32 +243,22 @@ class BackgroundScene:
                 _, dreal_f, pe_f = o.bg_sample_pe(rays_b, self.center, self.radius, Fb, bg.cfg["pos_xyz_dim"], bg.dtype, bg.KP,
                                                   z_in=z_f, pe_out=bg._buf("f:pe", (Nb * Fb, bg.KP), bg.dtype))
                 cfb = bg._net_forward(pe_f, pe_dir_b, img_b, Nb, Fb, Nb * Fb, sigma_noise_bg_fine, None, False, "f", saving=bool(training))
-                # descending sort of the union (:421 descending=flip) = ascending sort of the negated depths
-                zneg, order, raw_m = o.merge_samples((-z_f).contiguous(), (-z_b).contiguous(), cfb["raw"], cb["raw"])
-                z_m = -zneg
-                dreal_m = torch.gather(torch.cat([dreal_f, dreal_b], 1), 1, order.long())    # :432-433
+                z_m, order, raw_m, dreal_m = hier.merge_flipped(z_f, z_b, cfb["raw"], cb["raw"], dreal_f, dreal_b)
                 rgb_b, depth_b, _, _, _ = o.composite_bounded_fwd(raw_m, z_m, None, True, dreal_m)
                 b.update(cf=cfb, raw=raw_m, z=z_m, order=order, z_fine=z_f)
             b.update(rgb=rgb_b, depth=depth_b, **drawn)       # (the draws of this pass, for inspection; a supplied tensor is the caller's)
             ctx["bg"] = b
         # ---- foreground on the clipped rays
         std_fg = float(noise_std) if dn is not None else 0.0       # device noise: the foreground draws its own sigma noise (streams 1 / 3)
-        c = nerf.forward_rays(rays_fg, image_indices, S, seg_tokens, perturb, perturb_rand, sigma_noise, training, None,
-                              no_batch=no_batch, want_weights=Fn > 0, composite=Fn > 0, sigma_noise_std=std_fg)
-        ctx["c"] = c
         if Fn == 0:
+            c = ctx["c"] = nerf.forward_rays(rays_fg, image_indices, S, seg_tokens, perturb, perturb_rand, sigma_noise, training, None,
+                                             no_batch=no_batch, composite=False, sigma_noise_std=std_fg)
             raw, z, z_last = c["raw"], c["z"], c["z"][:, -1]              # stratified depths ascend: the last one is the maximum (:217)
-        else:
-            if dn is not None and fine_u is None and perturb != 0:          # stream 2, as SwitchNeRF.forward_hier draws it
-                fine_u = nerf._draw(o.RNG_FINE_U, N * Fn, dn["ray_base"] * Fn, o.RNG_UNIFORM).view(N, Fn)
-            if fine_u is None:
-                fine_u = det_u(N, Fn)
-            z_fine = o.sample_pdf(c["z"], c["weights"], fine_u, Fn)
-            cf = nerf.forward_rays(rays_fg, image_indices, Fn, min(seg_tokens, N * Fn), 0.0, None, sigma_noise_fine, training, None,
-                                   no_batch=no_batch, z_in=z_fine, pe_dir=c["pe_dir"], tag="f", composite=False, sigma_noise_std=std_fg)
-            z, order, raw = o.merge_samples(z_fine, c["z"], cf["raw"], c["raw"])
+        else:                    # (the fine u is drawn - stream 2 - or defaulted as SwitchNeRF.forward_hier does it)
+            c, cf, z_fine, z, order, raw = nerf.hier_passes(rays_fg, image_indices, S, Fn, seg_tokens, perturb, perturb_rand, fine_u,
+                                                            sigma_noise, sigma_noise_fine, None, no_batch, training, std_fg)
             z_last = z_fine.max(dim=-1)[0]                               # the FINE depths' maximum (:249-250)
-            ctx.update(cf=cf, order=order, z_fine=z_fine)
+            ctx.update(c=c, cf=cf, order=order, z_fine=z_fine)
         last_delta = torch.where(has_bg > 0, fg_far - z_last, last0).contiguous()          # :216-217 / :249-250
         rgb, depth, dvar, _, lam = o.composite_bounded_fwd(raw, z, last_delta, False, None, want_bg_lambda=True)
         ctx.update(raw=raw, z=z, last_delta=last_delta, bg_lambda=lam, fg_rgb=rgb, fg_depth=depth, depth_variance=dvar)

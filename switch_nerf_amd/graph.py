@@ -139,7 +139,7 @@ class GraphedRender:
     image with the same shapes - ~60 launches per call that the host otherwise enqueues slower than the GPU runs them.
 
         g = GraphedRender(model, rays, image_indices, n_samples, seg_tokens, fine_samples=F, no_batch=model.moe_no_batch)
-        out = g(rays, image_indices)     # dict: rgb, depth, depth_variance, l_aux_coarse, idx_coarse, sigma_coarse (+ *_fine)
+        out = g(rays, image_indices)     # dict: rgb, depth, depth_variance, l_aux_coarse, idx_coarse, sigma_coarse, raw_coarse (+ *_fine)
 
     The returned tensors live in the graph's static memory: consume (or clone) them before the next call.  Expert-parallel
     evaluation reads split sizes on the host (list_all_to_all) and cannot be captured."""
@@ -158,15 +158,13 @@ class GraphedRender:
         def run():
             with torch.no_grad():
                 chunk = min(int(seg_tokens), N * S)
-                if F > 0:
-                    c, cf, o = model.forward_hier(self.rays, self.idx, S, F, chunk, 0.0, None, None, None, None, no_batch=no_batch,
-                                                  training=False)
-                    return dict(rgb=o["rgb"], depth=o["depth"], depth_variance=o["depth_variance"], l_aux_coarse=c["l_aux"],
-                                l_aux_fine=cf["l_aux"], idx_coarse=c["idx"], idx_fine=cf["idx"], sigma_coarse=c["raw"][:, 3],
-                                sigma_fine=cf["raw"][:, 3])
-                c = model.forward_rays(self.rays, self.idx, S, chunk, 0.0, None, None, training=False, no_batch=no_batch)
-                return dict(rgb=c["rgb"], depth=c["depth"], depth_variance=c["depth_variance"], l_aux_coarse=c["l_aux"],
-                            idx_coarse=c["idx"], sigma_coarse=c["raw"][:, 3])
+                c, cf, o = model.render_forward(self.rays, self.idx, S, F, chunk, 0.0, None, None, None, None, training=False,
+                                                no_batch=no_batch)
+                res = dict(rgb=o["rgb"], depth=o["depth"], depth_variance=o["depth_variance"], l_aux_coarse=c["l_aux"],
+                           idx_coarse=c["idx"], sigma_coarse=c["raw"][:, 3], raw_coarse=c["raw"])
+                if cf is not None:
+                    res.update(l_aux_fine=cf["l_aux"], idx_fine=cf["idx"], sigma_fine=cf["raw"][:, 3], raw_fine=cf["raw"])
+                return res
 
         was_profile, model.profile = model.profile, False
         side = torch.cuda.Stream(device=dev)
@@ -208,7 +206,7 @@ class GraphedRenderTrain:
         _refuse_sh(model, "GraphedRenderTrain")
         if model.ep is not None and not model.ep.local:
             raise ValueError("GraphedRenderTrain: expert-parallel training is not captured")
-        from . import ops
+        from .autograd import render_outputs
         self.model = model
         dev = model.dev
         N, S, F = rays.shape[0], int(n_samples), int(fine_samples)
@@ -222,27 +220,15 @@ class GraphedRenderTrain:
         def fwd():
             pr = torch.rand(N, S, device=dev) if perturb > 0 and not dn else None                        # rendering.py:582
             noise = torch.randn(N * S, device=dev) * noise_std if noise_std > 0 and not dn else None     # rendering.py:366
-            if F > 0:
-                noise_f = torch.randn(N * F, device=dev) * noise_std if noise_std > 0 and not dn else None
-                c, cf, out = model.forward_hier(self.rays, self.idx, S, F, chunk, perturb, pr, None, noise, noise_f,
-                                                no_batch=model.moe_no_batch, training=True, sigma_noise_std=std)
-                model._noise_advance()
-                return (c, cf, out), (out["rgb"], c["l_aux"], cf["l_aux"], out["depth"], out["depth_variance"])
-            c = model.forward_rays(self.rays, self.idx, S, chunk, perturb, pr, noise, training=True, no_batch=model.moe_no_batch,
-                                   sigma_noise_std=std)
+            noise_f = torch.randn(N * F, device=dev) * noise_std if F > 0 and noise_std > 0 and not dn else None
+            state = model.render_forward(self.rays, self.idx, S, F, chunk, perturb, pr, None, noise, noise_f, training=True,
+                                         no_batch=model.moe_no_batch, sigma_noise_std=std)
             model._noise_advance()
-            return (c,), (c["rgb"], c["l_aux"], torch.zeros(0, device=dev), c["depth"], c["depth_variance"])
+            return state, render_outputs(*state)
 
         def bwd(state):
             model.grad.zero_()
-            if F > 0:
-                c, cf, out = state
-                d_raw_m = ops.composite_bwd(out["raw"], out["z"], self.d_rgb)
-                d_raw_f, d_raw_c = ops.unmerge_grad(d_raw_m, out["order"], F, S)
-                model.backward_net(cf, d_raw_f, self.d_laux_f)
-                model.backward_net(c, d_raw_c, self.d_laux_c)
-            else:
-                model.backward(state[0], self.d_rgb, self.d_laux_c)
+            model.render_backward(*state, self.d_rgb, self.d_laux_c, self.d_laux_f)
 
         was_profile, model.profile = model.profile, False
         step0 = model.noise_state_dict()["step"]           # the warm-up passes advance the noise counter: put it back before the capture

@@ -59,7 +59,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops, optim
+from . import hier, ops, optim
 from .dense import DenseNeRF
 
 MAX_CELLS = 64      # swn_cells_*: the centroids live in LDS, a point's membership in one 64-bit mask
@@ -431,8 +431,8 @@ class MegaNeRF:
             out["rgb"], out["depth"], out["depth_variance"], _ = o.composite_fwd(raw, z)
         else:
             _, _, _, w = o.composite_fwd(raw, z, want_weights=True)
-            if fine_u is None:                                 # det = (perturb == 0): linspace, else rand (rendering.py:605-609)
-                fine_u = lin(F).expand(N, F).contiguous() if perturb == 0 else torch.rand(N, F, device=self.dev)
+            if fine_u is None:
+                fine_u = hier.default_fine_u(lin, N, F, perturb, self.dev)
             z_fine = o.sample_pdf(z, w, fine_u, F)
             cf = self.forward_points(_points(rays, z_fine, image_indices, not sh), sigma_noise_fine, "f", dirs, F)
             zm, order, raw_m = o.merge_samples(z_fine, z, cf["out"], raw)
@@ -441,11 +441,10 @@ class MegaNeRF:
         # a MegaNeRF returns a tensor: no gate loss (rendering.py:385-406) - a zero operand with weight 0
         zero = torch.zeros(1, dtype=torch.float32, device=self.dev)
         out4, d_rgb, _, _ = o.step_loss(out["rgb"], rgbs.to(torch.float32).contiguous(), zero, None, 0.0, None)
-        d_raw = o.composite_bwd(out["raw"], out["z"], d_rgb)
         if F == 0:
-            self.backward_points(c, d_raw)
+            self.backward_points(c, o.composite_bwd(raw, z, d_rgb))
         else:
-            d_raw_f, d_raw_c = o.unmerge_grad(d_raw, out["order"], F, S)
+            d_raw_f, d_raw_c = hier.merged_bwd(out, d_rgb)
             self.backward_points(cf, d_raw_f)
             self.backward_points(c, d_raw_c)
         res = dict(loss=out4[2], photo_loss=out4[0], gate_loss=out4[1], psnr=out4[3], depth_variance=out["depth_variance"].mean(), ctx=c,
@@ -554,13 +553,12 @@ def _render_background(bg_nerf, cluster_2d, rays_b, img_b, center, radius, S, F,
     rgb, depth, _, w_b, _ = o.composite_bounded_fwd(raw_b, z_b, None, True, dreal_b, want_weights=F > 0)
     if F > 0:
         Fb = F // 2
-        z_f = o.sample_pdf(z_b.flip(-1).contiguous(), w_b, lin(Fb).expand(Nb, Fb).contiguous(), Fb)
+        z_f = o.sample_pdf(z_b.flip(-1).contiguous(), w_b, hier.default_fine_u(lin, Nb, Fb, 0.0, rays_b.device), Fb)
         _, dreal_f, p4f = o.bg_sample_pe(rays_b, center, radius, Fb, 0, torch.float32, 4, z_in=z_f)
         real = ro + rd * dreal_f.unsqueeze(-1) if cluster_2d else edge
         raw_f = _run(bg_nerf, _bg_points(rays_b, img_b, p4f, real, not sh), chunk, dirs)
-        zneg, order, raw_m = o.merge_samples((-z_f).contiguous(), (-z_b).contiguous(), raw_f, raw_b)      # descending sort (:421)
-        dreal_m = torch.gather(torch.cat([dreal_f, dreal_b], 1), 1, order.long())                         # :432-433
-        rgb, depth, _, _, _ = o.composite_bounded_fwd(raw_m, -zneg, None, True, dreal_m)
+        z_m, _, raw_m, dreal_m = hier.merge_flipped(z_f, z_b, raw_f, raw_b, dreal_f, dreal_b)
+        rgb, depth, _, _, _ = o.composite_bounded_fwd(raw_m, z_m, None, True, dreal_m)
     return rgb, depth
 
 
@@ -575,7 +573,7 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
     transmittance (rendering.py:104-134), like background.BackgroundScene does for a dense background model.
     A model in training mode (joint_training, after train()) is refused: training runs through MegaNeRF.train_step, and the autograd
     bridge that would let this function return differentiable tensors for a MegaNeRF is a later change."""
-    from .rendering import _point_keys
+    from .rendering import _gate_sigma_keys, _point_keys, _results
     if not isinstance(nerf, MegaNeRF):
         raise NotImplementedError("a MegaNeRF background model behind a foreground model of another kind is not built")
     if bg_nerf is not None and not (isinstance(bg_nerf, MegaNeRF) and bg_nerf.xyz_real):
@@ -622,20 +620,15 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
     z = ops.sample_z(rays, lin(S), None, 0.0, S)                  # evaluation: no jitter, no sigma noise (rendering.py:366)
     raw = _run(nerf, _points(rays, z, image_indices, not sh), chunk, dirs)
     res: Dict[str, torch.Tensor] = {}
-    if getattr(hparams, "return_sigma", False):
-        res["sigma_coarse"] = raw[:, 3].view(N, S)
-    raw_c, z_c = raw, z
+    raw_c, z_c, raw_f = raw, z, None
     if F == 0:
         typ, z_last = "coarse", z[:, -1]                          # stratified depths ascend: the last one is the maximum (:216)
     else:
         _, _, _, w = ops.composite_fwd(raw, z, want_weights=True)      # (the last delta only reaches the last weight, which :240 drops)
-        u = lin(F).expand(N, F).contiguous()                      # det = (perturb == 0): linspace (rendering.py:605-609)
-        z_fine = ops.sample_pdf(z, w, u, F)
+        z_fine = ops.sample_pdf(z, w, hier.default_fine_u(lin, N, F, 0.0, dev), F)      # evaluation: det = (perturb == 0)
         raw_f = _run(nerf, _points(rays, z_fine, image_indices, not sh), chunk, dirs)
         z, order, raw = ops.merge_samples(z_fine, z_c, raw_f, raw_c)
         typ, z_last = "fine", z_fine.max(dim=-1)[0]               # the FINE depths' maximum (:249-250)
-        if getattr(hparams, "return_sigma", False):
-            res["sigma_fine"] = raw_f[:, 3].view(N, F)
     if bg_nerf is None:
         ld, ld_c = 1e10, 1e10
         rgb, depth, dvar, _ = ops.composite_fwd(raw, z)
@@ -654,9 +647,6 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
     _point_keys(res, hparams, "coarse", rays, raw_c, z_c, raw_c, ld_c)      # (foreground keys only, like the reference)
     if F > 0:
         _point_keys(res, hparams, "fine", rays, raw_f, z, raw, ld, z_pts=z_fine, order=order)
-    res[f"rgb_{typ}"] = rgb
-    if get_depth:
-        res[f"depth_{typ}"] = depth
-    if get_depth_variance:
-        res[f"depth_variance_{typ}"] = dvar
+    res.update(_results(typ, rgb, None, None, depth, dvar, get_depth, get_depth_variance))      # (a tensor model: no gate loss, no gates)
+    _gate_sigma_keys(res, hparams, dict(raw=raw_c), None if raw_f is None else dict(raw=raw_f), N, S, F, gates=False)
     return res, Nb > 0

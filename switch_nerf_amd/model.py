@@ -30,7 +30,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, hier, ops
 
 BUILDING = dict(model_dim=256, num_experts=8, expert_layers=7, skips=(3,), pos_xyz_dim=12, pos_dir_dim=4,
                 appearance_dim=48, appearance_count=10, gate_hidden=256, gate_layers=2, layer2_out=128)
@@ -1559,28 +1559,57 @@ class SwitchNeRF:
             return g[: self.n_dense]
         return g
 
-    def forward_hier(self, rays, image_indices, n_samples, fine_samples, seg_tokens, perturb=0.0, perturb_rand=None,
-                     fine_u=None, sigma_noise=None, sigma_noise_fine=None, routing_override=None, no_batch=False, training=True,
-                     sigma_noise_std=0.0):
-        """_get_results with fine_samples > 0 and no cascade (rendering.py:199-274): coarse pass (weights only, its raw
-        outputs kept), importance sampling of the fine depths from the detached coarse weights, fine pass on those
-        depths, sort-merge of both sample sets (:419-433) and compositing of the union.
-        Returns (coarse ctx, fine ctx, merged results {raw, z, order, rgb, depth, depth_variance})."""
+    def render_forward(self, rays, image_indices, S, F, chunk, perturb, perturb_rand, fine_u, sigma_noise, sigma_noise_fine, *, training,
+                       no_batch, routing_override=None, sigma_noise_std=0.0):
+        """The render pass of S coarse and F fine samples per ray -> (c, cf, out): forward_hier's result, or for F == 0 the one context
+        of forward_rays as (c, None, c).  The forward of the autograd bridge, of the captured render graphs and of the eager render_rays
+        (grad_step writes the same two calls out itself); the caller advances the noise counter (_noise_advance) where its step ends."""
+        if F > 0:
+            return self.forward_hier(rays, image_indices, S, F, chunk, perturb, perturb_rand, fine_u, sigma_noise, sigma_noise_fine,
+                                     routing_override, no_batch, training, sigma_noise_std)
+        c = self.forward_rays(rays, image_indices, S, chunk, perturb, perturb_rand, sigma_noise, training, routing_override,
+                              no_batch=no_batch, sigma_noise_std=sigma_noise_std)
+        return c, None, c
+
+    def render_backward(self, c, cf, out, d_rgb, d_laux_c, d_laux_f):
+        """Backward of render_forward given dL/d rgb [N,3] and each level's dL/d l_aux[seg]: accumulates into self.grad, the fine level
+        first."""
+        if cf is None:
+            return self.backward(c, d_rgb, d_laux_c)
+        d_raw_f, d_raw_c = hier.merged_bwd(out, d_rgb)
+        self.backward_net(cf, d_raw_f, d_laux_f)
+        self.backward_net(c, d_raw_c, d_laux_c)
+
+    def hier_passes(self, rays, image_indices, n_samples, fine_samples, seg_tokens, perturb, perturb_rand, fine_u, sigma_noise,
+                    sigma_noise_fine, routing_override, no_batch, training, sigma_noise_std):
+        """forward_hier up to the compositing of the union: coarse pass (composited for its weights, its raw outputs kept), importance
+        sampling of the fine depths from the detached coarse weights, fine pass on those depths, sort-merge of both sample sets
+        (rendering.py:419-433) -> (coarse ctx, fine ctx, z_fine, merged z, order, merged raw).  BackgroundScene.forward composites the
+        union with its own bounded kernel."""
         N = rays.shape[0]
         c = self.forward_rays(rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise, training,
                               routing_override, no_batch=no_batch, want_weights=True, sigma_noise_std=sigma_noise_std)
         if fine_u is None and perturb != 0 and training and self._noise is not None:      # device noise: stream 2
             fine_u = self._draw(ops.RNG_FINE_U, N * fine_samples, self._noise["ray_base"] * fine_samples,
                                 ops.RNG_UNIFORM).view(N, fine_samples)
-        if fine_u is None:                                                # det = (perturb == 0): linspace, else rand (:605-609)
-            fine_u = (self._linspace(fine_samples).expand(N, fine_samples).contiguous() if perturb == 0
-                      else torch.rand(N, fine_samples, device=self.dev))
+        if fine_u is None:
+            fine_u = hier.default_fine_u(self._linspace, N, fine_samples, perturb, self.dev)
         z_fine = ops.sample_pdf(c["z"], c["weights"], fine_u, fine_samples)
         seg_f = min(seg_tokens, N * fine_samples)
         cf = self.forward_rays(rays, image_indices, fine_samples, seg_f, 0.0, None, sigma_noise_fine, training, None,
                                no_batch=no_batch, z_in=z_fine, pe_dir=c["pe_dir"], tag="f", composite=False,
                                sigma_noise_std=sigma_noise_std)
         zm, order, raw_m = ops.merge_samples(z_fine, c["z"], cf["raw"], c["raw"])
+        return c, cf, z_fine, zm, order, raw_m
+
+    def forward_hier(self, rays, image_indices, n_samples, fine_samples, seg_tokens, perturb=0.0, perturb_rand=None,
+                     fine_u=None, sigma_noise=None, sigma_noise_fine=None, routing_override=None, no_batch=False, training=True,
+                     sigma_noise_std=0.0):
+        """_get_results with fine_samples > 0 and no cascade (rendering.py:199-274): hier_passes and the compositing of the union.
+        Returns (coarse ctx, fine ctx, merged results {raw, z, order, z_fine, rgb, depth, depth_variance})."""
+        c, cf, z_fine, zm, order, raw_m = self.hier_passes(rays, image_indices, n_samples, fine_samples, seg_tokens, perturb, perturb_rand,
+                                                           fine_u, sigma_noise, sigma_noise_fine, routing_override, no_batch, training,
+                                                           sigma_noise_std)
         out = dict(raw=raw_m, z=zm, order=order, z_fine=z_fine)
         out["rgb"], out["depth"], out["depth_variance"], _ = ops.composite_fwd(raw_m, zm)
         return c, cf, out

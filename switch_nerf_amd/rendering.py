@@ -105,6 +105,51 @@ def _check_sh(nerf, bg_nerf, hparams):
         raise NotImplementedError("sh_deg: a background model (bg_nerf) with spherical-harmonics colour is not built")
 
 
+def _host_noise(hparams, training, N, rows, rows_fine, dev, device_noise, jitter=True):
+    """The noise a render call draws from the framework generator -> perturb, std (of the sigma noise; 0.0: none), perturb_rand [N, S],
+    sigma_noise [rows], sigma_noise_fine [rows_fine] (rows_fine None: no fine level), in the reference's order (rendering.py:582, :366).
+    Evaluation draws nothing; nor does a call whose passes draw for themselves (device_noise: seeded device noise, captured graphs).
+    jitter False: the callee draws the jitter itself (BackgroundScene.forward)."""
+    perturb = hparams.perturb if training else 0
+    use_noise = bool(getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and training)
+    pr = noise = noise_f = None
+    if not device_noise:
+        if jitter and perturb > 0:
+            pr = torch.rand(N, hparams.coarse_samples, device=dev)
+        if use_noise:
+            noise = torch.randn(rows, device=dev) * hparams.sigma_noise_std
+            if rows_fine is not None:
+                noise_f = torch.randn(rows_fine, device=dev) * hparams.sigma_noise_std
+    return perturb, float(hparams.sigma_noise_std) if use_noise else 0.0, pr, noise, noise_f
+
+
+def _results(typ, rgb, gate_c, gate_f, depth, dvar, get_depth, get_depth_variance, take=lambda t: t):
+    """The keys every branch returns for its top level `typ`; a gate loss of None has no key.  take: what a value goes through on its
+    way out (a captured graph's outputs are cloned out of its static memory)."""
+    res = {f"rgb_{typ}": take(rgb)}
+    if gate_c is not None:
+        res["gate_loss_coarse"] = take(gate_c)
+    if gate_f is not None:
+        res["gate_loss_fine"] = take(gate_f)
+    if get_depth:
+        res[f"depth_{typ}"] = take(depth)
+    if get_depth_variance:
+        res[f"depth_variance_{typ}"] = take(dvar)
+    return res
+
+
+def _gate_sigma_keys(res, hparams, c, cf, N, rows_c, rows_f, gates=True, sigma=True, take=lambda t: t):
+    """moe_gates_{typ} [N, rows, 1, 1] (hparams.moe_return_gates) and sigma_{typ} [N, rows] (hparams.return_sigma) of the levels that ran
+    (cf None: one level), from each level's "idx" and "raw"; gates / sigma False: the branch has no such key."""
+    for typ, lvl, rows in (("coarse", c, rows_c), ("fine", cf, rows_f)):
+        if lvl is None:
+            continue
+        if gates and getattr(hparams, "moe_return_gates", False):
+            res[f"moe_gates_{typ}"] = lvl["idx"].long().view(N, rows, 1, 1)
+        if sigma and getattr(hparams, "return_sigma", False):
+            res[f"sigma_{typ}"] = take(lvl["raw"][:, 3].view(N, rows))
+
+
 def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch.Tensor], hparams, sphere_center=None,
                 sphere_radius=None, get_depth: bool = True, get_depth_variance: bool = True,
                 get_bg_fg_rgb: bool = False) -> Tuple[Dict[str, torch.Tensor], bool]:
@@ -128,86 +173,37 @@ def render_rays(nerf, bg_nerf, rays: torch.Tensor, image_indices: Optional[torch
     chunk = min(hparams.model_chunk_size, P)
     # (a ragged last model chunk - P % chunk != 0 - is routed on its own like the reference's loop, rendering.py:354-383, in
     #  evaluation and in training)
-    perturb = hparams.perturb if nerf.training else 0
-    use_noise = bool(getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and nerf.training)
-    under_autograd = nerf.training and torch.is_grad_enabled() and hasattr(nerf, "flat_param") and getattr(nerf, "hash", None) is None
+    training = nerf.training
+    under_autograd = training and torch.is_grad_enabled() and hasattr(nerf, "flat_param") and getattr(nerf, "hash", None) is None
+    # forward / backward replayed from captured graphs (graph.GraphedRenderTrain): jitter and sigma noise are drawn inside them
+    graphed = under_autograd and getattr(nerf, "graph_train", False) and getattr(nerf, "ep", None) is None
+    perturb, std, pr, noise, noise_f = _host_noise(hparams, training, N, P, N * F if F > 0 else None, rays.device, dn or graphed)
     if image_indices is None:
         image_indices = torch.zeros(N, dtype=torch.long, device=rays.device)
-    if under_autograd and getattr(nerf, "graph_train", False) and getattr(nerf, "ep", None) is None:
-        # forward / backward replayed from captured graphs (graph.GraphedRenderTrain); jitter and sigma noise are drawn inside them
-        pr, noise, noise_f = "graph", (float(hparams.sigma_noise_std) if use_noise else 0.0), None
-    elif dn:       # seeded device noise: the passes draw jitter / sigma noise / fine u themselves (noise = the std), then advance the step
-        pr, noise, noise_f = None, (float(hparams.sigma_noise_std) if use_noise else 0.0), None
-    else:
-        pr = torch.rand(N, S, device=rays.device) if perturb > 0 else None
-        noise = torch.randn(P, device=rays.device) * hparams.sigma_noise_std if use_noise else None      # rendering.py:366
-        noise_f = torch.randn(N * F, device=rays.device) * hparams.sigma_noise_std if (F > 0 and noise is not None) else None
+    typ = "fine" if F > 0 else "coarse"
     if under_autograd:
         # training under autograd (the reference's Runner loop: loss.backward() + torch optimizer, runner.py:679-693): one autograd
-        # node over the HIP forward; its backward runs the HIP backward and fills nerf.flat_param.grad (autograd.py)
+        # node over the HIP forward; its backward runs the HIP backward and fills nerf.flat_param.grad (autograd.py).  Where the passes
+        # draw the noise themselves (captured graphs, seeded device noise) the std stands in for the noise tensor
         from .autograd import RenderRaysFunction
         rgb, gl_c, gl_f, depth, dvar = RenderRaysFunction.apply(nerf.flat_param, nerf, rays.contiguous(), image_indices, S, F, chunk,
-                                                                float(perturb), pr, noise, noise_f)
-        typ = "fine" if F > 0 else "coarse"
-        res = {f"rgb_{typ}": rgb, "gate_loss_coarse": gl_c}
-        if F > 0:
-            res["gate_loss_fine"] = gl_f
-        if get_depth:
-            res[f"depth_{typ}"] = depth
-        if get_depth_variance:
-            res[f"depth_variance_{typ}"] = dvar
-        st = nerf._last_ctx
-        if getattr(hparams, "moe_return_gates", False):
-            res["moe_gates_coarse"] = st[0]["idx"].long().view(N, S, 1, 1)
-            if F > 0:
-                res["moe_gates_fine"] = st[1]["idx"].long().view(N, F, 1, 1)
-        if getattr(hparams, "return_sigma", False):
-            res["sigma_coarse"] = st[0]["raw"][:, 3].view(N, S)
-            if F > 0:
-                res["sigma_fine"] = st[1]["raw"][:, 3].view(N, F)
-        _point_keys(res, hparams, "coarse", rays, st[0]["raw"], st[0]["z"], st[0]["raw"])
-        if F > 0:
-            out = st[2]
-            _point_keys(res, hparams, "fine", rays, st[1]["raw"], out["z"], out["raw"], z_pts=out["z_fine"], order=out["order"])
-        return res, False
-    if not nerf.training and getattr(nerf, "graph_eval", False) and getattr(nerf, "ep", None) is None and not _want_points(hparams):
+                                                                float(perturb), "graph" if graphed else pr,
+                                                                std if (dn or graphed) else noise, noise_f)
+        c, cf, out = nerf._last_ctx
+        res = _results(typ, rgb, gl_c, gl_f if F > 0 else None, depth, dvar, get_depth, get_depth_variance)
+    elif not training and getattr(nerf, "graph_eval", False) and getattr(nerf, "ep", None) is None and not _want_points(hparams):
         return _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get_depth, get_depth_variance), False
-    std = 0.0
-    if dn:
-        std, noise = noise, None
-    if F > 0:
-        c, cf, out = nerf.forward_hier(rays.contiguous(), image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
-                                       no_batch=nerf.moe_no_batch, training=nerf.training, sigma_noise_std=std)
+    else:          # (seeded device noise: the passes draw jitter / sigma noise / fine u themselves, then the step advances)
+        c, cf, out = nerf.render_forward(rays.contiguous(), image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
+                                         training=training, no_batch=nerf.moe_no_batch, sigma_noise_std=std if dn else 0.0)
         if dn:
             nerf._noise_advance()
-        res = {"rgb_fine": out["rgb"], "gate_loss_coarse": c["l_aux"], "gate_loss_fine": cf["l_aux"]}
-        if get_depth:
-            res["depth_fine"] = out["depth"]
-        if get_depth_variance:
-            res["depth_variance_fine"] = out["depth_variance"]
-        if getattr(hparams, "moe_return_gates", False):
-            res["moe_gates_coarse"] = c["idx"].long().view(N, S, 1, 1)
-            res["moe_gates_fine"] = cf["idx"].long().view(N, F, 1, 1)
-        if getattr(hparams, "return_sigma", False):
-            res["sigma_coarse"] = c["raw"][:, 3].view(N, S)
-            res["sigma_fine"] = cf["raw"][:, 3].view(N, F)
-        _point_keys(res, hparams, "coarse", rays, c["raw"], c["z"], c["raw"])
-        _point_keys(res, hparams, "fine", rays, cf["raw"], out["z"], out["raw"], z_pts=out["z_fine"], order=out["order"])
-        return res, False
-    c = nerf.forward_rays(rays.contiguous(), image_indices, S, chunk, float(perturb), pr, noise, training=nerf.training,
-                          no_batch=nerf.moe_no_batch, sigma_noise_std=std)
-    if dn:
-        nerf._noise_advance()
-    res = {"rgb_coarse": c["rgb"], "gate_loss_coarse": c["l_aux"]}
-    if get_depth:
-        res["depth_coarse"] = c["depth"]
-    if get_depth_variance:
-        res["depth_variance_coarse"] = c["depth_variance"]
-    if getattr(hparams, "moe_return_gates", False):
-        res["moe_gates_coarse"] = c["idx"].long().view(N, S, 1, 1)
-    if getattr(hparams, "return_sigma", False):
-        res["sigma_coarse"] = c["raw"][:, 3].view(N, S)
+        res = _results(typ, out["rgb"], c["l_aux"], cf["l_aux"] if cf is not None else None, out["depth"], out["depth_variance"],
+                       get_depth, get_depth_variance)
+    _gate_sigma_keys(res, hparams, c, cf, N, S, F)
     _point_keys(res, hparams, "coarse", rays, c["raw"], c["z"], c["raw"])
+    if F > 0:
+        _point_keys(res, hparams, "fine", rays, cf["raw"], out["z"], out["raw"], z_pts=out["z_fine"], order=out["order"])
     return res, False
 
 
@@ -232,13 +228,9 @@ def _render_rays_cascade(nerf, bg_nerf, rays, image_indices, hparams, get_depth,
     N, S, F = rays.shape[0], hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
     training = nerf.training
     chunk = min(hparams.model_chunk_size, N * S)
-    perturb = hparams.perturb if training else 0
-    use_noise = bool(getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and training)
+    perturb, _, pr, noise, noise_f = _host_noise(hparams, training, N, N * S, N * (S + F) if F > 0 else None, rays.device, False)
     if image_indices is None:
         image_indices = torch.zeros(N, dtype=torch.long, device=rays.device)
-    pr = torch.rand(N, S, device=rays.device) if perturb > 0 else None
-    noise = torch.randn(N * S, device=rays.device) * hparams.sigma_noise_std if use_noise else None
-    noise_f = torch.randn(N * (S + F), device=rays.device) * hparams.sigma_noise_std if (use_noise and F > 0) else None
     rays = rays.contiguous()
     nerf._check_runtime()
     if training and torch.is_grad_enabled() and any(getattr(h, "hash", None) is not None for h in nerf.halves()):
@@ -256,25 +248,17 @@ def _render_rays_cascade(nerf, bg_nerf, rays, image_indices, hparams, get_depth,
         else:
             rgb_c, gl_c, _, depth, dvar = RenderRaysFunction.apply(nerf.coarse.flat_param, nerf.coarse, rays, image_indices, S, 0, chunk,
                                                                    float(perturb), pr, noise, None)
-            (c,), cf = nerf.coarse._last_ctx, None
+            c, cf, rgb_f, gl_f = nerf.coarse._last_ctx[0], None, rgb_c, None
     else:
         c, cf = nerf.forward_cascade(rays, image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
                                      no_batch=nerf.moe_no_batch, training=training)
         rgb_c, gl_c = c["rgb"], c["l_aux"]
         top = cf if cf is not None else c
         rgb_f, gl_f, depth, dvar = top["rgb"], top["l_aux"], top["depth"], top["depth_variance"]
-    res = {"rgb_coarse": rgb_c, "gate_loss_coarse": gl_c}
-    typ = "fine" if F > 0 else "coarse"
+    res = _results("fine" if F > 0 else "coarse", rgb_f, gl_c, gl_f if F > 0 else None, depth, dvar, get_depth, get_depth_variance)
     if F > 0:
-        res["rgb_fine"], res["gate_loss_fine"] = rgb_f, gl_f
-    if get_depth:
-        res[f"depth_{typ}"] = depth
-    if get_depth_variance:
-        res[f"depth_variance_{typ}"] = dvar
-    if getattr(hparams, "return_sigma", False):
-        res["sigma_coarse"] = c["raw"][:, 3].view(N, S)
-        if F > 0:
-            res["sigma_fine"] = cf["raw"][:, 3].view(N, S + F)
+        res["rgb_coarse"] = rgb_c
+    _gate_sigma_keys(res, hparams, c, cf, N, S, S + F, gates=False)
     return res
 
 
@@ -288,22 +272,10 @@ def _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get
     nerf._sync_compute_copies()
     g = cached_graph(cache, key, lambda: GraphedRender(nerf, rays.contiguous(), image_indices, S, chunk, F, nerf.moe_no_batch))
     o = g(rays, image_indices)
-    typ = "fine" if F > 0 else "coarse"
-    res = {f"rgb_{typ}": o["rgb"].clone(), "gate_loss_coarse": o["l_aux_coarse"].clone()}
-    if F > 0:
-        res["gate_loss_fine"] = o["l_aux_fine"].clone()
-    if get_depth:
-        res[f"depth_{typ}"] = o["depth"].clone()
-    if get_depth_variance:
-        res[f"depth_variance_{typ}"] = o["depth_variance"].clone()
-    if getattr(hparams, "moe_return_gates", False):
-        res["moe_gates_coarse"] = o["idx_coarse"].long().view(N, S, 1, 1)
-        if F > 0:
-            res["moe_gates_fine"] = o["idx_fine"].long().view(N, F, 1, 1)
-    if getattr(hparams, "return_sigma", False):
-        res["sigma_coarse"] = o["sigma_coarse"].reshape(N, S).clone()
-        if F > 0:
-            res["sigma_fine"] = o["sigma_fine"].reshape(N, F).clone()
+    res = _results("fine" if F > 0 else "coarse", o["rgb"], o["l_aux_coarse"], o.get("l_aux_fine"), o["depth"], o["depth_variance"],
+                   get_depth, get_depth_variance, take=torch.clone)
+    _gate_sigma_keys(res, hparams, dict(idx=o["idx_coarse"], raw=o["raw_coarse"]),
+                     dict(idx=o["idx_fine"], raw=o["raw_fine"]) if F > 0 else None, N, S, F, take=torch.clone)
     return res
 
 
@@ -325,17 +297,14 @@ def _render_rays_bg(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, 
                     get_bg_fg_rgb):
     """The bg_nerf branch (rendering.py:32-159) through background.BackgroundScene."""
     N, S, F = rays.shape[0], hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
-    perturb = hparams.perturb if nerf.training else 0
-    use_noise = getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and nerf.training
-    std = hparams.sigma_noise_std if use_noise else 0.0
     if image_indices is None:
         image_indices = torch.zeros(N, dtype=torch.long, device=rays.device)
     scene = background_scene(nerf, bg_nerf, sphere_center, sphere_radius)
     dn = scene.device_noise and nerf.training      # seeded device noise: the scene draws what is not supplied (std = the sigma noise's)
+    perturb, std, _, noise, noise_f = _host_noise(hparams, nerf.training, N, N * S, N * F if F > 0 else None, rays.device, dn, jitter=False)
     kw = {}
-    if use_noise and not dn:        # rendering.py:366: randn per evaluated chunk, for either model
-        kw = dict(sigma_noise=torch.randn(N * S, device=rays.device) * std, sigma_noise_bg="randn", sigma_noise_bg_fine="randn",
-                  sigma_noise_fine=torch.randn(N * F, device=rays.device) * std if F else None)
+    if noise is not None:           # rendering.py:366: randn per evaluated chunk, for either model
+        kw = dict(sigma_noise=noise, sigma_noise_bg="randn", sigma_noise_bg_fine="randn", sigma_noise_fine=noise_f)
     cap = getattr(hparams, "bg_capacity", None)     # the padded form of the background rows (background.py), when the recipe asks for it
     if cap is not None:
         kw["bg_capacity"] = max(1, min(int(cap), N))
@@ -345,22 +314,14 @@ def _render_rays_bg(nerf, bg_nerf, rays, image_indices, hparams, sphere_center, 
         scene._noise_advance()
     scene.read_counts(ctx)                          # (padded form: the one readback and the checks the compact form made inside forward)
     typ = "fine" if F > 0 else "coarse"
-    res = {f"rgb_{typ}": ctx["rgb"], "gate_loss_coarse": ctx["c"]["l_aux"]}
-    if F > 0:
-        res["gate_loss_fine"] = ctx["cf"]["l_aux"]
-    if get_depth:
-        res[f"depth_{typ}"] = ctx["depth"]
-    if get_depth_variance:
-        res[f"depth_variance_{typ}"] = ctx["depth_variance"]
+    res = _results(typ, ctx["rgb"], ctx["c"]["l_aux"], ctx["cf"]["l_aux"] if F > 0 else None, ctx["depth"], ctx["depth_variance"],
+                   get_depth, get_depth_variance)
     if get_bg_fg_rgb:                                                    # :111-112, :124-125
         res[f"fg_rgb_{typ}"] = ctx["fg_rgb"]
         res[f"bg_rgb_{typ}"] = ctx["rgb"] - ctx["fg_rgb"]
         res[f"fg_depth_{typ}"] = ctx["fg_depth"]
         res[f"bg_depth_{typ}"] = ctx["depth"] - ctx["fg_depth"]
-    if getattr(hparams, "moe_return_gates", False):
-        res["moe_gates_coarse"] = ctx["c"]["idx"].long().view(N, S, 1, 1)
-        if F > 0:
-            res["moe_gates_fine"] = ctx["cf"]["idx"].long().view(N, F, 1, 1)
+    _gate_sigma_keys(res, hparams, ctx["c"], ctx.get("cf"), N, S, F, sigma=False)
     if _want_points(hparams):                                            # foreground keys only, like the reference
         c = ctx["c"]
         if F > 0:
@@ -383,38 +344,25 @@ def render_rays_mip(nerf, rays: torch.Tensor, radii: torch.Tensor, image_indices
     _check_affine(nerf, hparams)
     N = rays.shape[0]
     S, F = hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
-    perturb = hparams.perturb if nerf.training else 0
     dn = _device_noise(nerf, None, hparams) and nerf.training      # seeded device noise: forward_mip draws what is not supplied
-    pr = torch.rand(N, S, device=rays.device) if perturb > 0 and not dn else None
+    perturb, std, pr, noise, noise_f = _host_noise(hparams, nerf.training, N, N * (S - 1), N * max(F - 1, 0) if F > 0 else None,
+                                                   rays.device, dn)
     chunk = hparams.model_chunk_size
-    noise = noise_f = None
-    std = 0.0
-    if dn and getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0:
-        std = float(hparams.sigma_noise_std)
-    elif getattr(hparams, "use_sigma_noise", False) and hparams.sigma_noise_std > 0 and nerf.training:
-        noise = torch.randn(N * (S - 1), device=rays.device) * hparams.sigma_noise_std
-        noise_f = torch.randn(N * max(F - 1, 0), device=rays.device) * hparams.sigma_noise_std if F > 0 else None
     if image_indices is None:
         image_indices = torch.zeros(N, dtype=torch.long, device=rays.device)
     c, cf = nerf.forward_mip(rays.contiguous(), radii, image_indices, S, F, chunk, float(perturb), pr, None, noise, noise_f,
                              no_batch=nerf.moe_no_batch, rgb_padding=float(getattr(hparams, "rgb_padding", 0.001) or 0.0),
                              resample_padding=float(getattr(hparams, "weights_resample_padding", 0.01)), training=nerf.training,
                              fine_randomized=bool(hparams.perturb),      # rendering_mip.py:227: randomized=hparams.perturb, also in eval
-                             sigma_noise_std=std)
+                             sigma_noise_std=std if dn else 0.0)
     if dn:
         nerf._noise_advance()
-    res = {"rgb_coarse": c["rgb"], "gate_loss_coarse": c["l_aux"]}
     top, typ = (c, "coarse") if cf is None else (cf, "fine")
+    res = _results(typ, top["rgb"], c["l_aux"], None if cf is None else cf["l_aux"], top["depth"], top["depth_variance"], get_depth,
+                   get_depth_variance)
     if cf is not None:
-        res["rgb_fine"], res["gate_loss_fine"] = cf["rgb"], cf["l_aux"]
-    if get_depth:
-        res[f"depth_{typ}"] = top["depth"]
-    if get_depth_variance:
-        res[f"depth_variance_{typ}"] = top["depth_variance"]
-    if getattr(hparams, "moe_return_gates", False):
-        res["moe_gates_coarse"] = c["idx"].long().view(N, S - 1, 1, 1)
-        if cf is not None:
-            res["moe_gates_fine"] = cf["idx"].long().view(N, F - 1, 1, 1)
+        res["rgb_coarse"] = c["rgb"]
+    _gate_sigma_keys(res, hparams, c, cf, N, S - 1, F - 1, sigma=False)
     return res, False
 
 
