@@ -843,6 +843,27 @@ int swn_grad_accum(float* acc, const float* grad, long n, float scale, void* str
 int swn_adam_accum_step(float* param, float* acc, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow, int dtype,
                         long n, float lr, float beta1, float beta2, float eps, int step, float accum_scale, float grad_scale,
                         void* stream);
+/* The finite guard (check_finite, runner.py:620-673): a step whose scalar metrics are not all finite is dropped on the device.
+ * swn_finite_guard: metrics[n] (n <= 64; the loss kernels' out4 / out5) -> ok[0] = 1 iff every slot is finite, where slot psnr_slot
+ * (-1: none) also passes when it is +inf; skipped[0] += 1 - ok (skipped may be NULL: several ranks count behind their MIN
+ * all-reduce of ok).  One launch of one wave.
+ * The *_guarded optimiser launches read ok[0] once per workgroup.  ok = 1: exactly the unguarded launch, bit for bit, for optimizer
+ * step step_state[0] + 1, and step_state[0] advances by one.  ok = 0: parameters, moments, shadow and step_state are left untouched;
+ * grad is left as it is (an unguarded step does not write it either) and acc is cleared over [0, n), as a taken step leaves it.
+ * swn_grad_accum_guarded with ok = 0 clears acc too: a flagged micro-step discards the window's partial sums (zero_grad).
+ * step_state: int32[2] on the device, {optimizer steps taken, 0}; the second word counts the workgroups of a running launch and is 0
+ * between launches.  bias_table: float[table_rows][2] on the device, filled on the HOST by swn_adam_bias_table (no stream, no
+ * launch): row t - 1 = {1 - beta1^t, sqrt(1 - beta2^t)} as swn_adam_step computes them, up to the row where both are exactly 1, which
+ * holds for every later step; *rows = the rows written, an error if `capacity` rows do not reach it.                              */
+int swn_finite_guard(const float* metrics, int n, int psnr_slot, int* ok, long long* skipped, void* stream);
+int swn_adam_bias_table(float beta1, float beta2, float* table, long capacity, long* rows);
+int swn_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow, int dtype, long n,
+                          float lr, float beta1, float beta2, float eps, const float* bias_table, long table_rows, int* step_state,
+                          float grad_scale, const int* ok, void* stream);
+int swn_grad_accum_guarded(float* acc, const float* grad, long n, float scale, const int* ok, void* stream);
+int swn_adam_accum_step_guarded(float* param, float* acc, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow,
+                                int dtype, long n, float lr, float beta1, float beta2, float eps, const float* bias_table,
+                                long table_rows, int* step_state, float accum_scale, float grad_scale, const int* ok, void* stream);
 int swn_cast(const float* in, void* out, int dtype, long n, void* stream);
 /* out[b][c][r] = in[b][r][c]  (fp32 master -> dtype compute copy, transposed) */
 int swn_cast_transpose(const float* in, void* out, int dtype, int batch, int rows, int cols, void* stream);

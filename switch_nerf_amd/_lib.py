@@ -171,6 +171,11 @@ SIGNATURES = {
     "swn_adam_step": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, f32, vp],
     "swn_grad_accum": [vp, vp, i64, f32, vp],
     "swn_adam_accum_step": [vp, vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, i32, f32, f32, vp],
+    "swn_finite_guard": [vp, i32, i32, vp, vp, vp],
+    "swn_adam_bias_table": [f32, f32, vp, i64, C.POINTER(i64)],
+    "swn_adam_step_guarded": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, vp, i64, vp, f32, vp, vp],
+    "swn_grad_accum_guarded": [vp, vp, i64, f32, vp, vp],
+    "swn_adam_accum_step_guarded": [vp, vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, vp, i64, vp, f32, f32, vp, vp],
     "swn_cast": [vp, vp, i32, i64, vp],
     "swn_cast_transpose": [vp, vp, i32, i32, i32, i32, vp],
 }

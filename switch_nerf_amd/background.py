@@ -321,6 +321,8 @@ class BackgroundScene:
         should_accumulate: with gradient accumulation on (set_accumulation), see apply_step."""
         if self.accum_steps > 1 and bg_capacity is not None:
             raise NotImplementedError(self._ACCUM_PADDED)
+        if self.check_finite and bg_capacity is not None:
+            raise NotImplementedError(self._GUARD_PADDED)
         res = self.grad_step(rgbs, rays, image_indices, n_samples, seg_tokens, perturb, fine_samples, bg_capacity, **kw)
         return self.apply_step(res, optimizer_step, grad_allreduce, should_accumulate=should_accumulate)
 
@@ -331,6 +333,33 @@ class BackgroundScene:
     @property
     def accum_steps(self) -> int:
         return self.nerf.accum_steps
+
+    # ------------------------------------------------------------------------------------------ finite guard
+    _GUARD_PADDED = ("BackgroundScene: the finite guard (check_finite) is built for the compact eager step only, not for the padded "
+                     "form (bg_capacity=) or GraphedBackgroundStep")
+
+    @property
+    def check_finite(self) -> bool:
+        return self.nerf.check_finite
+
+    def set_check_finite(self, on: bool = True):
+        """SwitchNeRF.set_check_finite over both models: ONE flag and one counter (the foreground model's) for the step's metrics,
+        each model with its own device step count.  The compact eager step only."""
+        self.nerf.set_check_finite(on)
+        self.bg.set_check_finite(on, share=self.nerf)
+
+    def skipped_steps(self) -> int:
+        return self.nerf.skipped_steps()
+
+    def finite_guard_state_dict(self) -> dict:
+        return dict(nerf=self.nerf.finite_guard_state_dict(), bg_nerf=self.bg.finite_guard_state_dict())
+
+    def load_finite_guard_state_dict(self, sd: dict):
+        self.set_check_finite(bool(sd["nerf"].get("check_finite", False)))
+        for name, m in (("nerf", self.nerf), ("bg_nerf", self.bg)):
+            m.step_count = int(sd[name].get("step_count", m.step_count))
+        if self.check_finite:
+            self.nerf._guard["skipped"].fill_(int(sd["nerf"].get("skipped_steps", 0)))
 
     def set_accumulation(self, steps: int):
         """SwitchNeRF.set_accumulation on both models: one window over the two, each with its own buffer."""
@@ -365,7 +394,13 @@ class BackgroundScene:
         if ls_dev is not None:
             d_rgb = d_rgb * ls_dev
         self.backward(ctx, d_rgb.contiguous(), ls * nerf.wt * (0.5 if fine else 1.0), ls * nerf.wt * 0.5, loss_scale_dev=ls_dev)
-        return dict(loss=loss, photo_loss=photo, gate_loss=gate_loss, psnr=-10.0 * torch.log10(photo), rgb=ctx["rgb"],
+        psnr = -10.0 * torch.log10(photo)
+        guard = {}
+        if self.check_finite:                # ONE check for both models: the metrics of the blended image (a background ray's poison is in them)
+            if bg_capacity is not None:
+                raise NotImplementedError(self._GUARD_PADDED)
+            guard["step_ok"] = nerf._finite_guard(torch.stack([photo, gate_loss, loss, psnr]).to(torch.float32), 3)
+        return dict(**guard, loss=loss, photo_loss=photo, gate_loss=gate_loss, psnr=psnr, rgb=ctx["rgb"],
                     depth=ctx["depth"], depth_variance=ctx["depth_variance"].mean(), ctx=ctx)
 
     def read_counts(self, ctx):
@@ -399,6 +434,8 @@ class BackgroundScene:
         padded = ctx.get("C") is not None
         if self.accum_steps > 1 and (refresh is not None or not advance or padded):
             raise NotImplementedError(self._ACCUM_PADDED)
+        if self.check_finite and (refresh is not None or not advance or padded):
+            raise NotImplementedError(self._GUARD_PADDED)
         if padded:
             if advance:
                 self._noise_advance()

@@ -200,7 +200,8 @@ class Cascade:
                                                       cm.wt, coarse_photo, ls)
         fm.backward(cf, d_f, d_lf)
         cm.backward(c, d_c, d_lc)
-        return dict(loss=out5[3], photo_loss=out5[0], coarse_loss=out5[1], gate_loss=out5[2], psnr=out5[4],
+        guard = dict(step_ok=cm._finite_guard(out5, 4)) if cm.check_finite else {}      # ONE check over both halves' metrics
+        return dict(**guard, loss=out5[3], photo_loss=out5[0], coarse_loss=out5[1], gate_loss=out5[2], psnr=out5[4],
                     depth_variance=cf["depth_variance"].mean(), ctx=c, ctx_fine=cf, rgb=cf["rgb"], rgb_coarse=c["rgb"], depth=cf["depth"])
 
     @property
@@ -212,6 +213,30 @@ class Cascade:
         each half with its own buffer."""
         for h in self.halves():
             h.set_accumulation(steps)
+
+    @property
+    def check_finite(self) -> bool:
+        return self.coarse.check_finite
+
+    def set_check_finite(self, on: bool = True):
+        """SwitchNeRF.set_check_finite over the halves: ONE flag and one counter (the coarse half's) for the step's five metrics, as the
+        reference's single check; each half keeps its own device step count."""
+        self.coarse.set_check_finite(on)
+        if self.fine is not None:
+            self.fine.set_check_finite(on, share=self.coarse)
+
+    def skipped_steps(self) -> int:
+        return self.coarse.skipped_steps()
+
+    def finite_guard_state_dict(self) -> dict:
+        return {name: h.finite_guard_state_dict() for name, h in self._named_halves()}
+
+    def load_finite_guard_state_dict(self, sd: dict):
+        self.set_check_finite(bool(sd["coarse"].get("check_finite", False)))
+        for name, h in self._named_halves():
+            h.step_count = int(sd[name].get("step_count", h.step_count))
+        if self.check_finite:
+            self.coarse._guard["skipped"].fill_(int(sd["coarse"].get("skipped_steps", 0)))
 
     def apply_step(self, grad_allreduce=None, optimizer_step=True, should_accumulate=None):
         """One Adam step per half, each with its own step count (optim.apply_tail over the halves).  fp16: found-inf is the OR over

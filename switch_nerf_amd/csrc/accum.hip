@@ -45,6 +45,29 @@ __global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ acc
   }
 }
 
+// swn_grad_accum under the finite guard: a flagged micro-step contributes nothing and clears the window's partial sums (zero_grad)
+__global__ __launch_bounds__(256) void grad_accum_guarded_kernel(float* __restrict__ acc, const float* __restrict__ g, long n, long head,
+                                                                 long nvec, float scale, const int* __restrict__ ok) {
+  __shared__ int s_ok;
+  if (threadIdx.x == 0) s_ok = ok[0];
+  __syncthreads();
+  const bool add = s_ok != 0;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  for (long i = tid; i < nvec; i += stride) {
+    const long e = head + 4 * i;
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (add) {
+      const float4 a = *(const float4*)(acc + e), b = *(const float4*)(g + e);
+      r = make_float4(accum_add(a.x, b.x, scale), accum_add(a.y, b.y, scale), accum_add(a.z, b.z, scale), accum_add(a.w, b.w, scale));
+    }
+    *(float4*)(acc + e) = r;
+  }
+  for (long j = tid; j < n - 4 * nvec; j += stride) {
+    const long e = edge_index(j, head, nvec);
+    acc[e] = add ? accum_add(acc[e], g[e], scale) : 0.f;
+  }
+}
+
 struct AdamArgs {
   float lr, b1, b2, eps, bc1, bc2s, gscale, ascale;
 };
@@ -56,10 +79,12 @@ __device__ __forceinline__ float adam_accum_one(float a, float g, float p, float
   return adam_update(total, c.gscale, p, m, v, c.lr, c.b1, c.b2, c.eps, c.bc1, c.bc2s);
 }
 
+// The fused last micro-step over [0, n): 16-byte pieces on the aligned body, single elements around it.  The body of the unguarded
+// kernel and of the guarded one below: ONE text for both.
 template <typename T, bool HAS_GRAD>
-__global__ __launch_bounds__(256) void adam_accum_kernel(float* __restrict__ p, float* __restrict__ acc, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, T* __restrict__ shadow, long n,
-                                                         long head, long nvec, AdamArgs c) {
+__device__ __forceinline__ void adam_accum_range(float* __restrict__ p, float* __restrict__ acc, const float* __restrict__ g,
+                                                 float* __restrict__ m, float* __restrict__ v, T* __restrict__ shadow, long n, long head,
+                                                 long nvec, const AdamArgs& c) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
   for (long i = tid; i < nvec; i += stride) {
     const long e = head + 4 * i;
@@ -87,6 +112,30 @@ __global__ __launch_bounds__(256) void adam_accum_kernel(float* __restrict__ p, 
     acc[e] = 0.f;
     if (shadow) ElemIO<T>::st(shadow + e, po);
   }
+}
+
+template <typename T, bool HAS_GRAD>
+__global__ __launch_bounds__(256) void adam_accum_kernel(float* __restrict__ p, float* __restrict__ acc, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, T* __restrict__ shadow, long n,
+                                                         long head, long nvec, AdamArgs c) {
+  adam_accum_range<T, HAS_GRAD>(p, acc, g, m, v, shadow, n, head, nvec, c);
+}
+
+// adam_accum_kernel under the finite guard.  ok: the same loops with the step count and bias corrections read on the device.  A
+// skipped step is a store-only pass that clears acc - what a taken step leaves behind - and touches nothing else.
+template <typename T, bool HAS_GRAD>
+__global__ __launch_bounds__(256) void adam_accum_guarded_kernel(float* __restrict__ p, float* __restrict__ acc, const float* __restrict__ g,
+                                                                 float* __restrict__ m, float* __restrict__ v, T* __restrict__ shadow, long n,
+                                                                 long head, long nvec, AdamArgs c, GuardArgs ga) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  int t;
+  if (!guard_begin(ga, c.bc1, c.bc2s, t)) {
+    for (long i = tid; i < nvec; i += stride) *(float4*)(acc + head + 4 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long j = tid; j < n - 4 * nvec; j += stride) acc[edge_index(j, head, nvec)] = 0.f;
+    return;
+  }
+  adam_accum_range<T, HAS_GRAD>(p, acc, g, m, v, shadow, n, head, nvec, c);
+  guard_end(ga, t);
 }
 
 }  // namespace swn
@@ -123,6 +172,46 @@ extern "C" int swn_adam_accum_step(float* param, float* acc, const float* grad, 
     if (grad) SWN_ADAM_ACCUM(float, true); else SWN_ADAM_ACCUM(float, false);
   }
 #undef SWN_ADAM_ACCUM
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_grad_accum_guarded(float* acc, const float* grad, long n, float scale, const int* ok, void* stream) {
+  SWN_CHECK(acc && grad && ok && n >= 1, "swn_grad_accum_guarded: bad arguments");
+  SWN_CHECK((uintptr_t)acc % 4 == 0 && (uintptr_t)grad % 4 == 0 && (uintptr_t)ok % 4 == 0,
+            "swn_grad_accum_guarded: pointers must be 4-byte aligned");
+  const void* ptrs[2] = {acc, grad};
+  const AccumSplit s = accum_split(n, ptrs, 2, nullptr, 0);
+  hipLaunchKernelGGL(grad_accum_guarded_kernel, dim3(accum_blocks(n, s)), dim3(256), 0, as_stream(stream), acc, grad, n, s.head, s.nvec,
+                     scale, ok);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_adam_accum_step_guarded(float* param, float* acc, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow,
+                                           int dtype, long n, float lr, float beta1, float beta2, float eps, const float* bias_table,
+                                           long table_rows, int* step_state, float accum_scale, float grad_scale, const int* ok,
+                                           void* stream) {
+  SWN_CHECK(param && acc && exp_avg && exp_avg_sq && n >= 1, "swn_adam_accum_step_guarded: bad arguments");
+  SWN_CHECK(bias_table && table_rows >= 1 && step_state && ok, "swn_adam_accum_step_guarded: bias table, step state and flag are required");
+  SWN_CHECK((uintptr_t)bias_table % 4 == 0 && (uintptr_t)step_state % 4 == 0 && (uintptr_t)ok % 4 == 0,
+            "swn_adam_accum_step_guarded: misaligned pointer");
+  const bool half = shadow && dtype == SWN_HALF;
+  const void* ptrs[5] = {param, acc, grad, exp_avg, exp_avg_sq};
+  for (const void* q : ptrs) SWN_CHECK((uintptr_t)q % 4 == 0, "swn_adam_accum_step_guarded: pointers must be 4-byte aligned");
+  SWN_CHECK(!shadow || (uintptr_t)shadow % (half ? 2 : 4) == 0, "swn_adam_accum_step_guarded: misaligned shadow");
+  const AccumSplit s = accum_split(n, ptrs, 5, shadow, half ? 2 : 4);
+  const AdamArgs c = {lr, beta1, beta2, eps, 1.f, 1.f, grad_scale, accum_scale};      // (bc1, bc2s: read from the table in the kernel)
+  const GuardArgs ga = {ok, step_state, bias_table, table_rows};
+  const dim3 grid(accum_blocks(n, s)), block(256);
+#define SWN_ADAM_ACCUM_G(T, G) \
+  hipLaunchKernelGGL((adam_accum_guarded_kernel<T, G>), grid, block, 0, as_stream(stream), param, acc, grad, exp_avg, exp_avg_sq, (T*)shadow, n, s.head, s.nvec, c, ga)
+  if (half) {
+    if (grad) SWN_ADAM_ACCUM_G(bf16_t, true); else SWN_ADAM_ACCUM_G(bf16_t, false);
+  } else {
+    if (grad) SWN_ADAM_ACCUM_G(float, true); else SWN_ADAM_ACCUM_G(float, false);
+  }
+#undef SWN_ADAM_ACCUM_G
   SWN_LAUNCH_CHECK();
   return 0;
 }

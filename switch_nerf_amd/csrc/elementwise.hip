@@ -971,14 +971,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, T* __restrict__ shadow, long n, float lr, float b1,
                                                    float b2, float eps, float bc1, float bc2s, float gscale) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float mi = m[i], vi = v[i];
-    const float pi = adam_update(g[i], gscale, p[i], mi, vi, lr, b1, b2, eps, bc1, bc2s);   // adam.hpp: shared with swn_adam_accum_step
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-    if (shadow) ElemIO<T>::st(shadow + i, pi);
-  }
+  adam_range(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale);   // adam.hpp: shared with the guarded and the accumulating launches
 }
 
 template <typename T>

@@ -48,7 +48,11 @@ class GraphedTrainStep:
     gradient - final at that point, 14.7 of 15.8 MB - is issued on the model's side stream and travels while the second graph (router
     backward, front backward chain, dense weight gradients: a quarter of the step) runs; the dense prefix follows behind it.  This is
     the overlap DDP's buckets give the reference (runner.py:203-207); with one all-reduce behind the whole backward nothing hides it
-    at 1024 rays per GPU.  Results are bit-identical to the single-graph step (same sums over the same ranks)."""
+    at 1024 rays per GPU.  Results are bit-identical to the single-graph step (same sums over the same ranks).
+
+    Finite guard (model.set_check_finite, switched on before the capture): the guard's launch is part of the captured step and the
+    guarded optimizer launches behind the replay read its device flag, so ONE capture drops the step on a bad batch and takes it on a
+    good one, with no host read in between; res["step_ok"] is the flag of the last replay."""
 
     def __init__(self, model, rgbs, rays, image_indices, n_samples: int, seg_tokens: int, perturb: float = 1.0, noise_std: float = 1.0,
                  routing_override=None, warmup: int = 2, split_backward=None):
@@ -83,6 +87,7 @@ class GraphedTrainStep:
 
         was_profile, model.profile = model.profile, False
         step0 = model.noise_state_dict()["step"]           # the warm-up steps advance the noise counter like real ones: put it back
+        skipped0 = model._guard["skipped"].clone() if model.check_finite else None      # (and may count as skipped: put back too)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up on a side stream: allocates every cached buffer / workspace
@@ -95,9 +100,13 @@ class GraphedTrainStep:
         if dn:
             model._noise_step.fill_(step0)
             torch.cuda.synchronize()
+        if skipped0 is not None:
+            model._guard["skipped"].copy_(skipped0)
+            torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=side):
             self.res = run()
+        self.captures = 1                                  # captures of the step so far: replays never add one
         self.graph_b = None
         if self.split:
             self.graph_b = torch.cuda.CUDAGraph()
@@ -120,6 +129,8 @@ class GraphedTrainStep:
             self.idx.copy_(image_indices)
         self.graph.replay()
         ar = grad_allreduce
+        # finite guard: the ranks' MIN over the flag is the all-reduce OBJECT's; the split backward below hands apply_step a closure
+        flag_ar = getattr(grad_allreduce, "all_ranks_ok", None) if m.check_finite else None
         if self.graph_b is not None:
             if ar is not None and hasattr(ar, "begin") and m.accum_steps == 1:      # (accumulating: ONE all-reduce, of the buffer, in apply_step)
                 ar.begin(m.grad[m.n_dense:], m.side)       # the expert block is final: it travels under the second backward graph
@@ -127,7 +138,8 @@ class GraphedTrainStep:
             self.graph_b.replay()
         # all-reduce, loss-scale handling (fp16: inf check, skipped step, scale update - the captured step reads the scale from a
         # device scalar), Adam and the refresh of the compute copies (a second small graph): SwitchNeRF.apply_step
-        stepped = m.apply_step(ar, optimizer_step, refresh=self.copies.replay, should_accumulate=should_accumulate)
+        stepped = m.apply_step(ar, optimizer_step, refresh=self.copies.replay, should_accumulate=should_accumulate,
+                               **(dict(flag_allreduce=flag_ar) if flag_ar is not None else {}))
         if m.accum_steps > 1:
             self.res["optimizer_stepped"] = stepped
         return self.res
@@ -300,6 +312,8 @@ class GraphedBackgroundStep:
         scene._check_noise_sources()
         if scene.accum_steps > 1:
             raise NotImplementedError(scene._ACCUM_PADDED)
+        if scene.check_finite:
+            raise NotImplementedError(scene._GUARD_PADDED)
         self.scene = scene
         dev = scene.dev
         C = self.bg_capacity = N if bg_capacity is None else int(bg_capacity)

@@ -461,6 +461,14 @@ class MegaNeRF:
             raise NotImplementedError("MegaNeRF: gradient accumulation (set_accumulation) is not built for joint training: a window "
                                       "would span every cell model's buffer under the container's one step count")
 
+    _GUARD_JOINT = ("MegaNeRF: the finite guard (check_finite) is not built for joint training: the cells step under the container's "
+                    "one host step count")
+
+    def set_check_finite(self, on: bool = True):
+        """The finite guard (SwitchNeRF.set_check_finite) is not built for joint training through the cells: only off is taken."""
+        if on:
+            raise NotImplementedError(self._GUARD_JOINT)
+
     def apply_step(self, grad_allreduce=None, optimizer_step=True):
         """One Adam step on every cell with the model's one step count and learning rate.  A cell no point reached has a zero gradient,
         not a missing one: its step count advances, its moments decay and it moves by momentum, like the reference's joint_training cells
@@ -468,6 +476,8 @@ class MegaNeRF:
         self._need_joint("apply_step")
         if any(getattr(m, "accum_steps", 1) > 1 for m in self.sub_modules):
             raise NotImplementedError("MegaNeRF: gradient accumulation (set_accumulation on a cell model) is not built for joint training")
+        if any(getattr(m, "check_finite", False) for m in self.sub_modules):
+            raise NotImplementedError(self._GUARD_JOINT)
         if grad_allreduce is not None:
             raise NotImplementedError("MegaNeRF: data parallelism (a gradient all-reduce over the cells' buffers) is not built")
         if not optimizer_step:

@@ -30,7 +30,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, hier, ops
+from . import _lib, hier, ops, optim
 
 BUILDING = dict(model_dim=256, num_experts=8, expert_layers=7, skips=(3,), pos_xyz_dim=12, pos_dir_dim=4,
                 appearance_dim=48, appearance_count=10, gate_hidden=256, gate_layers=2, layer2_out=128)
@@ -109,6 +109,10 @@ DYNCAP_EP_ERROR = ("capacity_factor = 0 (dynamic capacity, nothing dropped) is n
                    "buffers are sized by a static capacity; use capacity_factor > 0, or < 0 (the dynamic capacity clamped at the static one)")
 ACCUM_OWNER_TAIL_ERROR = ("gradient accumulation (set_accumulation) is not built for expert parallelism with owner_tail=True: the tail's "
                           "gradient is summed on the experts' ranks inside the step")
+
+
+CHECK_FINITE_OWNER_TAIL_ERROR = ("the finite guard (check_finite) is not built for expert parallelism with owner_tail=True: the tail's "
+                                 "optimizer state is stepped on the experts' ranks inside the step")
 
 
 def accumulation_rule(iteration: int, steps: int) -> bool:
@@ -476,6 +480,8 @@ class SwitchNeRF:
             raise ValueError(DYNCAP_EP_ERROR)
         if ep is not None and getattr(ep, "owner_tail", False) and self.accum_steps > 1:
             raise NotImplementedError(ACCUM_OWNER_TAIL_ERROR)
+        if ep is not None and getattr(ep, "owner_tail", False) and self.check_finite:
+            raise NotImplementedError(CHECK_FINITE_OWNER_TAIL_ERROR)
         if ep is None and self.ep is not None:       # leaving expert parallelism: every rank needs every expert's trained weights
             self.gather_expert_shards()
         self.ep = ep
@@ -1418,6 +1424,65 @@ class SwitchNeRF:
         """The gradient the optimizer step consumes: the flat gradient, or the accumulation buffer while accumulation is on."""
         return self.accum if self.accum_steps > 1 else self.grad
 
+    # ------------------------------------------------------------------------------------------ finite guard
+    check_finite = False              # the reference's check_finite (runner.py:620-673; on by default there, off here)
+    _guard = None                     # on: dict(ok int32[1], skipped int64[1], step int32[2]) on the device
+    _step_host = 0
+
+    @property
+    def step_count(self) -> int:
+        """Optimizer steps taken (Adam's bias correction).  With the finite guard on the count lives on the device - a step the guard
+        drops must not advance it, and nothing in the step reads the flag on the host - and reading it here is a device-to-host read."""
+        return int(self._guard["step"][0].item()) if self._guard is not None else self._step_host
+
+    @step_count.setter
+    def step_count(self, n: int):
+        self._step_host = int(n)
+        if self._guard is not None:
+            self._guard["step"].copy_(torch.tensor([int(n), 0], dtype=torch.int32))
+
+    def set_check_finite(self, on: bool = True, share=None):
+        """The finite guard: a training step whose scalar metrics (photo / gate / total loss, psnr) are not all finite is dropped on
+        the device - no Adam step, no step-count advance, gradient accumulation buffer cleared - and counted (skipped_steps()).  A psnr
+        of +inf (a perfect reproduction) is allowed.  train_step then returns the device flag as res["step_ok"]; the host reads nothing.
+        share: the model whose flag and counter this one uses (the owner of several models - Cascade, BackgroundScene - sets it: one
+        check per step covers them all); each model keeps its own device step count.  Off: the step count returns to the host."""
+        on = bool(on)
+        if on and self.ep is not None and getattr(self.ep, "owner_tail", False):
+            raise NotImplementedError(CHECK_FINITE_OWNER_TAIL_ERROR)
+        count = self.step_count
+        if not on:
+            self.check_finite, self._guard = False, None
+            self._step_host = count
+            return
+        i = lambda n, dt: torch.zeros(n, dtype=dt, device=self.dev)
+        self._guard = dict(ok=share._guard["ok"] if share is not None else torch.ones(1, dtype=torch.int32, device=self.dev),
+                           skipped=share._guard["skipped"] if share is not None else i(1, torch.int64), step=i(2, torch.int32))
+        self.check_finite = True
+        self.step_count = count
+        ops.adam_bias_table(self.dev)          # exists before a capture (read, not created, inside a graph)
+
+    def skipped_steps(self) -> int:
+        """Steps the finite guard has dropped so far (a device-to-host read, on demand)."""
+        return int(self._guard["skipped"].item()) if self._guard is not None else 0
+
+    def finite_guard_state_dict(self) -> dict:
+        """{"check_finite", "skipped_steps", "step_count"} - what a resume needs besides the parameters and Adam's moments; store it
+        next to a checkpoint like noise_state_dict (state_dict itself is the reference's parameter key layout and holds tensors only)."""
+        return dict(check_finite=self.check_finite, skipped_steps=self.skipped_steps(), step_count=self.step_count)
+
+    def load_finite_guard_state_dict(self, sd: dict):
+        self.set_check_finite(bool(sd.get("check_finite", False)))
+        self.step_count = int(sd.get("step_count", self.step_count))
+        if self._guard is not None:
+            self._guard["skipped"].fill_(int(sd.get("skipped_steps", 0)))
+
+    def _finite_guard(self, metrics, psnr_slot: int):
+        """The guard's launch behind the loss kernel -> the device flag.  In a torch.distributed run the tail counts the skipped step,
+        behind the MIN all-reduce of the flag (optim.apply_tail); otherwise this launch does."""
+        g = self._guard
+        return ops.finite_guard(metrics, psnr_slot, g["ok"], None if optim.distributed() else g["skipped"])
+
     def grad_step(self, rgbs, rays, image_indices, n_samples, seg_tokens, perturb=1.0, perturb_rand=None, sigma_noise=None,
                   routing_override=None, fine_samples=0, fine_u=None, sigma_noise_fine=None, split=False, sigma_noise_std=0.0):
         """Forward + loss + backward of one training step: fills self.grad (zeroed first) and returns the metrics.  Nothing here
@@ -1461,14 +1526,20 @@ class SwitchNeRF:
             res["ctx_fine"] = cf
         if split:
             res["bwd_b"] = bwd_b
+        if self.check_finite:              # (inside a captured step: the flag is device state, like the noise counter)
+            res["step_ok"] = self._finite_guard(out4, 3)
         self._noise_advance()              # device noise: the next step draws at step + 1 (the last launch of the captured step)
         return res
 
-    def apply_step(self, grad_allreduce=None, optimizer_step=True, refresh=None, should_accumulate=None):
+    def apply_step(self, grad_allreduce=None, optimizer_step=True, refresh=None, should_accumulate=None, flag_allreduce=None):
         """Gradient all-reduce (N > 1) + Adam (runner.py:486, 686) + refresh of the compute copies of the weights (`refresh`: a
         replacement for refresh_compute_copies, e.g. the replay of its captured graph).
         With gradient accumulation on (set_accumulation(A > 1)) -> whether the optimizer stepped; should_accumulate: None = the
         model's window rule, a bool = the caller's decision for this micro-step (_apply_step_accum)."""
+        if self.check_finite:             # the guarded tails are wired in once, in optim.apply_tail: a group of this one model
+            stepped = optim.apply_tail([self], grad_allreduce=grad_allreduce, optimizer_step=optimizer_step, refresh=refresh,
+                                       should_accumulate=should_accumulate, flag_allreduce=flag_allreduce)
+            return stepped if self.accum_steps > 1 else None
         if self.accum_steps > 1:
             return self._apply_step_accum(grad_allreduce, optimizer_step, refresh, should_accumulate)
         if should_accumulate:
@@ -1679,6 +1750,8 @@ class SwitchNeRF:
         + wt * (mean(gate_loss_fine) + mean(gate_loss_coarse)) / 2, backward through both levels, Adam."""
         if self.accum_steps > 1:
             raise NotImplementedError("train_step_mip: gradient accumulation (set_accumulation) is not built for the mip step")
+        if self.check_finite:
+            raise NotImplementedError("train_step_mip: the finite guard (check_finite) is not built for the mip step")
         self.grad.zero_()
         c, cf = self.forward_mip(rays, radii, image_indices, n_samples, n_fine, seg_tokens, perturb, perturb_rand, fine_u,
                                  sigma_noise, sigma_noise_fine, False, rgb_padding, resample_padding, sigma_noise_std=sigma_noise_std)

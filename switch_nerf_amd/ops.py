@@ -4,6 +4,7 @@ Every function enqueues HIP kernels from libswn_hip.so on torch's current stream
 """
 from __future__ import annotations
 
+import math
 import os
 
 import ctypes as C
@@ -1595,6 +1596,71 @@ def adam_accum_step(param, acc, grad, m, v, shadow, step: int, lr: float, beta1=
     assert acc.numel() == n and (grad is None or grad.numel() == n)
     call("swn_adam_accum_step", _p(param), _p(acc), _p(grad), _p(m), _p(v), _p(shadow), _dt(shadow) if shadow is not None else F32, n,
          float(lr), float(beta1), float(beta2), float(eps), int(step), float(accum_scale), float(grad_scale), _stream())
+
+
+# ---- the finite guard (csrc/finite_guard.hip; the guarded accumulation launches: csrc/accum.hip)
+def finite_guard(metrics, psnr_slot: int, ok, skipped=None):
+    """ok[0] = 1 iff every metric is finite (+inf passes in slot psnr_slot; -1: no such slot); skipped[0] += 1 - ok.  One launch."""
+    assert metrics.dtype == torch.float32 and ok.dtype == torch.int32 and ok.numel() == 1
+    assert skipped is None or (skipped.dtype == torch.int64 and skipped.numel() == 1)
+    call("swn_finite_guard", _p(metrics), metrics.numel(), int(psnr_slot), _p(ok), _p(skipped), _stream())
+    return ok
+
+
+_bias_tables = {}
+
+
+def adam_bias_table(device, beta1=0.9, beta2=0.999):
+    """The device table [rows, 2] of Adam's bias corrections per step count that the guarded launches index (swn_adam_bias_table:
+    computed on the host by the expressions of swn_adam_step).  One per device and pair of betas, made on first use - a host-to-device
+    copy, so before a capture: set_check_finite makes the table of the default betas, a caller with other betas calls this first."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())      # "cuda" and "cuda:0" are one table
+    key = (device, float(beta1), float(beta2))
+    if key not in _bias_tables:
+        # the corrections are exactly 1 once beta^t < 2^-25 (half an ulp of 1): t > 25 ln 2 / -ln(beta), + 1 % and a few rows of slack
+        beta = float(torch.tensor(max(float(beta1), float(beta2)), dtype=torch.float32))      # (the fp32 value the launch is handed)
+        if not 0.0 <= beta < 1.0:
+            raise ValueError(f"adam_bias_table: betas must lie in [0, 1), got {beta1}, {beta2}")
+        cap = 64 if beta == 0.0 else int(1.01 * 25 * math.log(2.0) / -math.log(beta)) + 64
+        host = torch.empty(cap, 2, dtype=torch.float32)
+        rows = C.c_long(0)
+        call("swn_adam_bias_table", float(beta1), float(beta2), C.c_void_p(host.data_ptr()), cap, C.byref(rows))
+        _bias_tables[key] = host[: rows.value].to(device).contiguous()
+    return _bias_tables[key]
+
+
+def adam_step_guarded(param, grad, m, v, shadow, step_state, ok, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
+    """adam_step under the guard's flag: ok[0] = 1 takes optimizer step step_state[0] + 1 (the bits of adam_step) and advances
+    step_state[0]; ok[0] = 0 changes nothing.  step_state: int32[2] (see include/swn.h)."""
+    n = param.numel()
+    assert grad.numel() == m.numel() == v.numel() == n and step_state.dtype == torch.int32 and step_state.numel() == 2
+    assert ok.dtype == torch.int32 and ok.numel() == 1 and (shadow is None or shadow.numel() == n)
+    tab = adam_bias_table(param.device, beta1, beta2)
+    call("swn_adam_step_guarded", _p(param), _p(grad), _p(m), _p(v), _p(shadow), _dt(shadow) if shadow is not None else F32, n,
+         float(lr), float(beta1), float(beta2), float(eps), _p(tab), tab.shape[0], _p(step_state), float(grad_scale), _p(ok), _stream())
+
+
+def grad_accum_guarded(acc, grad, scale: float, ok):
+    """grad_accum under the guard's flag; ok[0] = 0 clears acc instead (a flagged micro-step discards the window's partial sums)."""
+    n = acc.numel()
+    assert grad.numel() == n and acc.dtype == grad.dtype == torch.float32 and ok.dtype == torch.int32 and ok.numel() == 1
+    call("swn_grad_accum_guarded", _p(acc), _p(grad), n, float(scale), _p(ok), _stream())
+    return acc
+
+
+def adam_accum_step_guarded(param, acc, grad, m, v, shadow, step_state, ok, lr: float, beta1=0.9, beta2=0.999, eps=1e-8,
+                            accum_scale=1.0, grad_scale=1.0):
+    """adam_accum_step under the guard's flag (step count as in adam_step_guarded); ok[0] = 0 clears acc and changes nothing else."""
+    n = param.numel()
+    assert acc.numel() == m.numel() == v.numel() == n and (grad is None or grad.numel() == n)
+    assert step_state.dtype == torch.int32 and step_state.numel() == 2 and ok.dtype == torch.int32 and ok.numel() == 1
+    assert shadow is None or shadow.numel() == n
+    tab = adam_bias_table(param.device, beta1, beta2)
+    call("swn_adam_accum_step_guarded", _p(param), _p(acc), _p(grad), _p(m), _p(v), _p(shadow),
+         _dt(shadow) if shadow is not None else F32, n, float(lr), float(beta1), float(beta2), float(eps), _p(tab), tab.shape[0],
+         _p(step_state), float(accum_scale), float(grad_scale), _p(ok), _stream())
 
 
 def cast(src, dst):

@@ -121,6 +121,13 @@ class GradAllReduce:
             self._timed("coll", lambda: dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group))
         return 1.0 / self.world
 
+    def all_ranks_ok(self, flag: torch.Tensor) -> torch.Tensor:
+        """The finite guard's per-rank flag (int32 [1], 1 = this rank's metrics are finite) -> in place, 1 only where every rank's is:
+        MIN over the ranks (combine_ok), on the current stream like the gradient's all-reduce."""
+        if self.active:
+            self._timed("coll", lambda: dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group))
+        return flag
+
     def begin(self, part: torch.Tensor, stream=None):
         """Start the all-reduce of `part` (final already) on `stream`, ordered after the work queued on the current stream."""
         self._drain()
@@ -164,6 +171,12 @@ class GradAllReduce:
         n = sum(1 for k, _a, _b in self._ev if k == "coll")
         self._ev = []
         return dict(collectives=n, allreduce_ms=coll, wait_ms=wait, hidden_fraction=(1.0 - wait / coll) if coll > 0 else None)
+
+
+def combine_ok(flags: torch.Tensor) -> torch.Tensor:
+    """The rule all_ranks_ok applies, on a tensor of per-rank flags [world] -> the step's flag.  The reference sums the flags and
+    compares with world_size (runner.py:660-666); for flags in {0, 1} that is their minimum."""
+    return flags.min()
 
 
 def make_grad_allreduce(group=None, loopback: bool = False) -> GradAllReduce:
