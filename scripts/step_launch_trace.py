@@ -3,7 +3,9 @@ descriptor field; pointers named after the model buffer / context key they fall 
 GPU is needed.  For host-side refactors: record the trace on two checkouts and compare - equal traces = the same kernels with the same
 arguments in the same order.  Not covered: the side-stream sections and the profile hooks (a CPU model has no side stream).
 
-    python scripts/step_launch_trace.py OUT.json [ROOT]     record (ROOT: the checkout whose switch_nerf_amd is traced, default this one)
+    python scripts/step_launch_trace.py OUT.json [ROOT [COUNTER]]     record (ROOT: the checkout whose switch_nerf_amd is traced, default
+                                                                      this one; COUNTER: the attribute path of a noise holder's step
+                                                                      counter there, default noise.step)
     python scripts/step_launch_trace.py --diff A.json B.json
 
 Every tensor whose address goes into a call is kept alive until its case ends, so no later buffer can take a freed temporary's address:
@@ -18,8 +20,13 @@ The `tail_*` cases trace apply_step alone, over every owner (model, cascade, sce
 fp32 host models; the torch calls of the tail (the inf check, accum.zero_(), the device scalar's fill_) are no library calls and do
 not show here: tests/test_optim_tail_cpu.py pins what they leave behind.  The `render_*` cases are the calls of
 tests/test_render_results_cpu.py through rendering.render_rays / render_rays_mip (autograd cases with their loss.backward()); that file
-pins the result dictionaries and the framework generator's consumption.  Captured-graph paths need a device and are not traced."""
+pins the result dictionaries and the framework generator's consumption.  Captured-graph paths need a device and are not traced.
+
+The `noise_*` cases run with seeded device noise on (a seed, a nonzero starting step, a nonzero ray_base) through the public API only
+and supply no noise tensors: the draws (seed, base, stream id, domain, scale), the in-kernel jitter and the counter's advance show with
+the counter named `c*.noise_step`.  tests/test_noise_state_cpu.py pins the host state behind them."""
 import ctypes as C
+import functools
 import json
 import sys
 
@@ -49,6 +56,7 @@ if sys.argv[1] == "--diff":
             print("   ", a[k][int(p.split("]")[0][1:])][0], p, str(u)[:120], "|", str(v)[:120])
     sys.exit(0)
 out_path, root = sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else HERE
+COUNTER = sys.argv[3] if len(sys.argv) > 3 else "noise.step"
 sys.path.insert(0, root)
 sys.path.insert(0, os.path.join(HERE, "tests"))
 import synth  # noqa: E402
@@ -292,6 +300,48 @@ def render(**kw):
 
 import test_optim_tail_cpu as tail_cases  # noqa: E402
 
+HASH = dict(n_levels=8, log2_table=12, base_res=4, per_level_scale=1.6, aabb_lo=(-1.2, -1.2, -1.2), aabb_hi=(1.2, 1.2, 1.2))
+
+
+def counter(holder):
+    return dict(noise_step=functools.reduce(getattr, COUNTER.split("."), holder))
+
+
+def noise_step(N=64, S=64, chunk=2048, fine=0, hash_grid=False, mip=False, **kw):
+    """grad_step / train_step_mip with device noise on and nothing supplied: jitter, sigma noise, fine u (and gate noise) are drawn"""
+    m = SwitchNeRF(dict(synth.BUILDING, hash=HASH) if hash_grid else synth.BUILDING, dtype=BF16, device="cpu", **kw)
+    m.set_device_noise(7, step=3, ray_base=5)
+    rays, img, rgbs = synth.make_rays(301, N)
+    if mip:
+        st = m.train_step_mip(dev(rgbs), dev(rays), torch.full((N, 1), 1e-3), dev(img), S + 1, fine + 1, chunk, perturb=1.0, sigma_noise_std=1.0)
+    else:
+        st = m.grad_step(dev(rgbs), dev(rays), dev(img), S, chunk, perturb=1.0, fine_samples=fine, sigma_noise_std=1.0)
+    return m, [st["ctx"]] + ([st["ctx_fine"]] if st.get("ctx_fine") is not None else []) + [counter(m)]
+
+
+def noise_scene(fine=0, N=16, S=8):
+    """BackgroundScene.train_step (compact form) with the scene's device noise on: both models' draws, one advance"""
+    m, b = DenseNeRF(synth.DENSE, dtype=F32, device="cpu"), DenseNeRF(synth.DENSE_BG, dtype=F32, device="cpu")
+    scene = BackgroundScene(m, b, synth.SPHERE_CENTER, synth.SPHERE_RADIUS)
+    scene.set_device_noise(7, step=3, ray_base=5)
+    rays, img, rgbs = synth.make_bg_rays(304, N)
+    st = scene.train_step(dev(rgbs), dev(rays), dev(img), S, N * S, perturb=1.0, fine_samples=fine, noise_std=1.0)
+    return [m, b], [st["ctx"], counter(scene)]
+
+
+class _OnDevice(torch.Tensor):
+    is_cuda = True      # (MoELayer.forward refuses host tensors; every launch behind it is mocked)
+
+
+def noise_moe_layer(P=64, M=64, E=4):
+    """One training forward of moe.MoELayer with gate noise drawn from the layer's seeded generator, and the advance behind it"""
+    from switch_nerf_amd.moe import MoELayer
+    layer = MoELayer(dict(type="top", k=1, capacity_factor=1.0, gate_noise=1.0), M, dict(type="expertmlp", count_per_node=E, layer_num=2),
+                     seeds=(1, 1, 1), dtype=F32).train()
+    layer.set_device_noise(7, step=3, row_base=5, device="cpu")
+    layer(torch.rand(P, M, generator=torch.Generator().manual_seed(308)).as_subclass(_OnDevice))
+    return [], [counter(layer)]
+
 MORE_CASES = {
     **{"render_" + k: (render, v) for k, v in render_cases.CASES.items()},
     **{"tail_" + k: (tail, v) for k, v in tail_cases.CASES.items()},
@@ -317,6 +367,15 @@ MORE_CASES = {
     "mega_train_fine": (mega, dict(fine=4)),
     "mega_sh_train_coarse": (mega, dict(cfg=CELL_SH)),
     "mega_sh_train_fine": (mega, dict(cfg=CELL_SH, fine=4)),
+    "noise_grad_step": (noise_step, dict()),
+    "noise_grad_step_fine": (noise_step, dict(fine=64)),
+    "noise_grad_step_gate_noise": (noise_step, dict(gate_noise=1.0)),
+    "noise_hash_grad_step": (noise_step, dict(hash_grid=True)),
+    "noise_hash_grad_step_fine": (noise_step, dict(hash_grid=True, fine=64)),
+    "noise_train_step_mip": (noise_step, dict(mip=True, fine=64)),
+    "noise_scene_train_step": (noise_scene, dict()),
+    "noise_scene_train_step_fine": (noise_scene, dict(fine=8)),
+    "noise_moe_layer": (noise_moe_layer, dict()),
 }
 res = {}
 for name, (fn, kw) in list((k, (train, v)) for k, v in CASES.items()) + list(MORE_CASES.items()):

@@ -44,9 +44,9 @@ class RenderRaysFunction(torch.autograd.Function):
         if isinstance(perturb_rand, str) and perturb_rand == "graph":
             from .graph import GraphedRenderTrain, cached_graph
             cache = nerf.__dict__.setdefault("_train_graphs", {})
-            dn = nerf._noise or {}                           # (a captured graph holds the seed and ray_base it was captured with)
+            dn = nerf.noise                                  # (a captured graph holds the seed and ray_base it was captured with)
             key = (rays.shape[0], S, F, int(chunk), float(perturb), float(sigma_noise or 0.0), bool(nerf.moe_no_batch), nerf.dtype,
-                   dn.get("seed"), dn.get("ray_base"))
+                   dn.seed, dn.base if dn.on else None)
             g = cached_graph(cache, key, lambda: GraphedRenderTrain(nerf, rays, image_indices, S, F, chunk, float(perturb),
                                                                     float(sigma_noise or 0.0)))
             state, outs = g.forward(rays, image_indices)

@@ -34,6 +34,7 @@ from __future__ import annotations
 import torch
 
 from . import hier, ops, optim
+from .noise import DeviceNoise
 
 
 class BackgroundScene:
@@ -51,6 +52,7 @@ class BackgroundScene:
         self.center, self.radius = sphere_center, sphere_radius
         bg_nerf._grow_bufs = True           # the number of background rays changes every batch
         self.dev = nerf.dev
+        self.noise, self._fg_noise = DeviceNoise(), None      # the ONE noise state of both models (set_device_noise)
         # ONE loss scaler over both models (the reference's single GradScaler over both optimizers, runner.py:483, 679-690): when either
         # model computes in fp16, both hold the SAME LossScaler object - one scale multiplies the loss gradient, both unscale by it, one
         # growth tracker is checkpointed whichever model's state_dict is asked (a 16-bit-float foreground beside an fp16 background included)
@@ -78,65 +80,45 @@ class BackgroundScene:
                 m._ls_dev = None
 
     # ------------------------------------------------------------------------------------------ seeded device noise
-    _noise = None            # {"seed", "ray_base"} while the scene's device noise is on
-    _noise_step = None       # the ONE step counter of both models: a device int64[1] (the foreground model holds the same tensor)
-    _fg_own_noise = None     # the foreground model's (_noise, _noise_step, _ray_base_pending) from before the switch-on
-
     def set_device_noise(self, seed, step: int = 0, ray_base: int = 0):
         """Seeded device-side noise for both models (SwitchNeRF.set_device_noise has the contract); seed = None switches it off and hands
         the foreground model back the noise state it had.  On: the foreground model is switched on with the same seed and the SAME counter
         tensor, so it draws its streams as it does without a background; a TRAINING forward draws what the caller does not supply for the
         background model - jitter, coarse / fine sigma noise (noise_std > 0), fine u - from the generator's background domain, background
-        row j being global ray ray_base + idx_bg[j].  train_step ends in one advance of the counter."""
-        nerf = self.nerf
+        row j being global ray ray_base + idx_bg[j].  train_step ends in one advance of the counter.  While it is on the model holds a
+        lent copy of self.noise (DeviceNoise.lend) and self._fg_noise keeps the model's own object, from before the FIRST switch-on."""
+        nerf, was_on = self.nerf, self.noise.on
+        self.noise.set(seed, step, ray_base, self.dev)
         if seed is None:
-            if self._noise is not None:
-                nerf._noise, nerf._noise_step, nerf._ray_base_pending = self._fg_own_noise
-                nerf._noise_scene = None
-            self._noise = self._fg_own_noise = None
+            if was_on:
+                nerf.noise = self._fg_noise
+            self._fg_noise = None
             return
-        seed, ray_base = int(seed), int(ray_base)
-        if not 0 <= seed < 1 << 64:
-            raise ValueError(f"device noise: seed {seed} outside [0, 2^64)")
-        if ray_base < 0:
-            raise ValueError(f"device noise: ray_base {ray_base} < 0")
-        step = ops.rng_check_step(step)
-        if self._noise_step is None:
-            self._noise_step = ops.rng_step_tensor(step, self.dev)
-        else:
-            self._noise_step.fill_(step)
-        if self._noise is None:
-            self._fg_own_noise = (nerf._noise, nerf._noise_step, nerf._ray_base_pending)
-        self._noise = dict(seed=seed, ray_base=ray_base)
-        nerf._noise, nerf._noise_step, nerf._ray_base_pending = dict(seed=seed, ray_base=ray_base), self._noise_step, ray_base
-        nerf._noise_scene = self             # (rendering._device_noise: this model's noise is the scene's business)
+        if not was_on:
+            self._fg_noise = nerf.noise
+        nerf.noise = self.noise.lend(self)       # (rendering._device_noise: this model's noise is the scene's business)
 
     @property
     def device_noise(self) -> bool:
-        return self._noise is not None
+        return self.noise.on
 
     def set_ray_base(self, ray_base: int):
         """The global index of this process's first ray (parallel.shard_rays(..., model=scene)), for both models.  Nothing to set while
         the noise is off: set_device_noise takes the ray_base it starts with."""
-        if int(ray_base) < 0:
-            raise ValueError(f"device noise: ray_base {ray_base} < 0")
-        if self._noise is not None:
-            self._noise["ray_base"] = int(ray_base)
+        self.noise.set_base(ray_base)
+        if self.noise.on:
             self.nerf.set_ray_base(ray_base)
 
     def noise_state_dict(self) -> dict:
         """{"seed", "step", "ray_base"} of the scene (both models): what a resume needs besides the parameters.  Reads the step back."""
-        if self._noise is None:
-            return dict(seed=None, step=0, ray_base=0)
-        return dict(seed=self._noise["seed"], step=int(self._noise_step.item()), ray_base=self._noise["ray_base"])
+        return self.noise.state_dict()
 
     def load_noise_state_dict(self, sd: dict):
         self.set_device_noise(sd.get("seed"), int(sd.get("step", 0)), int(sd.get("ray_base", 0)))
 
     def _noise_advance(self):
         """The one advance of the shared step counter that ends a training step.  Nothing with the noise off."""
-        if self._noise is not None:
-            ops.rng_advance(self._noise_step)
+        self.noise.advance()
 
     def _check_noise_sources(self):
         """Never mix the two noise sources silently: a model drawing seeded noise of its own inside a scene that draws the background's
@@ -145,12 +127,11 @@ class BackgroundScene:
         if getattr(bg, "device_noise", False):
             raise RuntimeError("BackgroundScene: the background model's own device noise is on (bg_nerf.set_device_noise): the scene "
                                "carries the noise of both models - turn it off there and call BackgroundScene.set_device_noise(seed)")
-        if self._noise is None and getattr(nerf, "device_noise", False):
+        if not self.noise.on and getattr(nerf, "device_noise", False):
             raise RuntimeError("BackgroundScene: the foreground model's device noise is on but the scene's is not, so the background "
                                "would draw from the framework generator - call BackgroundScene.set_device_noise(seed) instead of "
                                "the model's set_device_noise (or turn the model's off)")
-        if self._noise is not None and (nerf._noise_step is not self._noise_step or nerf._noise is None
-                                        or nerf._noise["seed"] != self._noise["seed"]):
+        if self.noise.on and (nerf.noise.step is not self.noise.step or not nerf.noise.on or nerf.noise.seed != self.noise.seed):
             raise RuntimeError("BackgroundScene: the foreground model's device noise was changed behind the scene's back "
                                "(SwitchNeRF.set_device_noise after BackgroundScene.set_device_noise): set it on the scene")
 
@@ -174,7 +155,7 @@ class BackgroundScene:
         exclusive upper bound of its entries, e.g. the full batch's rays) instead of a host read of its maximum."""
         o, nerf, bg = ops, self.nerf, self.bg
         self._check_noise_sources()
-        dn = self._noise if training else None
+        dn = self.noise if training and self.noise.on else None
         N, S, Fn = rays.shape[0], n_samples, int(fine_samples)
         padded = bg_capacity is not None
         if padded:
@@ -210,10 +191,10 @@ class BackgroundScene:
                     rows = ray_index.index_select(0, idx_bg)
                     lim = int(ray_index_limit) if ray_index_limit is not None else int(ray_index.max().item()) + 1
                 draw = lambda stream, per_row, kind, scale=1.0: o.rng_fill_rows(
-                    Nb, per_row, dn["ray_base"], rows, kind, dn["seed"], self._noise_step, stream, o.RNG_DOMAIN_BG, scale, lim)
+                    Nb, per_row, dn.base, rows, kind, dn.seed, dn.step, stream, o.RNG_DOMAIN_BG, scale, lim)
             if dn is not None and perturb > 0 and perturb_rand_bg is None:
                 z_b, dreal_b, pe_b = o.bg_sample_pe_rng(rays_b, self.center, self.radius, Sb, bg.cfg["pos_xyz_dim"], bg.dtype, bg.KP,
-                                                        dn["seed"], self._noise_step, dn["ray_base"], rows, lim, float(perturb),
+                                                        dn.seed, dn.step, dn.base, rows, lim, float(perturb),
                                                         pe_out=bg._buf("c:pe", (Nb * Sb, bg.KP), bg.dtype))
             else:
                 if perturb > 0 and perturb_rand_bg is None:

@@ -135,7 +135,7 @@ class Cascade:
     # ------------------------------------------------------------------------------------------ what stays refused
     def _check_runtime(self):
         for h in self.halves():
-            if getattr(h, "device_noise", False) or getattr(h, "_noise_scene", None) is not None:
+            if getattr(h, "device_noise", False) or getattr(getattr(h, "noise", None), "owner", None) is not None:
                 _refuse("seeded device noise (set_device_noise)")
             if getattr(h, "graph_train", False) or getattr(h, "graph_eval", False):
                 _refuse("graph capture (graph_train / graph_eval)")

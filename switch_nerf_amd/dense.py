@@ -184,7 +184,7 @@ class DenseNeRF(SwitchNeRF):
     # ------------------------------------------------------------------------------------------ forward
     def forward_rays(self, rays, *args, head=None, **kw):
         if self.sh_deg is not None:
-            if self._noise_scene is not None or self.xyz_dim != 3:
+            if self.noise.owner is not None or self.xyz_dim != 3:
                 raise NotImplementedError("sh_deg: a background model / a scene with one is not built with spherical-harmonics colour")
             if head is None:      # the heads contract against the fp32 ray directions of THIS pass
                 head = ShHead(rays[:, 3:6].contiguous(), False)

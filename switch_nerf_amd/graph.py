@@ -98,7 +98,7 @@ class GraphedTrainStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         if dn:
-            model._noise_step.fill_(step0)
+            model.noise.rewind(step0)
             torch.cuda.synchronize()
         if skipped0 is not None:
             model._guard["skipped"].copy_(skipped0)
@@ -255,7 +255,7 @@ class GraphedRenderTrain:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         if dn:
-            model._noise_step.fill_(step0)
+            model.noise.rewind(step0)
             torch.cuda.synchronize()
         self.fwd_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.fwd_graph, stream=side):
@@ -348,7 +348,7 @@ class GraphedBackgroundStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         if dn:
-            scene._noise_step.fill_(step0)
+            scene.noise.rewind(step0)
             torch.cuda.synchronize()
         # the background model's cached buffers grow with the largest row count seen (a later eager compact step on a larger batch
         # replaces them): the capture keeps the ones it baked in alive

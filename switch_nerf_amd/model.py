@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib, hier, ops, optim
+from .noise import DeviceNoise
 
 BUILDING = dict(model_dim=256, num_experts=8, expert_layers=7, skips=(3,), pos_xyz_dim=12, pos_dir_dim=4,
                 appearance_dim=48, appearance_count=10, gate_hidden=256, gate_layers=2, layer2_out=128)
@@ -176,6 +177,7 @@ class SwitchNeRF:
         self._kernel_sel = {}         # kernel_set(): what the last forward / backward selected
         self.ep = None                # parallel.ExpertParallel: experts sharded over ranks, tokens exchanged (set_expert_parallel)
         self.expert_wgrad_splits = 0         # row splits of the legacy expert weight-gradient launch (0 = heuristic)
+        self.noise = DeviceNoise()    # the seeded device noise's state (set_device_noise); a BackgroundScene lends its own while it is on
 
     def _configure(self, cfg):
         """Sets the network dimensions and returns the flat parameter layout [(name, shape)]; Linear weights are [in, out]."""
@@ -572,14 +574,14 @@ class SwitchNeRF:
         o, dt, dev = ops, self.dtype, self.dev
         N, S = rays.shape[0], n_samples
         self._sync_compute_copies()       # (an optimizer outside this class may have stepped flat_param since the last forward)
-        dn = self._noise if training else None
+        dn = self.noise if training and self.noise.on else None
         jitter_rng = dn is not None and perturb > 0 and perturb_rand is None and z_in is None
         drawn = None
         if dn is not None and sigma_noise is None and sigma_noise_std > 0:
-            sigma_noise = drawn = self._draw(o.RNG_SIGMA if tag == "c" else o.RNG_SIGMA_FINE, N * S, dn["ray_base"] * S, o.RNG_NORMAL,
-                                             float(sigma_noise_std))
+            sigma_noise = drawn = dn.draw(o.RNG_SIGMA if tag == "c" else o.RNG_SIGMA_FINE, N * S, dn.base * S, o.RNG_NORMAL,
+                                          float(sigma_noise_std))
         if jitter_rng and self.hash is not None:      # (the plain path draws it inside swn_sample_pe_rng)
-            perturb_rand = self._draw(o.RNG_JITTER, N * S, dn["ray_base"] * S, o.RNG_UNIFORM).view(N, S)
+            perturb_rand = dn.draw(o.RNG_JITTER, N * S, dn.base * S, o.RNG_UNIFORM).view(N, S)
         if self.hash is not None:         # hash-grid encoding of the sample positions (BASELINE configs[4])
             z = z_in if z_in is not None else o.sample_z(rays, self._linspace(S), perturb_rand,
                                                          perturb, S)
@@ -589,7 +591,7 @@ class SwitchNeRF:
         elif z_in is None:
             t_steps = self._linspace(S)
             if jitter_rng:
-                z, pe, pe_dir = o.sample_pe_rng(rays, t_steps, dn["seed"], self._noise_step, dn["ray_base"], perturb, S,
+                z, pe, pe_dir = o.sample_pe_rng(rays, t_steps, dn.seed, dn.step, dn.base, perturb, S,
                                                 self.cfg["pos_xyz_dim"], self.cfg["pos_dir_dim"], dt, self.KP, self.DP)
             else:
                 z, pe, pe_dir = o.sample_pe(rays, t_steps, perturb_rand, perturb, S, self.cfg["pos_xyz_dim"],
@@ -610,11 +612,6 @@ class SwitchNeRF:
         return c
 
     # ------------------------------------------------------------------------------------------ seeded device noise
-    _noise = None            # {"seed", "ray_base"} while device noise is on
-    _ray_base_pending = 0    # set_ray_base() ahead of a switch-on by rendering.render_rays (hparams.device_noise_seed)
-    _noise_step = None       # the step counter: a device int64[1] owned by the model (the kernels read it, swn_rng_advance bumps it)
-    _noise_scene = None      # the background.BackgroundScene that carries this model's noise (its seed, ITS counter tensor), if any
-
     def set_device_noise(self, seed, step: int = 0, ray_base: int = 0):
         """Seeded device-side noise (csrc/philox.hpp): seed = None turns it off (the default - nothing differs from a model that never
         called this).  On: a TRAINING forward draws what the caller does not supply - the stratified jitter (perturb > 0), the sigma
@@ -623,54 +620,28 @@ class SwitchNeRF:
         mode and in a captured graph, on one GPU and on W GPUs (ray_base = the rank's first global ray), and after a resume
         (noise_state_dict).  The step lives on the device and is advanced by the last launch of every training step.
         (A graph captured earlier keeps the seed and ray_base it was captured with; the step it reads from the device.)"""
-        if seed is None:
-            self._noise = None
-            return
-        seed, ray_base = int(seed), int(ray_base)
-        if not 0 <= seed < 1 << 64:
-            raise ValueError(f"device noise: seed {seed} outside [0, 2^64)")
-        if ray_base < 0:
-            raise ValueError(f"device noise: ray_base {ray_base} < 0")
-        step = ops.rng_check_step(step)
-        if self._noise_step is None:
-            self._noise_step = ops.rng_step_tensor(step, self.dev)
-        else:
-            self._noise_step.fill_(step)          # (the same tensor: captured launches hold its address)
-        self._noise = dict(seed=seed, ray_base=ray_base)
-        self._ray_base_pending = ray_base
+        self.noise.set(seed, step, ray_base, self.dev)
 
     @property
     def device_noise(self) -> bool:
-        return self._noise is not None
+        return self.noise.on
 
     def set_ray_base(self, ray_base: int):
         """The global index of this model's first ray (data parallel: the rank's slice of the batch, parallel.shard_rays).  Set before
         the noise is switched on through hparams.device_noise_seed (rendering.render_rays), it is what that switch-on starts with."""
-        if int(ray_base) < 0:
-            raise ValueError(f"device noise: ray_base {ray_base} < 0")
-        self._ray_base_pending = int(ray_base)
-        if self._noise is not None:
-            self._noise["ray_base"] = int(ray_base)
+        self.noise.set_base(ray_base)
 
     def noise_state_dict(self) -> dict:
         """{"seed", "step", "ray_base"} - what a resume needs besides the parameters (seed None: device noise off).  Reads the step
         back from the device.  Store it next to a checkpoint, e.g. torch.save({**ckpt, "noise_state": model.noise_state_dict()})."""
-        if self._noise is None:
-            return dict(seed=None, step=0, ray_base=0)
-        return dict(seed=self._noise["seed"], step=int(self._noise_step.item()), ray_base=self._noise["ray_base"])
+        return self.noise.state_dict()
 
     def load_noise_state_dict(self, sd: dict):
         self.set_device_noise(sd.get("seed"), int(sd.get("step", 0)), int(sd.get("ray_base", 0)))
 
-    def _draw(self, stream_id: int, n: int, elem_base: int, kind: int, scale: float = 1.0):
-        """n draws of a stream from global element elem_base on -> f32 [n] (swn_rng_fill; consumed through the supplied-noise arguments)."""
-        return ops.rng_fill(n, elem_base, kind, self._noise["seed"], self._noise_step, stream_id, scale)
-
     def _noise_advance(self):
         """The step counter's advance: the LAST launch of a training step (inside a captured step).  Nothing with device noise off."""
-        if self._noise is not None:
-            step = self._noise_step
-            ops.rng_advance(step)
+        self.noise.advance()
 
     def _dir_pe(self, rays):
         """PE of the ray directions only (per ray)."""
@@ -834,9 +805,9 @@ class SwitchNeRF:
                     x_features=self.KP if big else 0)
         if not (sv and self.gate_noise > 0):       # (training only, like `self.training and self.gate_noise > 0`)
             return None
-        if self.gate_noise_draw is None and self._noise is not None:     # stream 4, element (ray_base * S + point) * E + expert
+        if self.gate_noise_draw is None and self.noise.on:     # stream 4, element (ray_base * S + point) * E + expert
             r0 = 0 if row_range is None else row_range[0]
-            return self._draw(o.RNG_GATE, P * E, (self._noise["ray_base"] * S + r0) * E, o.RNG_NORMAL).view(P, E)
+            return self.noise.draw(o.RNG_GATE, P * E, (self.noise.base * S + r0) * E, o.RNG_NORMAL).view(P, E)
         if self.gate_noise_draw is None:
             return torch.randn(P, E, device=dev, dtype=torch.float32)
         # a supplied draw (tests): [N * S, E] of this pass's point grid; a row range takes its rows
@@ -1660,9 +1631,9 @@ class SwitchNeRF:
         N = rays.shape[0]
         c = self.forward_rays(rays, image_indices, n_samples, seg_tokens, perturb, perturb_rand, sigma_noise, training,
                               routing_override, no_batch=no_batch, want_weights=True, sigma_noise_std=sigma_noise_std)
-        if fine_u is None and perturb != 0 and training and self._noise is not None:      # device noise: stream 2
-            fine_u = self._draw(ops.RNG_FINE_U, N * fine_samples, self._noise["ray_base"] * fine_samples,
-                                ops.RNG_UNIFORM).view(N, fine_samples)
+        if fine_u is None and perturb != 0 and training and self.noise.on:      # device noise: stream 2
+            fine_u = self.noise.draw(ops.RNG_FINE_U, N * fine_samples, self.noise.base * fine_samples,
+                                     ops.RNG_UNIFORM).view(N, fine_samples)
         if fine_u is None:
             fine_u = hier.default_fine_u(self._linspace, N, fine_samples, perturb, self.dev)
         z_fine = ops.sample_pdf(c["z"], c["weights"], fine_u, fine_samples)
@@ -1699,9 +1670,9 @@ class SwitchNeRF:
             pe_dir = self._dir_pe(rays)
         seg = min(seg_tokens, N * S1)
         drawn = None
-        if training and self._noise is not None and sigma_noise is None and sigma_noise_std > 0:      # one value per interval
-            sigma_noise = drawn = self._draw(ops.RNG_SIGMA if tag == "c" else ops.RNG_SIGMA_FINE, N * S1, self._noise["ray_base"] * S1,
-                                     ops.RNG_NORMAL, float(sigma_noise_std))
+        if training and self.noise.on and sigma_noise is None and sigma_noise_std > 0:      # one value per interval
+            sigma_noise = drawn = self.noise.draw(ops.RNG_SIGMA if tag == "c" else ops.RNG_SIGMA_FINE, N * S1, self.noise.base * S1,
+                                                  ops.RNG_NORMAL, float(sigma_noise_std))
         c = self._net_forward(pe, pe_dir, image_indices, N, S1, seg, sigma_noise, None, no_batch, tag, saving=bool(training))
         c["z_edges"] = z
         if drawn is not None:
@@ -1726,16 +1697,16 @@ class SwitchNeRF:
             fine_randomized = perturb > 0
         t_steps = self._linspace(n_samples)
         radii = radii.reshape(-1).contiguous()
-        dn = self._noise if training else None
+        dn = self.noise if training and self.noise.on else None
         if dn is not None and perturb > 0 and perturb_rand is None:       # device noise: stream 0 through the fill
-            perturb_rand = self._draw(ops.RNG_JITTER, N * n_samples, dn["ray_base"] * n_samples, ops.RNG_UNIFORM).view(N, n_samples)
+            perturb_rand = dn.draw(ops.RNG_JITTER, N * n_samples, dn.base * n_samples, ops.RNG_UNIFORM).view(N, n_samples)
         z = ops.sample_z(rays, t_steps, perturb_rand, perturb, n_samples)
         c = self.forward_level_mip(rays, radii, image_indices, z, seg_tokens, sigma_noise, no_batch, "c", n_fine > 0, rgb_padding,
                                    training=training, sigma_noise_std=sigma_noise_std)
         if n_fine <= 0:
             return c, None
         if fine_u is None and fine_randomized and dn is not None:          # stream 2
-            fine_u = self._draw(ops.RNG_FINE_U, N * n_fine, dn["ray_base"] * n_fine, ops.RNG_UNIFORM).view(N, n_fine)
+            fine_u = dn.draw(ops.RNG_FINE_U, N * n_fine, dn.base * n_fine, ops.RNG_UNIFORM).view(N, n_fine)
         if fine_u is None and fine_randomized:
             fine_u = torch.rand(N, n_fine, device=self.dev)
         z_f = ops.mip_resample(z, c["weights"], fine_u if fine_randomized else None, n_fine, resample_padding)

@@ -31,6 +31,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .noise import DeviceNoise
 
 
 def layer_capacity(capacity_factor: float, n_tokens: int, n_experts: int, top_k: int = 1, max_rows: Optional[int] = None) -> int:
@@ -360,6 +361,7 @@ class MoELayer(nn.Module):
         # additive, so they reach the router kernel as ONE noise operand (swn_gate_fwd_noise)
         self.use_normal_noise = bool(gate_type.get("use_normal_noise", False))
         self._noise_scale = 0.0
+        self.noise = DeviceNoise()                 # seeded device noise of the router's draws (set_device_noise); base = row_base
         # --use_load_importance_loss (opts.py:210; extract_critical_load_importance, tutel_fast_dispatch.py:219-265): the layer's loss is the
         # load / importance loss of "Scaling Vision with Sparse MoE" instead of the load-balance loss; needs gate_noise > 0 (:154)
         self.use_load_importance_loss = bool(gate_type.get("use_load_importance_loss", False))
@@ -401,15 +403,14 @@ class MoELayer(nn.Module):
         ex = self.experts[0]
         noise = clean = None
         E = self.n_experts
-        dn, drew = self._noise, []
+        dn, drew = self.noise, []
 
         def draw(given, stream_id):
             if given is not None:
                 return given.to(x.device, torch.float32).reshape(-1, E).contiguous()
-            if dn is not None:                 # seeded device noise (set_device_noise): element (row_base + p) * E + e of the stream
+            if dn.on:                          # seeded device noise (set_device_noise): element (row_base + p) * E + e of the stream
                 drew.append(stream_id)
-                return ops.rng_fill(x.shape[0] * E, dn["row_base"] * E, ops.RNG_NORMAL, dn["seed"], self._noise_step,
-                                    stream_id).view(-1, E)
+                return dn.draw(stream_id, x.shape[0] * E, dn.base * E, ops.RNG_NORMAL).view(-1, E)
             return torch.randn(x.shape[0], E, device=x.device, dtype=torch.float32)
         if self.training and self.use_normal_noise:            # logits + n1 / E (+ gate_noise * n2 / E) = logits + (n1 + gate_noise * n2) / E
             noise = clean = draw(normal_noise_draw, ops.RNG_ROUTER_NORMAL)    # (clean: the part that belongs to `logits` in the load / importance loss, :116-117)
@@ -420,7 +421,7 @@ class MoELayer(nn.Module):
             noise = draw(gate_noise_draw, ops.RNG_GATE)
             self._noise_scale = self.gate_noise / E
         if drew:
-            ops.rng_advance(self._noise_step)      # the next training forward draws at step + 1
+            dn.advance()                           # the next training forward draws at step + 1
         l_bal = None
         if self.top_k == 1 and not self.use_load_importance_loss:
             y, l_aux, idx = _MoEFunction.apply(self, x, g, self.gates[0].wg.weight, noise, *ex.weights, *ex.bias)
@@ -439,30 +440,17 @@ class MoELayer(nn.Module):
             y.gate_extras = extras
         return y
 
-    _noise = None            # {"seed", "row_base"} while seeded device noise is on
-    _noise_step = None       # its step counter: a device int64[1] owned by the layer
-
     def set_device_noise(self, seed, step: int = 0, row_base: int = 0, device="cuda"):
         """The switch of SwitchNeRF.set_device_noise for this layer's router noise: seed = None (default) draws with torch.randn as
         before; a seed draws the gate noise (and the use_normal_noise draw, a stream of its own) of a TRAINING forward from the library's
         Philox generator keyed by (seed, step, stream, (row_base + token) * E + expert); the counter advances once per forward that drew.
         Supplied draws (gate_noise_draw / normal_noise_draw) still win."""
-        if seed is None:
-            self._noise = None
-            return
-        if not 0 <= int(seed) < 1 << 64 or int(row_base) < 0:
+        if seed is not None and (not 0 <= int(seed) < 1 << 64 or int(row_base) < 0):
             raise ValueError("device noise: seed outside [0, 2^64) or row_base < 0")
-        step = ops.rng_check_step(step)
-        if self._noise_step is None:
-            self._noise_step = ops.rng_step_tensor(step, device)
-        else:
-            self._noise_step.fill_(step)
-        self._noise = dict(seed=int(seed), row_base=int(row_base))
+        self.noise.set(seed, step, row_base, device)
 
     def noise_state_dict(self) -> dict:
-        if self._noise is None:
-            return dict(seed=None, step=0, row_base=0)
-        return dict(seed=self._noise["seed"], step=int(self._noise_step.item()), row_base=self._noise["row_base"])
+        return self.noise.state_dict("row_base")
 
     def load_noise_state_dict(self, sd: dict):
         self.set_device_noise(sd.get("seed"), int(sd.get("step", 0)), int(sd.get("row_base", 0)))

@@ -58,7 +58,7 @@ def _device_noise(nerf, bg_nerf, hparams) -> bool:
     Returns whether the model draws its own noise.  A model whose noise is carried by a BackgroundScene (BackgroundScene.set_device_noise
     marks it) does not: the scene draws for both models and advances the one counter (_render_rays_bg)."""
     seed = getattr(hparams, "device_noise_seed", None)
-    by_scene = getattr(nerf, "_noise_scene", None) is not None
+    by_scene = getattr(getattr(nerf, "noise", None), "owner", None) is not None
     if seed is None and (by_scene or not getattr(nerf, "device_noise", False)):
         return False
     if by_scene:
@@ -74,9 +74,8 @@ def _device_noise(nerf, bg_nerf, hparams) -> bool:
     if seed is None:                      # (switched on by the caller: SwitchNeRF.set_device_noise)
         return True
     ray_base = getattr(hparams, "ray_base", None)
-    if not nerf.device_noise or nerf._noise["seed"] != int(seed):
-        keep = nerf._noise["ray_base"] if nerf.device_noise else getattr(nerf, "_ray_base_pending", 0)
-        nerf.set_device_noise(int(seed), 0, keep if ray_base is None else int(ray_base))
+    if not nerf.device_noise or nerf.noise.seed != int(seed):      # (the base outlives a switch-off: set_ray_base ahead of this)
+        nerf.set_device_noise(int(seed), 0, nerf.noise.base if ray_base is None else int(ray_base))
     elif ray_base is not None:
         nerf.set_ray_base(int(ray_base))
     return True

@@ -244,7 +244,7 @@ def test_batch_without_background_rays_advances_once():
     rays, img, rgbs = (_dev(a) for a in synth.make_rays(703, N_RAYS, far=0.3))      # every far below the bound
     st = sc.train_step(rgbs, rays, img, S_SAMPLES, CHUNK, perturb=1.0, noise_std=STD)
     assert st["ctx"]["Nb"] == 0 and sc.bg.step_count == 0 and sc.nerf.step_count == 1
-    assert sc.noise_state_dict()["step"] == 6 and int(sc.nerf._noise_step.item()) == 6
+    assert sc.noise_state_dict()["step"] == 6 and int(sc.nerf.noise.step.item()) == 6
     _train(sc, [_batch()])
     assert sc.noise_state_dict()["step"] == 7
 
@@ -291,12 +291,12 @@ def test_mixed_noise_sources_are_refused():
 def test_detach_hands_the_foreground_its_noise_state_back():
     sc = _scene()
     sc.nerf.set_device_noise(3, step=4, ray_base=9)
-    own_step = sc.nerf._noise_step
+    own_step = sc.nerf.noise.step
     sc.set_device_noise(11)
-    assert sc.nerf._noise_step is sc._noise_step and sc.nerf.noise_state_dict() == dict(seed=11, step=0, ray_base=0)
+    assert sc.nerf.noise.step is sc.noise.step and sc.nerf.noise_state_dict() == dict(seed=11, step=0, ray_base=0)
     assert not sc.bg.device_noise                                   # the background model never holds a counter
     sc.detach()
-    assert not sc.device_noise and sc.nerf._noise_step is own_step
+    assert not sc.device_noise and sc.nerf.noise.step is own_step
     assert sc.nerf.noise_state_dict() == dict(seed=3, step=4, ray_base=9)
 
 

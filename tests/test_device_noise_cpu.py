@@ -85,10 +85,13 @@ def test_render_rays_switch_keeps_the_models_ray_base():
     import torch
     from switch_nerf_amd import parallel, rendering
     from switch_nerf_amd.model import SwitchNeRF
+    from switch_nerf_amd.noise import DeviceNoise
 
     class Stub:
         dev = torch.device("cpu")
-        _noise, _noise_step, _ray_base_pending = None, None, 0
+
+        def __init__(self):
+            self.noise = DeviceNoise()
         set_device_noise, set_ray_base = SwitchNeRF.set_device_noise, SwitchNeRF.set_ray_base
         device_noise, noise_state_dict = SwitchNeRF.device_noise, SwitchNeRF.noise_state_dict
 
@@ -99,10 +102,10 @@ def test_render_rays_switch_keeps_the_models_ray_base():
     assert rendering._device_noise(m, None, hp) and m.noise_state_dict()["ray_base"] == 768
     parallel.shard_rays(1024, 1, 4, model=m)                                   # after it
     assert rendering._device_noise(m, None, hp) and m.noise_state_dict()["ray_base"] == 256
-    assert rendering._device_noise(m, None, types.SimpleNamespace(device_noise_seed=9, ray_base=None)) and m._noise["ray_base"] == 256
-    assert rendering._device_noise(m, None, types.SimpleNamespace(device_noise_seed=9, ray_base=5)) and m._noise["ray_base"] == 5
+    assert rendering._device_noise(m, None, types.SimpleNamespace(device_noise_seed=9, ray_base=None)) and m.noise.base == 256
+    assert rendering._device_noise(m, None, types.SimpleNamespace(device_noise_seed=9, ray_base=5)) and m.noise.base == 5
     assert rendering._device_noise(m, None, types.SimpleNamespace()) is True   # on, nothing in hparams: stays as it is
-    assert m._noise["ray_base"] == 5
+    assert m.noise.base == 5
     with pytest.raises(NotImplementedError, match="device_noise_seed"):
         rendering._device_noise(m, object(), hp)
     assert rendering._device_noise(Stub(), None, types.SimpleNamespace()) is False

@@ -175,6 +175,22 @@ def test_graphed_step_equals_eager_with_noise_on():
     assert ma.noise_state_dict()["step"] == mb.noise_state_dict()["step"] == 3
 
 
+def test_reseed_behind_a_capture_fills_the_captured_counter():
+    """set_device_noise after a GraphedTrainStep was captured (same seed and ray_base, step 5) must FILL the counter tensor the graph
+    holds by address, never replace it: the replay then equals an eager step of a model seeded at step 5 bit for bit (rgb, loss, the
+    flat gradient), and both counters read 6."""
+    from switch_nerf_amd.graph import GraphedTrainStep
+    rays, img, rgbs = _batches(1)[0]
+    ma, mb = _model(4321), _model(None)
+    step = GraphedTrainStep(ma, rgbs, rays, img, S_SAMPLES, CHUNK, perturb=1.0, noise_std=STD)
+    for m in (ma, mb):
+        m.set_device_noise(4321, step=5, ray_base=0)
+    ra = step(rgbs, rays, img, optimizer_step=False)
+    rb = mb.train_step(rgbs, rays, img, S_SAMPLES, CHUNK, perturb=1.0, sigma_noise_std=STD, optimizer_step=False)
+    assert torch.equal(ra["rgb"], rb["rgb"]) and torch.equal(ra["loss"], rb["loss"]) and torch.equal(ma.grad, mb.grad)
+    assert ma.noise_state_dict()["step"] == mb.noise_state_dict()["step"] == 6
+
+
 def test_batch_split_invariance():
     """forward_rays on 2N rays draws, for ray i, what the two halves run with ray_base 0 and N draw (z and the sigma noise; rgb is not
     compared: routing is per chunk)."""

@@ -61,7 +61,7 @@ def test_what_sh_training_still_refuses(monkeypatch):
     with pytest.raises(NotImplementedError, match="fp16"):
         MegaNeRF(_subs(sh, torch.float16), CEN, 1.0, False, False, **kw)
     subs = _subs(sh)
-    subs[1]._noise = dict(seed=3, ray_base=0)
+    subs[1].set_device_noise(3)
     with pytest.raises(NotImplementedError, match="device noise"):
         MegaNeRF(subs, CEN, 1.0, False, False, **kw)
     subs = _subs(sh)

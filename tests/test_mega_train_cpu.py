@@ -82,7 +82,7 @@ def test_what_training_refuses(monkeypatch):
     with pytest.raises(NotImplementedError, match="fp16"):
         MegaNeRF(_subs(dtype=torch.float16), CEN, 1.0, False, False, joint_training=True)
     subs = _subs()
-    subs[1]._noise = dict(seed=3, ray_base=0)          # (what set_device_noise leaves; the call itself needs the device)
+    subs[1].set_device_noise(3)
     with pytest.raises(NotImplementedError, match="device noise"):
         MegaNeRF(subs, CEN, 1.0, False, False, joint_training=True)
     subs = _subs()
