@@ -885,10 +885,29 @@ int swn_cells_assign(const float* x, int stride, const float* centroids, int n_c
 int swn_cells_pack_workspace_bytes(int n_points, int n_cells, size_t* bytes);
 int swn_cells_pack(const float* weights, const int32_t* counts, int n_points, int n_cells, int32_t* begin, int32_t* rows,
                    long rows_capacity, int32_t* slot, void* workspace, size_t workspace_bytes, void* stream);
+/* swn_cells_pack_padded: the PADDED row space of a membership - cell i owns the fixed rows [i * capacity, (i + 1) * capacity) whatever
+ *   the batch, so a training step through the cells has static shapes (MegaNeRF cell_capacity; graph capture).  begin [n_cells + 1]:
+ *   begin[i] = i * capacity.  rows [n_cells * capacity]: the member point indices of cell i, ascending, in the first
+ *   min(counts[i], capacity) entries of its range, -1 (a padding row) in the rest; every entry is written exactly once and nothing at
+ *   or past rows[n_cells * capacity].  slot [n_points, n_cells]: the row of point p inside cell i; -1 for a non-member and for a member
+ *   that did not fit (rank >= capacity).  overflow [1]: the memberships dropped, sum over the cells of max(counts[i] - capacity, 0);
+ *   counts (swn_cells_assign's, the TRUE members, also above capacity) is read only.  Stable like swn_cells_pack: ballots and integer
+ *   prefixes, no atomics; two runs give the same bits.  begin / rows / slot are valid inputs of swn_cells_blend and
+ *   swn_cells_blend_bwd with total = n_cells * capacity: the blend skips a slot of -1 (a point none of whose members fit gets
+ *   zeros; every other point's value is bit-equal to the compact layout's), its adjoint writes exactly +0 into a padding row.
+ *   workspace: swn_cells_pack_workspace_bytes().  Errors: n_cells outside 1..64, capacity < 1, n_cells * capacity past 2^31 - 1.      */
+int swn_cells_pack_padded(const float* weights, const int32_t* counts, int n_points, int n_cells, int capacity, int32_t* begin,
+                          int32_t* rows, int32_t* slot, int32_t* overflow, void* workspace, size_t workspace_bytes, void* stream);
 /* swn_cells_gather: x_out [total, stride - col0] = columns [col0, stride) of x[rows[r]] (col0 = 3 drops the real position of an
  *   xyz_real model, mega_nerf.py:36); noise_out [total] = sigma_noise[rows[r]] when sigma_noise [n_points] is given (both or neither). */
 int swn_cells_gather(const float* x, int stride, int col0, const int32_t* rows, long total, int n_points, const float* sigma_noise,
                      float* x_out, float* noise_out, void* stream);
+/* swn_cells_gather_padded: swn_cells_gather over the padded row space of swn_cells_pack_padded, for rows of stride - col0 == 7 columns
+ *   (position, direction, image index).  x_out [n_cells * capacity, 7], noise_out [n_cells * capacity].  A real row (rows[r] >= 0)
+ *   copies x[rows[r]] and sigma_noise[rows[r]] bit for bit; a padding row reads nothing of x and becomes a benign input of its cell:
+ *   position = centroids[r / capacity], direction (0, 0, 1), image index 0, sigma noise 0.                                           */
+int swn_cells_gather_padded(const float* x, int stride, int col0, const int32_t* rows, const float* centroids, int n_cells, int capacity,
+                            int n_points, const float* sigma_noise, float* x_out, float* noise_out, void* stream);
 /* swn_cells_blend: out[p][:] = sum over the member cells i, ascending, of weights[p][i] * sub_out[begin[i] + slot[p][i]][:], channels 1
  *   or 4; hard != 0 (margin == 1): the plain copy of the one member's row (:47).  One thread per point: no atomics, no zero fill,
  *   the sum order is the reference's loop order.                                                                                   */

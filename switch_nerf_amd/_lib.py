@@ -160,7 +160,9 @@ SIGNATURES = {
     "swn_cells_assign": [vp, i32, vp, i32, i32, f32, i32, vp, vp, vp],
     "swn_cells_pack_workspace_bytes": [i32, i32, C.POINTER(sz)],
     "swn_cells_pack": [vp, vp, i32, i32, vp, vp, i64, vp, vp, sz, vp],
+    "swn_cells_pack_padded": [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp],
     "swn_cells_gather": [vp, i32, i32, vp, i64, i32, vp, vp, vp, vp],
+    "swn_cells_gather_padded": [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "swn_cells_blend": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp],
     "swn_cells_blend_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp],
     "swn_cells_blend_sh": [vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp, vp, vp],

@@ -5,6 +5,8 @@
 //   cells_scan_kernel      exclusive prefix of those over the blocks, begin[K + 1]             > swn_cells_pack
 //   cells_place_kernel     slot[P, K] (row of a point inside a cell, or -1) and rows[total]   /
 //   cells_gather_kernel    every cell's input rows (and sigma-noise rows) from rows[]
+//   cells_pad_kernel, cells_gather_padded_kernel      the PADDED row space (swn_cells_pack_padded, swn_cells_gather_padded): every
+//                          cell owns a fixed range of `capacity` rows, so nothing about a step's shapes depends on the batch
 //   cells_blend_kernel     out[p] = sum over the member cells, ascending, of weights * sub-model output (a per-point gather: no atomics)
 //   cells_blend_bwd_kernel d_sub[r] = weights * d_out[rows[r]]: the blend's adjoint, one packed row per thread (training, mega.py)
 // Plain C++, fp32, fma contraction off: the distance is the direct sqrt(sum (x_j - c_j)^2) in the order j = dim_start .. 2 and the
@@ -123,9 +125,9 @@ __global__ __launch_bounds__(CELLS_BLOCK) void cells_count_kernel(const float* _
 
 // ONE workgroup: block_counts[n_blocks][K] -> in place, the members of the cell in the blocks before (exclusive prefix over the blocks).
 // Thread = (run c of consecutive blocks, cell i): run sums, the runs before through LDS, then the running prefix inside the run.
-// begin[0 .. K] = exclusive scan of counts.
+// begin[0 .. K] = exclusive scan of counts; capacity > 0 (the padded row space): begin[k] = k * capacity whatever the counts.
 __global__ __launch_bounds__(CELLS_SCAN_THREADS) void cells_scan_kernel(int32_t* __restrict__ block_counts, const int32_t* __restrict__ counts,
-                                                                       int n_blocks, int K, int32_t* __restrict__ begin) {
+                                                                       int n_blocks, int K, int capacity, int32_t* __restrict__ begin) {
   __shared__ int part[CELLS_SCAN_THREADS];
   const int t = threadIdx.x;
   int n_runs = CELLS_SCAN_THREADS / K;
@@ -152,15 +154,16 @@ __global__ __launch_bounds__(CELLS_SCAN_THREADS) void cells_scan_kernel(int32_t*
     int run = 0;
     for (int k = 0; k < K; ++k) {
       begin[k] = run;
-      run += counts[k];
+      run += capacity > 0 ? capacity : counts[k];
     }
     begin[K] = run;
   }
 }
 
+// capacity > 0 (the padded row space): a member whose rank inside its cell is capacity or more does not fit - no row, slot -1.
 __global__ __launch_bounds__(CELLS_BLOCK) void cells_place_kernel(const float* __restrict__ weights, const int32_t* __restrict__ block_base,
                                                                  const int32_t* __restrict__ begin, int K, int P, long rows_capacity,
-                                                                 int32_t* __restrict__ rows, int32_t* __restrict__ slot) {
+                                                                 int capacity, int32_t* __restrict__ rows, int32_t* __restrict__ slot) {
   __shared__ int wave_cnt[CELLS_WAVES][CELLS_MAX];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long p = (long)blockIdx.x * CELLS_BLOCK + threadIdx.x;
@@ -173,8 +176,12 @@ __global__ __launch_bounds__(CELLS_BLOCK) void cells_place_kernel(const float* _
     if (member) {
       s = block_base[(long)blockIdx.x * K + i] + __popcll(m & ((1ull << lane) - 1ull));
       for (int k = 0; k < w; ++k) s += wave_cnt[k][i];
-      const long r = (long)begin[i] + s;
-      if (r >= 0 && r < rows_capacity) rows[r] = (int32_t)p;
+      if (capacity > 0 && s >= capacity) {
+        s = -1;
+      } else {
+        const long r = (long)begin[i] + s;
+        if (r >= 0 && r < rows_capacity) rows[r] = (int32_t)p;
+      }
     }
     slot[p * K + i] = s;
   }
@@ -195,6 +202,44 @@ __global__ __launch_bounds__(256) void cells_gather_kernel(const float* __restri
   if (c == 0 && noise) noise_out[r] = ok ? noise[p] : 0.f;
 }
 
+// The padded row space behind cells_place_kernel: row j of cell i's range is a padding row (-1) from j = counts[i] on - the place
+// kernel wrote the min(counts[i], capacity) rows in front, so every one of the n_cells * capacity rows is written exactly once.
+// overflow = the memberships that did not fit, summed over the cells in ascending order by one thread (no atomics).
+__global__ __launch_bounds__(256) void cells_pad_kernel(const int32_t* __restrict__ counts, int K, int capacity, int32_t* __restrict__ rows,
+                                                       int32_t* __restrict__ overflow) {
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r == 0) {
+    int over = 0;
+    for (int i = 0; i < K; ++i) over += counts[i] > capacity ? counts[i] - capacity : 0;
+    *overflow = over;
+  }
+  if (r >= (long)K * capacity) return;
+  const int i = (int)(r / capacity);
+  if (r - (long)i * capacity >= counts[i]) rows[r] = -1;
+}
+
+// cells_gather_kernel over the padded row space, rows of (position, direction, image index): a padding row (rows[r] < 0) reads
+// nothing of x and becomes a point the cell's network can run on - its own centroid seen along (0, 0, 1) in image 0, sigma noise 0.
+__global__ __launch_bounds__(256) void cells_gather_padded_kernel(const float* __restrict__ x, int stride, int col0,
+                                                                 const int32_t* __restrict__ rows, const float* __restrict__ centroids,
+                                                                 int K, int capacity, int P, const float* __restrict__ noise,
+                                                                 float* __restrict__ x_out, float* __restrict__ noise_out) {
+  constexpr int width = 7;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)K * capacity * width) return;
+  const long r = e / width;
+  const int c = (int)(e - r * width);
+  const int p = rows[r];
+  const bool real = p >= 0 && p < P;
+  float v;
+  if (real)
+    v = x[(long)p * stride + col0 + c];
+  else
+    v = c < 3 ? centroids[(r / capacity) * 3 + c] : (c == 5 ? 1.f : 0.f);
+  x_out[e] = v;
+  if (c == 0 && noise) noise_out[r] = real ? noise[p] : 0.f;
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void cells_blend_kernel(const float* __restrict__ weights, const int32_t* __restrict__ slot,
                                                          const int32_t* __restrict__ begin, const float* __restrict__ sub_out, long total,
@@ -209,7 +254,7 @@ __global__ __launch_bounds__(256) void cells_blend_kernel(const float* __restric
     const int s = slot[p * K + i];
     if (s < 0) continue;
     const long r = (long)begin[i] + s;
-    if (r >= total) continue;                 // (never for a slot list of swn_cells_pack)
+    if (r >= total) continue;                 // (never for a slot list of swn_cells_pack / _pack_padded)
     float v[C];
     if constexpr (C == 4) {
       const float4 q = *reinterpret_cast<const float4*>(sub_out + r * 4);
@@ -252,7 +297,7 @@ __global__ __launch_bounds__(256) void cells_blend_bwd_kernel(const float* __res
   const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= total) return;
   const int p = rows[r];
-  const bool ok = p >= 0 && p < P;            // (never false for a row list of swn_cells_pack)
+  const bool ok = p >= 0 && p < P;            // (false for the padding rows of swn_cells_pack_padded only: they get +0)
   float wt = 1.f;
   if (!hard && ok) {
     int lo = 0, hi = K - 1;                   // the first cell whose end lies past r
@@ -312,9 +357,31 @@ extern "C" int swn_cells_pack(const float* weights, const int32_t* counts, int n
   int32_t* block_counts = (int32_t*)workspace;
   hipLaunchKernelGGL(cells_count_kernel, dim3(n_blocks), dim3(CELLS_BLOCK), 0, as_stream(stream), weights, n_cells, n_points, block_counts);
   hipLaunchKernelGGL(cells_scan_kernel, dim3(1), dim3(CELLS_SCAN_THREADS), 0, as_stream(stream), block_counts, counts, n_blocks, n_cells,
-                     begin);
+                     0, begin);
   hipLaunchKernelGGL(cells_place_kernel, dim3(n_blocks), dim3(CELLS_BLOCK), 0, as_stream(stream), weights, block_counts, begin, n_cells,
-                     n_points, rows_capacity, rows, slot);
+                     n_points, rows_capacity, 0, rows, slot);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cells_pack_padded(const float* weights, const int32_t* counts, int n_points, int n_cells, int capacity, int32_t* begin,
+                                     int32_t* rows, int32_t* slot, int32_t* overflow, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  SWN_CHECK(n_cells >= 1 && n_cells <= CELLS_MAX, "swn_cells_pack_padded: n_cells %d outside [1, %d]", n_cells, CELLS_MAX);
+  SWN_CHECK(weights && counts && begin && rows && slot && overflow && workspace, "swn_cells_pack_padded: null pointer");
+  SWN_CHECK(n_points >= 1 && capacity >= 1, "swn_cells_pack_padded: bad sizes (n_points %d, capacity %d)", n_points, capacity);
+  const long total = (long)n_cells * capacity;
+  SWN_CHECK(total <= 2147483647l, "swn_cells_pack_padded: %d cells of %d rows exceed the 32-bit row space", n_cells, capacity);
+  const int n_blocks = cdiv(n_points, CELLS_BLOCK);
+  SWN_CHECK(workspace_bytes >= (size_t)n_blocks * n_cells * sizeof(int32_t), "swn_cells_pack_padded: workspace of %zu bytes, %zu needed",
+            workspace_bytes, (size_t)n_blocks * n_cells * sizeof(int32_t));
+  int32_t* block_counts = (int32_t*)workspace;
+  hipLaunchKernelGGL(cells_count_kernel, dim3(n_blocks), dim3(CELLS_BLOCK), 0, as_stream(stream), weights, n_cells, n_points, block_counts);
+  hipLaunchKernelGGL(cells_scan_kernel, dim3(1), dim3(CELLS_SCAN_THREADS), 0, as_stream(stream), block_counts, counts, n_blocks, n_cells,
+                     capacity, begin);
+  hipLaunchKernelGGL(cells_place_kernel, dim3(n_blocks), dim3(CELLS_BLOCK), 0, as_stream(stream), weights, block_counts, begin, n_cells,
+                     n_points, total, capacity, rows, slot);
+  hipLaunchKernelGGL(cells_pad_kernel, dim3(cdiv(total, 256)), dim3(256), 0, as_stream(stream), counts, n_cells, capacity, rows, overflow);
   SWN_LAUNCH_CHECK();
   return 0;
 }
@@ -330,6 +397,23 @@ extern "C" int swn_cells_gather(const float* x, int stride, int col0, const int3
   SWN_CHECK(n <= 2147483647l * 256, "swn_cells_gather: %ld elements exceed the grid", n);      // (cdiv returns an int)
   hipLaunchKernelGGL(cells_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, stride, col0, rows, total, n_points,
                      sigma_noise, x_out, noise_out);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cells_gather_padded(const float* x, int stride, int col0, const int32_t* rows, const float* centroids, int n_cells,
+                                       int capacity, int n_points, const float* sigma_noise, float* x_out, float* noise_out, void* stream) {
+  SWN_CHECK(n_cells >= 1 && n_cells <= CELLS_MAX, "swn_cells_gather_padded: n_cells %d outside [1, %d]", n_cells, CELLS_MAX);
+  SWN_CHECK(x && rows && centroids && x_out, "swn_cells_gather_padded: null pointer");
+  SWN_CHECK((sigma_noise == nullptr) == (noise_out == nullptr), "swn_cells_gather_padded: sigma_noise and noise_out come together");
+  SWN_CHECK(n_points >= 1 && capacity >= 1 && col0 >= 0, "swn_cells_gather_padded: bad sizes (n_points %d, capacity %d, col0 %d)", n_points,
+            capacity, col0);
+  SWN_CHECK(stride - col0 == 7, "swn_cells_gather_padded: columns [%d, %d) are not the 7 of (position, direction, image index)", col0, stride);
+  const long n = (long)n_cells * capacity * 7;
+  SWN_CHECK((long)n_cells * capacity <= 2147483647l, "swn_cells_gather_padded: %d cells of %d rows exceed the 32-bit row space", n_cells,
+            capacity);
+  hipLaunchKernelGGL(cells_gather_padded_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, stride, col0, rows, centroids,
+                     n_cells, capacity, n_points, sigma_noise, x_out, noise_out);
   SWN_LAUNCH_CHECK();
   return 0;
 }

@@ -377,3 +377,73 @@ class GraphedBackgroundStep:
         ctx = self.res["ctx"]
         ctx["Nb"] = ctx["n_out"] = None                    # the counts of THIS replay are read in apply_step
         return scene.apply_step(self.res, optimizer_step, grad_allreduce, refresh=self.copies.replay, advance=False)
+
+
+class GraphedMegaStep:
+    """step = GraphedMegaStep(model, rgbs, rays, image_indices, n_samples, cell_capacity, ...); res = step(rgbs, rays, image_indices)
+
+    The joint training step of a mega.MegaNeRF in its padded form (cell_capacity = C rows per cell, or (C_coarse, C_fine)) captured once
+    and replayed - built like GraphedBackgroundStep: static input buffers, warm-up on a side stream, ONE capture of every cell's
+    grad.zero_() + the padded grad_step (coarse only, or coarse + fine with fine_samples > 0), and a second small graph for every cell's
+    refresh_compute_copies.  The tail (MegaNeRF.apply_step(res=...): the 8-byte readback of the overflow counts, one Adam step per cell
+    through optim.apply_tail, the copies graph) runs outside the graph.  Same result dict as MegaNeRF.train_step (tensors live in
+    static graph memory: read them before the next call).
+
+    One capture serves every batch of its shape, however its points fall over the cells - up to C per cell: a batch with more in a cell
+    raises RuntimeError from the tail with no parameter touched, and the next replay is unaffected.  The jitter (perturb > 0) and the
+    sigma noise of both passes (noise_std > 0) are drawn inside the graph from the framework's device generator.
+    Not built: spherical-harmonics cells, seeded device noise for cells, data parallelism (no gradient all-reduce), the xyz_real
+    background half, a grouped launch over the cells."""
+
+    def __init__(self, model, rgbs, rays, image_indices, n_samples: int, cell_capacity, perturb: float = 1.0, noise_std: float = 1.0,
+                 fine_samples: int = 0, warmup: int = 2):
+        model._need_joint("GraphedMegaStep")
+        if cell_capacity is None:
+            raise ValueError("GraphedMegaStep: cell_capacity is required - the compact form reads the cells' row counts on the host and "
+                             "cannot be captured")
+        self.cell_capacity = model._capacity(cell_capacity)
+        self.model = model
+        dev = model.dev
+        N, S, F = rays.shape[0], int(n_samples), int(fine_samples)
+        self.rgbs, self.rays, self.idx = rgbs.clone().contiguous(), rays.clone().contiguous(), image_indices.clone().contiguous()
+
+        def run():
+            pr = torch.rand(N, S, device=dev) if perturb > 0 else None
+            noise = torch.randn(N * S, device=dev) * noise_std if noise_std > 0 else None
+            noise_f = torch.randn(N * F, device=dev) * noise_std if noise_std > 0 and F > 0 else None
+            return model.grad_step(self.rgbs, self.rays, self.idx, S, perturb, pr, noise, F, None, noise_f, self.cell_capacity)
+
+        profiles = [m.profile for m in model.sub_modules]
+        for m in model.sub_modules:
+            m.profile = False
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                      # warm-up on a side stream: allocates every cached buffer / workspace
+            for _ in range(max(1, warmup)):
+                run()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        # a cell's cached buffers grow with the largest row count seen (a later eager compact step with more rows in a cell replaces
+        # them): the capture keeps the ones it baked in alive
+        self._held = [list(m._bufs.values()) + [getattr(m, "_ones", None)] for m in model.sub_modules]
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=side):
+            self.res = run()
+        self.captures = 1                                  # captures of the step so far: replays never add one
+        self.copies = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.copies, stream=side):
+            for m in model.sub_modules:
+                m.refresh_compute_copies()
+        for m, p in zip(model.sub_modules, profiles):
+            m.profile = p
+
+    def __call__(self, rgbs=None, rays=None, image_indices=None, optimizer_step=True):
+        if rgbs is not None:
+            self.rgbs.copy_(rgbs)
+        if rays is not None:
+            self.rays.copy_(rays)
+        if image_indices is not None:
+            self.idx.copy_(image_indices)
+        self.graph.replay()
+        self.model.apply_step(None, optimizer_step, self.res, refresh=self.copies.replay)
+        return self.res

@@ -48,9 +48,28 @@ blend (rendering.py:344-347), so the basis is no part of a cell:
 The [total, 3 B + 1] gradient is never written.  The points carry no direction columns ([P, 3 + 1]); one direction serves the
 rows_per_group samples of a ray.  At degree 0 a cell's row holds sigmoid(lin) and the blend's evaluation puts a second sigmoid on it,
 as in inference.
+
+Two forms of the cells' rows in training.  The COMPACT form (default, cell_capacity=None) is the one above: counts.tolist() sizes the
+ragged calls, empty cells are skipped.  The PADDED form (forward_points / grad_step / train_step with cell_capacity = C, or (C_coarse,
+C_fine) for the two passes of the hierarchical step) runs EVERY cell on exactly C rows whatever the batch:
+
+    begin, rows, slot, overflow = ops.cells_pack_padded(weights, counts, C)     cell i owns rows [i C, (i + 1) C); -1 = a padding row
+    xin, noise = ops.cells_gather_padded(x, rows, centroids, C, 0, sigma_noise) a padding row: the cell's centroid, direction (0, 0, 1)
+    c_i = sub_modules[i].forward_rays(rows [i C, (i + 1) C) ...)                every cell, a cell without a member included
+    out = ops.cells_blend(weights, slot, begin, sub_out, hard)                  the same kernel on the fixed begin[]
+    d_sub = ops.cells_blend_bwd(weights, rows, begin, d_out, K C, hard)         exactly +0 on the padding rows
+
+A padding row's gradient is +0, so it adds exact zeros to every sum of its cell's backward.  Nothing is read on the host in forward_points,
+backward_points or grad_step: ctx["counts"] is the device tensor of the true members, ctx["overflow"] the device count of memberships
+that did not fit, and apply_step(res=...) reads res["cell_overflow"] once behind the step's last launch - a batch with more than C
+members in a cell raises RuntimeError there, before any parameter, moment or step count is touched.  What padding costs: K C rows of
+network work against the batch's P (K times the largest cell's share at the tightest C).  What it buys: static shapes, so the step is
+captured into a hipGraph (graph.GraphedMegaStep).  Not built for the padded form: spherical-harmonics cells (sh_training), seeded
+device noise, data parallelism, the xyz_real background half, a grouped launch over the cells.
+
 Not built for training (each raises NotImplementedError): the xyz_real background half, fp16 cells (one loss scale over K models), seeded
-device noise, graph capture (counts.tolist() sizes the ragged calls), expert / data parallelism, and rendering.render_rays on a model in
-training mode (the autograd bridge for a MegaNeRF is a later change).
+device noise, graph capture of the COMPACT form (counts.tolist() sizes the ragged calls), expert / data parallelism, and
+rendering.render_rays on a model in training mode (the autograd bridge for a MegaNeRF is a later change).
 """
 from __future__ import annotations
 
@@ -331,9 +350,25 @@ class MegaNeRF:
         return dict(weights=weights, rows=rows, begin=begin, slot=slot, counts=n, total=total, hard=self.boundary_margin == 1,
                     P=x.shape[0]), xin, nin
 
-    def _cells(self, counts):
+    def _capacity(self, cell_capacity):
+        """cell_capacity as forward_points / grad_step / train_step take it -> None (the compact form) or (C_coarse, C_fine)."""
+        if cell_capacity is None:
+            return None
+        pair = tuple(cell_capacity) if isinstance(cell_capacity, (tuple, list)) else (cell_capacity, cell_capacity)
+        if len(pair) != 2 or any(isinstance(c, bool) or not isinstance(c, int) or c < 1 for c in pair):
+            raise ValueError(f"cell_capacity {cell_capacity!r}: expected None, an int >= 1 (rows per cell) or a pair (coarse, fine) of them")
+        if self.sh_deg is not None:
+            raise NotImplementedError("cell_capacity (the padded form of the cells' rows) is not built for spherical-harmonics cells "
+                                      "(sh_training): train them in the compact form")
+        return pair
+
+    def _cells(self, counts, capacity=None):
         """(cell index, sub-model, its slice of the packed rows) of every non-empty cell (empty cells are skipped, mega_nerf.py:38; in
-        training their gradient stays zero, :51-59)."""
+        training their gradient stays zero, :51-59).  capacity (the padded form): every cell, on its fixed range of that many rows."""
+        if capacity is not None:
+            for i, child in enumerate(self.sub_modules):
+                yield i, child, slice(i * capacity, (i + 1) * capacity)
+            return
         b = 0
         for i, (child, n) in enumerate(zip(self.sub_modules, counts)):
             if n > 0:
@@ -341,16 +376,32 @@ class MegaNeRF:
             b += n
 
     # ------------------------------------------------------------------------------------------ training through the cells
-    def forward_points(self, x, sigma_noise=None, tag: str = "c", dirs=None, rows_per_group: int = 1):
+    def _gather_cells_padded(self, x, sigma_noise, C):
+        """_gather_cells in the padded form (module doc): no host read, every cell on C rows.  routing["counts"] is the device tensor of
+        the true members, routing["overflow"] [1] the device count of memberships that did not fit, routing["C"] the capacity."""
+        x = x.to(torch.float32).contiguous()
+        noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
+        weights, counts = ops.cells_assign(x, self.centroids, self.cluster_dim_start, self.boundary_margin)
+        begin, rows, slot, overflow = ops.cells_pack_padded(weights, counts, C)
+        xin, nin = ops.cells_gather_padded(x, rows, self.centroids, C, 0, noise)
+        return dict(weights=weights, rows=rows, begin=begin, slot=slot, counts=counts, total=len(self.sub_modules) * C,
+                    hard=self.boundary_margin == 1, P=x.shape[0], C=C, overflow=overflow), xin, nin
+
+    def forward_points(self, x, sigma_noise=None, tag: str = "c", dirs=None, rows_per_group: int = 1, cell_capacity=None):
         """The training form of __call__: x [P, 3 + 3 + 1] -> ctx with ctx["out"] [P, 4] and what backward_points needs.  Every non-empty
         cell runs a SAVING forward on its packed rows (DenseNeRF.forward_rays on one-sample rays, as DenseNeRF.__call__ does), so a cell
         holds ONE live context per tag: a second forward_points under the same tag overwrites the first one's saved activations (the
         hierarchical step runs its fine pass under tag "f").
         Cells with sh_deg (sh_training): x [P, 3 + 1] (no direction columns) and dirs [P / rows_per_group, 3], point p seen along
         dirs[p // rows_per_group] (not normalised), the training form of call_rgb: ctx["out"] = (sigmoid(eval_sh(blended coefficients,
-        direction)), blended sigma)."""
+        direction)), blended sigma).
+        cell_capacity = C, or (C_coarse, C_fine) of which tag "f" takes the second: the padded form (module doc) - every cell, one
+        without a member included, runs on exactly C rows; nothing is read on the host, so the pass can be captured into a hipGraph.
+        ctx["counts"] is then the device int32 [K] of true members and ctx["overflow"] the device count of memberships dropped because
+        a cell had more than C (apply_step(res=...) refuses such a step).  Not built for cells with sh_deg."""
         self._need_joint("forward_points")
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        cap = self._capacity(cell_capacity)
+        if cap is None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError("MegaNeRF: graph capture is not built - counts.tolist() sizes the ragged per-cell calls on the host")
         sh = self.sh_deg is not None
         width = 4 if sh else 7
@@ -367,7 +418,8 @@ class MegaNeRF:
             dirs = dirs.to(torch.float32).contiguous()
         elif dirs is not None:
             raise ValueError("forward_points: dirs belong to cells with sh_deg; these points carry their direction columns")
-        r, xin, nin = self._gather_cells(x, sigma_noise)
+        C = None if cap is None else cap[1 if tag == "f" else 0]
+        r, xin, nin = self._gather_cells(x, sigma_noise) if C is None else self._gather_cells_padded(x, sigma_noise, C)
         total, cells = r["total"], [None] * len(self.sub_modules)
         if sh:
             # each cell's heads write its slice of the packed rows (degree 0: the reference NeRF's own sigmoid on its three outputs, as
@@ -380,7 +432,7 @@ class MegaNeRF:
         rays = torch.cat([xin[:, :6], torch.zeros(total, 2, device=self.dev)], 1)      # o = xyz, near = far = 0 -> the sample IS the point
         img = xin[:, 6].long()
         sub_out = torch.empty(total, 4, dtype=torch.float32, device=self.dev)
-        for i, child, sl in self._cells(r["counts"]):
+        for i, child, sl in self._cells(r["counts"], C):
             c = cells[i] = child.forward_rays(rays[sl].contiguous(), img[sl].contiguous(), 1, sl.stop - sl.start, 0.0, None,
                                               None if nin is None else nin[sl], training=True, tag=tag, composite=False)
             sub_out[sl] = c["raw"]
@@ -399,19 +451,22 @@ class MegaNeRF:
                                                self.sh_deg, ctx["total"], ctx["hard"], ctx["sub_out"] if self.sh_deg == 0 else None)
         else:
             d_sub, dp = ops.cells_blend_bwd(ctx["weights"], ctx["rows"], ctx["begin"], d_out, ctx["total"], ctx["hard"]), None
-        for i, child, sl in self._cells(ctx["counts"]):
+        for i, child, sl in self._cells(ctx["counts"], ctx.get("C")):      # (the form follows the context's)
             c = ctx["cells"][i]
             if dp is not None:
                 c["coef_dirs"] = dp[sl]
             child.backward_net(c, d_sub[sl], None)
 
     def grad_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, fine_samples=0, fine_u=None,
-                  sigma_noise_fine=None):
+                  sigma_noise_fine=None, cell_capacity=None):
         """Forward + loss + backward of one training step (SwitchNeRF.grad_step's contract): zeroes every cell's gradient, fills it, and
         returns the metrics.  The whole batch goes through the cells in one call: a MegaNeRF's output for a point does not depend on the
         other points of its chunk, so there is no model_chunk_size loop.  fine_samples > 0: the sequence of SwitchNeRF.forward_hier
-        (coarse pass with weights, sample_pdf from the detached weights, fine pass under tag "f", sort-merge, compositing of the union)."""
+        (coarse pass with weights, sample_pdf from the detached weights, fine pass under tag "f", sort-merge, compositing of the union).
+        cell_capacity: the padded form (forward_points) - no host read in the whole step; the result then holds "cell_overflow", the
+        device int32 [2] of memberships dropped in the coarse and the fine pass (0 for a pass that did not run), for apply_step(res=...)."""
         self._need_joint("grad_step")
+        cap = self._capacity(cell_capacity)
         o = ops
         N, S, F = rays.shape[0], int(n_samples), int(fine_samples)
         rays = rays.to(torch.float32).contiguous()
@@ -423,7 +478,7 @@ class MegaNeRF:
         z = o.sample_z(rays, lin(S), perturb_rand if perturb != 0 else None, perturb, S)
         sh = self.sh_deg is not None          # (sh_deg: no direction columns, one direction per ray: rendering.py:316-330)
         dirs = rays[:, 3:6].contiguous() if sh else None
-        c = self.forward_points(_points(rays, z, image_indices, not sh), sigma_noise, "c", dirs, S)
+        c = self.forward_points(_points(rays, z, image_indices, not sh), sigma_noise, "c", dirs, S, cap)
         raw = c["out"]
         if F == 0:
             cf = None
@@ -434,7 +489,7 @@ class MegaNeRF:
             if fine_u is None:
                 fine_u = hier.default_fine_u(lin, N, F, perturb, self.dev)
             z_fine = o.sample_pdf(z, w, fine_u, F)
-            cf = self.forward_points(_points(rays, z_fine, image_indices, not sh), sigma_noise_fine, "f", dirs, F)
+            cf = self.forward_points(_points(rays, z_fine, image_indices, not sh), sigma_noise_fine, "f", dirs, F, cap)
             zm, order, raw_m = o.merge_samples(z_fine, z, cf["out"], raw)
             out = dict(raw=raw_m, z=zm, order=order, z_fine=z_fine)
             out["rgb"], out["depth"], out["depth_variance"], _ = o.composite_fwd(raw_m, zm)
@@ -451,6 +506,8 @@ class MegaNeRF:
                    rgb=out["rgb"], depth=out["depth"])
         if cf is not None:
             res["ctx_fine"] = cf
+        if cap is not None:
+            res["cell_overflow"] = torch.cat([c["overflow"], cf["overflow"] if cf is not None else torch.zeros_like(c["overflow"])])
         return res
 
     def set_accumulation(self, steps: int):
@@ -469,10 +526,14 @@ class MegaNeRF:
         if on:
             raise NotImplementedError(self._GUARD_JOINT)
 
-    def apply_step(self, grad_allreduce=None, optimizer_step=True):
+    def apply_step(self, grad_allreduce=None, optimizer_step=True, res=None, refresh=None):
         """One Adam step on every cell with the model's one step count and learning rate.  A cell no point reached has a zero gradient,
         not a missing one: its step count advances, its moments decay and it moves by momentum, like the reference's joint_training cells
-        under one torch.optim.Adam."""
+        under one torch.optim.Adam.
+        res: the result of the grad_step being applied.  A padded step's (cell_capacity) carries "cell_overflow", read here ONCE - the
+        step's only device-to-host read, behind its last launch: a batch that had more members in a cell than the capacity was computed
+        without the surplus rows and raises RuntimeError before any parameter, moment or step count is touched.
+        refresh: a replacement for every cell's refresh_compute_copies (the replay of their captured graph), run once."""
         self._need_joint("apply_step")
         if any(getattr(m, "accum_steps", 1) > 1 for m in self.sub_modules):
             raise NotImplementedError("MegaNeRF: gradient accumulation (set_accumulation on a cell model) is not built for joint training")
@@ -480,18 +541,27 @@ class MegaNeRF:
             raise NotImplementedError(self._GUARD_JOINT)
         if grad_allreduce is not None:
             raise NotImplementedError("MegaNeRF: data parallelism (a gradient all-reduce over the cells' buffers) is not built")
+        if res is not None and res.get("cell_overflow") is not None:
+            dropped = res["cell_overflow"].tolist()
+            if any(dropped):
+                passes = [("coarse", res["ctx"])] + ([("fine", res["ctx_fine"])] if "ctx_fine" in res else [])
+                what = "; ".join(f"{name}: cell capacity {c['C']}, members per cell {c['counts'].tolist()}" for name, c in passes)
+                raise RuntimeError(f"MegaNeRF: {sum(dropped)} (point, cell) memberships of this batch did not fit their cell's rows ({what}): "
+                                   "the step was computed without them and is not applied; raise cell_capacity")
         if not optimizer_step:
             return
         for m in self.sub_modules:
             m.step_count, m.lr = self.step_count, self.lr      # (the tail advances each cell's count, like the model's here)
         self.step_count += 1
-        optim.apply_tail(self.sub_modules)
+        optim.apply_tail(self.sub_modules, refresh=refresh)
 
     def train_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, optimizer_step=True,
-                   fine_samples=0, fine_u=None, sigma_noise_fine=None):
-        """grad_step + apply_step; result keys as SwitchNeRF.train_step (loss, photo_loss, psnr, rgb, depth, depth_variance; gate_loss 0)."""
-        res = self.grad_step(rgbs, rays, image_indices, n_samples, perturb, perturb_rand, sigma_noise, fine_samples, fine_u, sigma_noise_fine)
-        self.apply_step(None, optimizer_step)
+                   fine_samples=0, fine_u=None, sigma_noise_fine=None, cell_capacity=None):
+        """grad_step + apply_step; result keys as SwitchNeRF.train_step (loss, photo_loss, psnr, rgb, depth, depth_variance; gate_loss 0).
+        cell_capacity: the padded form (module doc); a batch that overflows a cell raises RuntimeError with no parameter touched."""
+        res = self.grad_step(rgbs, rays, image_indices, n_samples, perturb, perturb_rand, sigma_noise, fine_samples, fine_u, sigma_noise_fine,
+                             cell_capacity)
+        self.apply_step(None, optimizer_step, res)
         return res
 
 

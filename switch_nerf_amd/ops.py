@@ -1081,6 +1081,43 @@ def cells_gather(x, rows, total: int, col0: int = 0, sigma_noise=None):
     return x_out, noise_out
 
 
+def cells_pack_padded(weights, counts, capacity: int):
+    """The PADDED row space of a membership (swn_cells_pack_padded): cell i owns the rows [i C, (i + 1) C), C = capacity, whatever the
+    batch -> begin [K + 1] (i C), rows [K C] (cell i's member points, ascending, in the first min(counts[i], C) entries of its range; -1
+    = a padding row), slot [P, K] (-1 also for a member that did not fit), overflow [1] int32 (the memberships dropped).  begin / rows /
+    slot go to cells_blend / cells_blend_bwd with total = K C."""
+    P, K = weights.shape
+    Cc = int(capacity)
+    assert weights.dtype == torch.float32 and counts.dtype == torch.int32 and counts.numel() == K and Cc >= 1
+    dev = weights.device
+    begin = torch.empty(K + 1, dtype=torch.int32, device=dev)
+    rows = torch.empty(K * Cc, dtype=torch.int32, device=dev)
+    slot = torch.empty(P, K, dtype=torch.int32, device=dev)
+    overflow = torch.empty(1, dtype=torch.int32, device=dev)
+    need = C.c_size_t(0)
+    call("swn_cells_pack_workspace_bytes", P, K, C.byref(need))
+    ws = torch.empty(max(1, need.value // 4), dtype=torch.int32, device=dev)
+    call("swn_cells_pack_padded", _p(weights), _p(counts), P, K, Cc, _p(begin), _p(rows), _p(slot), _p(overflow), _p(ws), need.value,
+         _stream())
+    return begin, rows, slot, overflow
+
+
+def cells_gather_padded(x, rows, centroids, capacity: int, col0: int = 0, sigma_noise=None):
+    """cells_gather over the padded row space (swn_cells_gather_padded), x [P, col0 + 7]: x_out [K C, 7], noise_out [K C] or None.  A
+    padding row (rows[r] < 0) is its cell's centroid seen along (0, 0, 1) in image 0 with sigma noise 0; it reads nothing of x."""
+    P, stride = x.shape
+    K, Cc = centroids.shape[0], int(capacity)
+    assert x.dtype == centroids.dtype == torch.float32 and rows.dtype == torch.int32 and rows.numel() == K * Cc
+    x_out = torch.empty(K * Cc, stride - col0, dtype=torch.float32, device=x.device)
+    noise_out = None
+    if sigma_noise is not None:
+        assert sigma_noise.dtype == torch.float32 and sigma_noise.numel() == P
+        noise_out = torch.empty(K * Cc, dtype=torch.float32, device=x.device)
+    call("swn_cells_gather_padded", _p(x), stride, int(col0), _p(rows), _p(centroids), K, Cc, P, _p(sigma_noise), _p(x_out), _p(noise_out),
+         _stream())
+    return x_out, noise_out
+
+
 def cells_blend(weights, slot, begin, sub_out, hard: bool):
     """out [P, C] = sum over the member cells (ascending) of weights * sub_out[begin[i] + slot] (swn_cells_blend), C = sub_out.shape[1]
     in {1, 4}; hard: the plain copy of the one member's row."""
