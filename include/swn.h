@@ -966,6 +966,25 @@ int swn_heads_coef_bwd(const void* y, const void* h2, int dtype, const float* w_
                        float* d_w_sigma, float* d_b_sigma, float* d_w_color, float* d_b_color, float* group_colsum, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- image metrics of the validation loop (metrics.py; ssim.hip) ---------------------------------------------------------------------
+ * The reference's metrics.py on the device: ssim (:51-121), psnr (:8-10), ssim_mask / psnr_mask (:124-208), in one pass over the two
+ * images.  pred, target: fp32 [n_img, A, B, C], channels last, C in 1..4.  mask (may be NULL): uint8 [n_img, A, B], non-zero = valid.
+ * The window is separable: filter_size taps (host pointer; ODD, 1..15), the images zero-padded by filter_size / 2 on every side, the pass
+ * along B first, then the pass along A, over x, y, x^2, y^2, xy.  Per pixel and channel, with the blurred fields mu0, mu1, exx, eyy, exy:
+ *     s00 = max(exx - mu0^2, 0), s11 = max(eyy - mu1^2, 0), s01 = sign(exy - mu0 mu1) min(sqrt(s00 s11), |exy - mu0 mu1|)
+ *     map = (2 mu0 mu1 + c1) (2 s01 + c2) / ((mu0^2 + mu1^2 + c1) (s00 + s11 + c2))
+ * out [n_img, 4] = (mean of map, mean of (pred - target)^2, the same two means over the pixels the mask selects, all their channels);
+ * a mask that selects nothing, or no mask, gives nan in the last two.  map_out (may be NULL): the map, [n_img, A, B, C].
+ * Two launches on `stream`, no host read: a fused kernel, one workgroup per image and tile of SWN_SSIM_TILE x SWN_SSIM_TILE pixels, whose
+ * blurred fields stay in LDS and which writes five sums (the masked pixel count as an integer) to the tile's own slot of the workspace;
+ * then a reduce over each image's tiles in ascending order with fp64 accumulators.  No atomics: bit-identical from run to run.
+ * Errors: an even filter_size or one outside 1..15 returns -1 (every other error 1, as elsewhere); C outside 1..4; sizes < 1; a
+ * workspace smaller than swn_ssim_workspace_bytes; a null or misaligned pointer.  Nothing is launched on an error.                     */
+#define SWN_SSIM_TILE 32
+int swn_ssim_workspace_bytes(int n_img, int A, int B, size_t* bytes);
+int swn_ssim_fwd(const float* pred, const float* target, const uint8_t* mask, int n_img, int A, int B, int C, const float* taps,
+                 int filter_size, float c1, float c2, float* map_out, void* workspace, size_t workspace_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

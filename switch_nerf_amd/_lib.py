@@ -178,6 +178,8 @@ SIGNATURES = {
     "swn_adam_step_guarded": [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, vp, i64, vp, f32, vp, vp],
     "swn_grad_accum_guarded": [vp, vp, i64, f32, vp, vp],
     "swn_adam_accum_step_guarded": [vp, vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, vp, i64, vp, f32, f32, vp, vp],
+    "swn_ssim_workspace_bytes": [i32, i32, i32, C.POINTER(sz)],
+    "swn_ssim_fwd": [vp, vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, sz, vp, vp],
     "swn_cast": [vp, vp, i32, i64, vp],
     "swn_cast_transpose": [vp, vp, i32, i32, i32, i32, vp],
 }

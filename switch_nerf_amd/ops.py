@@ -1700,6 +1700,34 @@ def adam_accum_step_guarded(param, acc, grad, m, v, shadow, step_state, ok, lr: 
          _p(step_state), float(accum_scale), float(grad_scale), _p(ok), _stream())
 
 
+# ---- image metrics (csrc/ssim.hip; the user-facing layer: metrics.py)
+_ssim_ws = {}
+
+
+def ssim_fwd(pred, target, taps, c1: float, c2: float, mask=None, map_out=None, out=None):
+    """SSIM and squared error of image pairs in one pass (swn_ssim_fwd): pred, target fp32 [n, A, B, C] channels last, C <= 4; taps: the
+    window, a host fp32 tensor of odd length <= 15; mask uint8 [n, A, B] or None -> out [n, 4] = (ssim, mse, ssim over the masked
+    pixels, mse over them; nan without a mask or with an empty one).  map_out [n, A, B, C]: the SSIM map.  Two launches, no host read.
+    The workspace is one per (device, stream, shape), never freed (a captured hipGraph holds its address)."""
+    assert pred.dim() == 4 and pred.shape == target.shape and pred.dtype == target.dtype == torch.float32
+    n, A, B, Cc = pred.shape
+    assert taps.device.type == "cpu" and taps.dtype == torch.float32 and taps.is_contiguous() and taps.dim() == 1
+    assert mask is None or (mask.dtype == torch.uint8 and mask.shape == (n, A, B))
+    assert map_out is None or (map_out.dtype == torch.float32 and map_out.shape == pred.shape)
+    if out is None:
+        out = torch.empty(n, 4, dtype=torch.float32, device=pred.device)
+    assert out.dtype == torch.float32 and out.shape == (n, 4)
+    key = (pred.device, torch.cuda.current_stream().cuda_stream, n, A, B)
+    ws = _ssim_ws.get(key)
+    if ws is None:
+        need = C.c_size_t(0)
+        call("swn_ssim_workspace_bytes", n, A, B, C.byref(need))
+        ws = _ssim_ws[key] = torch.empty(need.value, dtype=torch.uint8, device=pred.device)
+    call("swn_ssim_fwd", _p(pred), _p(target), _p(mask), n, A, B, Cc, C.c_void_p(taps.data_ptr()), taps.numel(), float(c1), float(c2),
+         _p(map_out), _p(ws), ws.numel(), _p(out), _stream())
+    return out
+
+
 def cast(src, dst):
     call("swn_cast", _p(src), _p(dst), _dt(dst), src.numel(), _stream())
     return dst
