@@ -985,6 +985,41 @@ int swn_ssim_workspace_bytes(int n_img, int A, int B, size_t* bytes);
 int swn_ssim_fwd(const float* pred, const float* target, const uint8_t* mask, int n_img, int A, int B, int C, const float* taps,
                  int filter_size, float c1, float c2, float* map_out, void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* ---- rays from cameras (rays.py; raygen.hip) ------------------------------------------------------------------------------------------
+ * The reference's ray_utils.py in fp32, one thread per ray: get_ray_directions (:6-19), get_rays / get_rays_batch (:22-44),
+ * _get_rays_inner (:47-66).  A ray is 8 floats (origin, unit direction, near, far), written as two 16-byte stores.  For the pixel
+ * (col, row) of a camera with intrinsics fx, fy, cx, cy and pose c2w [3][4] (row-major; x down, so an altitude is an x coordinate):
+ *     (i, j) = (col, row), + 0.5 each with center_pixels;  c = ((i - cx) / fx, -(j - cy) / fy, -1) / |.|
+ *     d = c2w[:, :3] c / |.|  (each dot product (c0 r0 + c1 r1) + c2 r2),  o = c2w[:, 3]
+ *     near, far as given; with an altitude pair (a0, a1), for the plane x = a where o.x < a AND d.x > 0:
+ *         w = o - (a, 0, 0), si = -(w . n) / (d . n) with n = (-1, 0, 0), p = w + si d + (a, 0, 0), bound = |o - p|
+ *     near = max(bound(a0) or near, near); far = min(bound(a1) or far, far); far = max(near, far)
+ * IEEE division and square root, no contraction, a norm's squares added as (x^2 + y^2) + z^2: the same pixel of the same camera gives the
+ * same bits through every entry.  No LDS, no atomics, no host read; the output is a pure function of the arguments.
+ * altitude_range: two floats in HOST memory, or NULL (no planes).
+ * swn_rays_from_camera: ONE camera passed by value (`camera` points to HOST memory) -> rays [n, 8] of the row-major pixels
+ *   [pixel_begin, pixel_begin + n) and, when image_indices is not NULL, image_indices [n] = camera->image_index.  The directions are
+ *   never written to memory.
+ * swn_ray_directions: directions [H, W, 3] of the camera space.   swn_rays_from_directions: directions [n, 3] (device) and poses
+ *   c2w [n_cameras, 3, 4] (device, 16-byte aligned) -> rays [n_cameras, n, 8].
+ * swn_rays_from_pixels: the gather form of a training batch.  camera_table [n_cameras, 16] (device): c2w then fx, fy, cx, cy per camera;
+ *   cam_idx / pix_idx [n] int64 (idx_is_i64 != 0) or int32, pix_idx row-major in [0, W * H) -> rays [n, 8].  Index values are not checked.
+ * Errors return -1 and launch nothing: a null pointer, n <= 0, a pixel range outside W * H, an altitude pair that is not ascending,
+ * near > far, a misaligned pointer (rays and tables 16 bytes).                                                                          */
+typedef struct swn_camera {
+  float c2w[12];
+  float fx, fy, cx, cy;
+  int32_t W, H, center_pixels, reserved;
+  int64_t image_index;
+} swn_camera;
+int swn_rays_from_camera(const swn_camera* camera, float near, float far, const float* altitude_range, long pixel_begin, long n,
+                         float* rays, int64_t* image_indices, void* stream);
+int swn_ray_directions(int W, int H, float fx, float fy, float cx, float cy, int center_pixels, float* directions, void* stream);
+int swn_rays_from_directions(const float* directions, const float* c2w, int n_cameras, long n, float near, float far,
+                             const float* altitude_range, float* rays, void* stream);
+int swn_rays_from_pixels(const float* camera_table, int n_cameras, const void* cam_idx, const void* pix_idx, int idx_is_i64, long n, int W,
+                         int H, int center_pixels, float near, float far, const float* altitude_range, float* rays, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,12 @@ class HashCfg(C.Structure):
                 ("aabb_hi", f32 * 3)]
 
 
+class Camera(C.Structure):
+    """swn_camera (include/swn.h): one camera by value - c2w [3][4] row-major, fx, fy, cx, cy, W, H, center_pixels, image_index."""
+    _fields_ = [("c2w", f32 * 12), ("fx", f32), ("fy", f32), ("cx", f32), ("cy", f32), ("W", C.c_int32), ("H", C.c_int32),
+                ("center_pixels", C.c_int32), ("reserved", C.c_int32), ("image_index", C.c_int64)]
+
+
 class ChainDesc(C.Structure):
     _fields_ = [("dtype", i32), ("n_layers", i32), ("n_groups", i32), ("n_wsets", i32), ("group_stride", i32),
                 ("group_rows", vp), ("group_rows_clamp", i32), ("group_begin", vp), ("x", vp), ("x_gather", vp), ("x_save", vp), ("x_scale", vp), ("x_relu", i32),
@@ -180,6 +186,10 @@ SIGNATURES = {
     "swn_adam_accum_step_guarded": [vp, vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, vp, i64, vp, f32, f32, vp, vp],
     "swn_ssim_workspace_bytes": [i32, i32, i32, C.POINTER(sz)],
     "swn_ssim_fwd": [vp, vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp, sz, vp, vp],
+    "swn_rays_from_camera": [C.POINTER(Camera), f32, f32, vp, i64, i64, vp, vp, vp],
+    "swn_ray_directions": [i32, i32, f32, f32, f32, f32, i32, vp, vp],
+    "swn_rays_from_directions": [vp, vp, i32, i64, f32, f32, vp, vp, vp],
+    "swn_rays_from_pixels": [vp, i32, vp, vp, i32, i64, i32, i32, i32, f32, f32, vp, vp, vp],
     "swn_cast": [vp, vp, i32, i64, vp],
     "swn_cast_transpose": [vp, vp, i32, i32, i32, i32, vp],
 }

@@ -1728,6 +1728,79 @@ def ssim_fwd(pred, target, taps, c1: float, c2: float, mask=None, map_out=None, 
     return out
 
 
+# ---- rays from cameras (csrc/raygen.hip; the user-facing layer: rays.py)
+def _alt_arg(ray_altitude_range):
+    """-> a host float[2] for the altitude planes, or None."""
+    if ray_altitude_range is None:
+        return None
+    a = [float(v) for v in ray_altitude_range]
+    if len(a) != 2:
+        raise ValueError(f"ray_altitude_range must be a pair, got {len(a)} values")
+    return (C.c_float * 2)(*a)
+
+
+def _rays_out(out, n: int, dev, lead=()):
+    shape = tuple(lead) + (n, 8)
+    if out is None:
+        return torch.empty(*shape, dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous fp32 device tensor {shape}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def rays_from_camera(camera: "_lib.Camera", near: float, far: float, ray_altitude_range, pixel_begin: int, n: int, out=None,
+                     image_indices_out=None, device=None):
+    """swn_rays_from_camera: the rays [n, 8] of the row-major pixels [pixel_begin, pixel_begin + n) of one camera (a _lib.Camera, passed
+    by value), written into `out` when given; image_indices_out: an int64 [n] filled with the camera's image index.  One launch."""
+    dev = out.device if out is not None else torch.device("cuda" if device is None else device)
+    out = _rays_out(out, n, dev)
+    ii = image_indices_out
+    if ii is not None and (ii.dtype != torch.int64 or tuple(ii.shape) != (n,) or not ii.is_contiguous() or ii.device != out.device):
+        raise ValueError(f"image_indices_out must be a contiguous int64 [{n}] tensor on {out.device}")
+    with torch.cuda.device(out.device):
+        call("swn_rays_from_camera", C.byref(camera), float(near), float(far), _alt_arg(ray_altitude_range), int(pixel_begin), int(n),
+             _p(out), _p(ii), _stream())
+    return out
+
+
+def ray_directions(W: int, H: int, fx: float, fy: float, cx: float, cy: float, center_pixels: bool, device):
+    """swn_ray_directions -> the camera-space unit directions [H, W, 3]."""
+    out = torch.empty(int(H), int(W), 3, dtype=torch.float32, device=device)
+    with torch.cuda.device(out.device):
+        call("swn_ray_directions", int(W), int(H), float(fx), float(fy), float(cx), float(cy), int(bool(center_pixels)), _p(out), _stream())
+    return out
+
+
+def rays_from_directions(directions, c2w, near: float, far: float, ray_altitude_range, out=None):
+    """swn_rays_from_directions: directions [n, 3] and poses c2w [K, 3, 4], both fp32 on the device -> rays [K, n, 8]."""
+    assert directions.dtype == c2w.dtype == torch.float32 and directions.dim() == 2 and directions.shape[1] == 3
+    assert c2w.dim() == 3 and tuple(c2w.shape[1:]) == (3, 4) and c2w.device == directions.device
+    if c2w.data_ptr() % 16:
+        c2w = c2w.clone()
+    n, K = directions.shape[0], c2w.shape[0]
+    out = _rays_out(out, n, directions.device, (K,))
+    with torch.cuda.device(out.device):
+        call("swn_rays_from_directions", _p(directions), _p(c2w), K, n, float(near), float(far), _alt_arg(ray_altitude_range), _p(out),
+             _stream())
+    return out
+
+
+def rays_from_pixels(table, cam_idx, pix_idx, W: int, H: int, center_pixels: bool, near: float, far: float, ray_altitude_range, out=None):
+    """swn_rays_from_pixels: table [M, 16] fp32 (c2w, fx, fy, cx, cy per camera), cam_idx / pix_idx [n] both int32 or both int64 ->
+    rays [n, 8].  Index values are not checked (rays.pixel_rays(check=True) does)."""
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] == 16
+    assert cam_idx.dtype == pix_idx.dtype and cam_idx.shape == pix_idx.shape and cam_idx.dim() == 1
+    assert cam_idx.device == pix_idx.device == table.device
+    n = cam_idx.shape[0]
+    out = _rays_out(out, n, table.device)
+    cp, i64 = _idx_arg(cam_idx)
+    pp, _ = _idx_arg(pix_idx)
+    with torch.cuda.device(out.device):
+        call("swn_rays_from_pixels", _p(table), table.shape[0], cp, pp, i64, n, int(W), int(H), int(bool(center_pixels)), float(near),
+             float(far), _alt_arg(ray_altitude_range), _p(out), _stream())
+    return out
+
+
 def cast(src, dst):
     call("swn_cast", _p(src), _p(dst), _dt(dst), src.numel(), _stream())
     return dst

@@ -261,16 +261,26 @@ def _render_rays_cascade(nerf, bg_nerf, rays, image_indices, hparams, get_depth,
     return res
 
 
-def _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get_depth, get_depth_variance):
+def _render_rays_graphed(nerf, rays, image_indices, hparams, N, S, F, chunk, get_depth, get_depth_variance, fill=None):
     """Evaluation with `nerf.graph_eval = True`: the forward of this batch shape is captured once (graph.GraphedRender, cached on the
     model per (rays, samples, fine samples, chunk, no_batch)) and replayed - Runner.render_image's pixel-batch loop
-    (runner.py:2835-2885) is ~60 launches per call otherwise.  Results are cloned out of the graph's static memory."""
+    (runner.py:2835-2885) is ~60 launches per call otherwise.  Results are cloned out of the graph's static memory.
+    fill (render_image's hook; rays and image_indices are None then): fill(rays_buffer, index_buffer) writes the batch straight into
+    the graph's static inputs, so nothing is copied in."""
     from .graph import GraphedRender, cached_graph
     cache = nerf.__dict__.setdefault("_render_graphs", {})
     key = (N, S, F, int(chunk), bool(nerf.moe_no_batch), nerf.dtype)
     nerf._sync_compute_copies()
+    if fill is not None and key not in cache:      # the capture wants a batch to warm up on
+        rays = torch.empty(N, 8, dtype=torch.float32, device=nerf.dev)
+        image_indices = torch.empty(N, dtype=torch.long, device=nerf.dev)
+        fill(rays, image_indices)
     g = cached_graph(cache, key, lambda: GraphedRender(nerf, rays.contiguous(), image_indices, S, chunk, F, nerf.moe_no_batch))
-    o = g(rays, image_indices)
+    if fill is None:
+        o = g(rays, image_indices)
+    else:
+        fill(g.rays, g.idx)
+        o = g()
     res = _results("fine" if F > 0 else "coarse", o["rgb"], o["l_aux_coarse"], o.get("l_aux_fine"), o["depth"], o["depth_variance"],
                    get_depth, get_depth_variance, take=torch.clone)
     _gate_sigma_keys(res, hparams, dict(idx=o["idx_coarse"], raw=o["raw_coarse"]),
@@ -390,3 +400,93 @@ def render_image_rays(nerf, bg_nerf, rays: torch.Tensor, image_index, hparams, s
         for k, v in batch.items():
             results.setdefault(k, []).append(v.cpu())
     return {k: torch.cat(v) for k, v in results.items()}
+
+
+def _takes_graph_eval(nerf, bg_nerf, hparams) -> bool:
+    """Whether render_rays, in evaluation, ends in its graph_eval branch for these models (its own dispatch, in its order)."""
+    if getattr(nerf, "is_cascade", False) or getattr(hparams, "use_cascade", False):
+        return False
+    if getattr(nerf, "is_mega_nerf", False) or getattr(bg_nerf, "is_mega_nerf", False) or bg_nerf is not None:
+        return False
+    return bool(getattr(nerf, "graph_eval", False)) and getattr(nerf, "ep", None) is None and not _want_points(hparams)
+
+
+def _graphed_image_batch(nerf, hparams, n, fill):
+    """render_rays' steps down to its graph_eval branch (get_depth, no depth variance) for a batch of n rays that `fill` writes into the
+    graph's static inputs (_render_rays_graphed)."""
+    _check_affine(nerf, hparams)
+    _check_sh(nerf, None, hparams)
+    _device_noise(nerf, None, hparams)
+    S, F = hparams.coarse_samples, int(getattr(hparams, "fine_samples", 0))
+    return _render_rays_graphed(nerf, None, None, hparams, n, S, F, min(hparams.model_chunk_size, n * S), True, False, fill=fill)
+
+
+def _model_device(nerf):
+    dev = getattr(nerf, "dev", None)
+    return dev if dev is not None else nerf.halves()[0].dev
+
+
+def render_image(nerf, bg_nerf, camera, hparams, near: float, far: float, ray_altitude_range=None, sphere_center=None,
+                 sphere_radius=None) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
+    """Runner.render_image (/root/reference/switch_nerf/runner.py:2835-2885) from a rays.Camera: the image is walked in batches of
+    hparams.image_pixel_batch_size pixels (a ragged last batch, no padding), each batch's rays come from ONE launch (rays.camera_rays,
+    hparams.center_pixels, default on) and go through render_rays(..., get_depth=True, get_depth_variance=False, get_bg_fg_rgb=True).
+    -> (results, rays [H * W, 8]), everything on the device: a per-ray value is written into its slice of a [H * W, ...] tensor
+    allocated when its key first appears, a 0-dim value is stacked to [n_batches], the gate losses ([chunks * moe layers] per batch) are
+    concatenated in batch order as the reference concatenates them.  Image indices are an int64 tensor of camera.image_index, or None
+    with hparams.appearance_dim == 0.  Every model render_rays accepts in evaluation works and every refusal is render_rays' own.
+    With nerf.graph_eval = True on the plain path the rays (and indices) are generated directly into the cached GraphedRender's static
+    inputs and the graph is replayed; the last batch has its own cached graph.  The rays are fp32 also where the reference builds them
+    inside autocast."""
+    from . import rays as raygen
+    for m, who in ((nerf, "nerf"), (bg_nerf, "bg_nerf")):
+        if m is not None and getattr(m, "training", False):
+            raise RuntimeError(f"render_image: {who} is in training mode; validation images are rendered in evaluation (call .eval())")
+    dev = _model_device(nerf)
+    P = camera.W * camera.H
+    center = bool(getattr(hparams, "center_pixels", True))
+    spans = raygen.batches(P, hparams.image_pixel_batch_size)
+    with_index = getattr(hparams, "appearance_dim", 1) > 0
+    gen = lambda begin, n, out, idx=None: raygen.camera_rays(camera, near, far, ray_altitude_range, center, begin, n, out, idx)
+    graphed = _takes_graph_eval(nerf, bg_nerf, hparams)
+    if graphed:
+        rays = gen(0, P, torch.empty(P, 8, dtype=torch.float32, device=dev))
+    else:
+        rays = torch.empty(P, 8, dtype=torch.float32, device=dev)
+        indices = torch.full((P,), camera.image_index, dtype=torch.long, device=dev) if with_index else None
+    results: Dict[str, torch.Tensor] = {}
+    loose: Dict[str, list] = {}
+    with torch.no_grad():
+        for begin, n in spans:
+            if graphed:
+                def fill(rays_buf, idx_buf, begin=begin, n=n):
+                    own = with_index and idx_buf.dtype == torch.long      # (the fused launch fills an int64 index buffer)
+                    gen(begin, n, rays_buf, idx_buf if own else None)
+                    if not own:
+                        idx_buf.fill_(camera.image_index if with_index else 0)
+                batch = _graphed_image_batch(nerf, hparams, n, fill)
+            else:
+                r = gen(begin, n, rays[begin:begin + n])
+                batch, _ = render_rays(nerf, bg_nerf, r, indices[begin:begin + n] if with_index else None, hparams, sphere_center,
+                                       sphere_radius, True, False, True)
+            for k, v in batch.items():
+                if v.dim() >= 1 and v.shape[0] == n and not k.startswith("gate_loss"):
+                    if k not in results:
+                        results[k] = torch.empty(P, *v.shape[1:], dtype=v.dtype, device=v.device)
+                    results[k][begin:begin + n] = v
+                else:
+                    loose.setdefault(k, []).append(v)
+    for k, v in loose.items():
+        results[k] = torch.stack(v) if v[0].dim() == 0 else torch.cat(v)
+    return results, rays
+
+
+def validate_image(nerf, bg_nerf, camera, target, hparams, near: float, far: float, ray_altitude_range=None, sphere_center=None,
+                   sphere_radius=None, valid_mask=None):
+    """One validation image from a camera, scored where it lies: render_image, the top level's rgb as [H, W, 3], metrics.image_metrics
+    against target [H, W, 3] (valid_mask [H, W]: the cell's mask) -> (the metrics as device tensors, the image).  No host read."""
+    from . import metrics
+    results, _ = render_image(nerf, bg_nerf, camera, hparams, near, far, ray_altitude_range, sphere_center, sphere_radius)
+    typ = "fine" if "rgb_fine" in results else "coarse"
+    image = results[f"rgb_{typ}"].view(camera.H, camera.W, 3)
+    return metrics.image_metrics(image, target, valid_mask=valid_mask), image
