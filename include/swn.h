@@ -596,6 +596,16 @@ typedef struct swn_chain_desc {
   int32_t x_features;           /* geometry 6 / 7: features per row of x when fewer than layers[0].k: 128 under a first layer whose packed
                                    weights are zero-padded from k = 128 to k = 256 (the rows of x are 128 features wide; the kernel zeroes
                                    the other half of its input tile).  0 = layers[0].k                                         */
+  int32_t x_k;                  /* geometry 7 with x_features = 128: the first layer's REAL K - columns x_k .. 255 of its padded weights
+                                   are zero (or meet zero columns of x), and the first layer's K loop runs x_k / 16 steps instead of 16:
+                                   it neither fetches the other weight fragments nor reads the other half of the input tile (which
+                                   the kernel then leaves unzeroed).  A multiple of 16 with 0 < x_k <= 128.  One kernel per K-loop
+                                   length: built for tag 3 (x_k = 80 or 128) and for tags 5 and 8 (x_k = 128); swn_mlp_chain refuses
+                                   everything else.  The sums are those of the padded layer - the products left out are finite x 0,
+                                   the order of the others per accumulator is unchanged - so the results have the same bits, except
+                                   that a non-finite value of x reaches every output of the padded layer as NaN and here only through
+                                   its real products (and a sum that is exactly -0 keeps its sign).
+                                   0 = run all of layers[0].k (the padded layer as it stands)                                      */
   /* The dense TAIL of the network folded into the expert FORWARD chain (tail_first > 0; geometry 7, tag 7, x_gather required): the
      expert output never travels to memory and back between the MoE layer and the layers behind it (models/nerf_moe.py:385-441:
      GatingDecoder -> act relu -> sigma head, Linear "1", Linear "2" over cat([h, PE(dir), embedding_a]), colour head).

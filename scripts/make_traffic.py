@@ -18,9 +18,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # launch of bench.py's `kernels` table -> the kernels whose counters add up to it (substring match on the demangled name)
 LAUNCHES = {
     "expert_fwd": ["chainq_kernel<swn_big::Bf16, 7, true>"],
-    "expert_bwd": ["chainq_kernel<swn_big::Bf16, 8, true>", "dwsig_runs_kernel"],
+    "expert_bwd": ["chainq_kernel<swn_big::Bf16, 8, true>", "chainq_xk_kernel<swn_big::Bf16, 8, 8>", "dwsig_runs_kernel"],
     "expert_wgrad": ["wgrad_stream_kernel<unsigned short, 1>"],
-    "front_fwd": ["chainq_kernel<swn_big::Bf16, 3, true>"],
+    "front_fwd": ["chainq_kernel<swn_big::Bf16, 3, true>", "chainq_xk_kernel<swn_big::Bf16, 3, 5>", "chainq_xk_kernel<swn_big::Bf16, 3, 8>"],
     "front_bwd": ["chainq_kernel<swn_big::Bf16, 6, true>"],
     "dense_wgrad": ["wgrad_stream_kernel<unsigned short, 0>"],
     "gate_fwd": ["gate_fwd_mfma_kernel"],

@@ -63,7 +63,7 @@ class ChainDesc(C.Structure):
                 ("y", vp), ("y_add", vp), ("y_add_gather", vp), ("geometry", i32), ("tag", i32),
                 ("comb_y", vp), ("comb_dsig", vp), ("comb_wsig", vp), ("comb_gate", vp), ("comb_dgate", vp), ("comb_dwsig", vp), ("comb_dwsig_ws", vp),
                 ("heads_ws", vp), ("heads_bs", vp), ("heads_wc", vp), ("heads_bc", vp), ("heads_noise", vp), ("heads_raw", vp), ("sched", vp), ("x_features", i32),
-                ("head_layers", i32), ("tail_first", i32), ("y_features", i32), ("tail_gate", vp), ("tail_dropped", vp), ("tail_n_dropped", vp),
+                ("x_k", i32), ("head_layers", i32), ("tail_first", i32), ("y_features", i32), ("tail_gate", vp), ("tail_dropped", vp), ("tail_n_dropped", vp),
                 ("tail_dropped_max", i32), ("tail_tokens", i32), ("tail_bias_row", vp),
                 ("layers", ChainLayer * 12), ("packed_rows", i32)]
 

@@ -1322,6 +1322,14 @@ extern "C" int swn_mlp_chain(const swn_chain_desc* desc, void* stream) {
   SWN_CHECK(d.tag != 7 || d.tail_first > 0, "swn_mlp_chain: tag 7 is the fused-tail forward chain (tail_first > 0)");
   SWN_CHECK(d.x_features == 0 || d.x_features == d.layers[0].k || (d.x_features == 128 && d.layers[0].k == 256 && d.geometry >= 6),
             "swn_mlp_chain: x_features = %d: only 128-feature rows under a zero-padded k = 256 first layer on geometry 6 / 7", d.x_features);
+  if (d.x_k != 0) {      // the first layer's real K (include/swn.h): meaningful only where the first layer is padded in K
+    SWN_CHECK(d.x_k > 0 && d.x_k <= 256, "swn_mlp_chain: x_k = %d not in (0, 256]", d.x_k);
+    SWN_CHECK(d.x_k % 16 == 0, "swn_mlp_chain: x_k = %d is not a multiple of the K step (16)", d.x_k);
+    SWN_CHECK(d.geometry >= 6, "swn_mlp_chain: x_k = %d: only the persistent chains (geometry 6 / 7) take a real K, not geometry %d", d.x_k, d.geometry);
+    SWN_CHECK(d.x_features == 128, "swn_mlp_chain: x_k = %d needs x_features = 128 (a first layer zero-padded in K), not %d", d.x_k, d.x_features);
+    SWN_CHECK(d.x_k <= ((d.x_features + 15) & ~15), "swn_mlp_chain: x_k = %d beyond x_features = %d", d.x_k, d.x_features);
+    SWN_CHECK(d.tail_first == 0, "swn_mlp_chain: x_k = %d: a fused tail's chain input is 256 features wide", d.x_k);
+  }
   SWN_CHECK(!(wide && concat), "swn_mlp_chain: concat-skip layers are built for the 256-feature kernels only");
   SWN_CHECK(d.geometry >= 0 && d.geometry <= 7, "swn_mlp_chain: geometry %d not in [0,7]", d.geometry);
   SWN_CHECK(d.packed_rows >= 0, "swn_mlp_chain: packed_rows %d < 0", d.packed_rows);

@@ -604,9 +604,14 @@ __global__ __launch_bounds__(G::NT, G::OCC) void chainb_kernel(const Args args) 
 #define SWN_WQ_DEPTH 4            // weight-fragment register sets of a wave's K loop: SWN_WQ_DEPTH - 1 K steps in flight
 #endif
 constexpr int WQD = SWN_WQ_DEPTH, WQA = SWN_WQ_DEPTH - 1;
-template <typename E, int NS = KSTEPS>
+// NS < WS (geometries 6 / 7, swn_chain_desc.x_k): a first layer whose real K is NS * 16 under weights zero-padded to K = WS * 16 - the
+// loop runs the real steps only, on the first NS of every feature tile's WS fragments and the first NS * 32 bytes of the LDS rows.  The
+// products it leaves out are finite x 0: the accumulators receive the same sums in the same order.  (Not the same: a non-finite
+// activation - NaN in every output of the padded layer, not here - and the sign of a sum that is exactly -0.)
+template <typename E, int NS = KSTEPS, int WS = NS>
 __device__ __forceinline__ void k_phase2(f32x16_t (&acc)[4][2], const Ctx& cx, __amdgpu_buffer_rsrc_t rs_cur, u32x4_t (&wq)[WQD][2]) {
-  constexpr int MI = 4;           // NS = K steps of this layer (K / 16): 16, or 8 for a 128-feature chain input (geometries 6 / 7)
+  constexpr int MI = 4;           // NS = K steps of this layer, WS = fragments per feature tile of its packed weights
+  static_assert(NS >= WQA && NS <= WS, "k_phase2: the caller's preload covers steps 0 .. WQA - 1");
   char* smem = cx.smem;
   const int lane16 = cx.lane * 16;
   const int fg = cx.w & 3;
@@ -619,7 +624,7 @@ __device__ __forceinline__ void k_phase2(f32x16_t (&acc)[4][2], const Ctx& cx, _
   auto load_w = [&](int ks) {          // the two feature tiles of this wave, K step ks
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      wq[ks % WQD][i] = __builtin_amdgcn_raw_buffer_load_b128(rs_cur, lane16, ((2 * fg + i) * NS + ks) * 1024, 0);
+      wq[ks % WQD][i] = __builtin_amdgcn_raw_buffer_load_b128(rs_cur, lane16, ((2 * fg + i) * WS + ks) * 1024, 0);
   };
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) read_a(0, mi);
@@ -1090,9 +1095,10 @@ constexpr int Q_LDS = Q_YIDX + 2048;
 // instantiation for every layer: a second, 8-step one beside it cost 160 spilled registers): the first 16 chunk positions of a tile row
 // receive the row - position p of row r holds chunk p ^ (r & 15) < 16, copied by the lanes that own them (an inactive lane of an
 // LDS-DMA writes nothing) - and the other lanes ZERO the upper 16 positions (what is left there from the previous tile would meet zero
-// weights, but 0 x inf is not 0)
+// weights, but 0 x inf is not 0).  zero_hi = false: the first layer's K loop stops inside the row's 128 features (swn_chain_desc.x_k) and nothing reads the
+// upper positions before the first epilogue rewrites the rows - they are left as they are.
 template <bool NARROW>
-__device__ __forceinline__ void stage_pieces_q(const Ctx& cx, const char* x, int c0, int n, int stride, int idx_off) {
+__device__ __forceinline__ void stage_pieces_q(const Ctx& cx, const char* x, int c0, int n, int stride, int idx_off, bool zero_hi = true) {
   const int* idx = (const int*)(cx.smem + idx_off);
   constexpr int XRB = NARROW ? 256 : ROWB;
   // all source rows first (one LDS round trip), then the copies back to back: with the index read in front of every copy the 16 copies of
@@ -1101,7 +1107,7 @@ __device__ __forceinline__ void stage_pieces_q(const Ctx& cx, const char* x, int
 #pragma unroll
   for (int j = 0; j < 16; ++j) src[j] = j < n ? idx[2 * (c0 + j * stride) + cx.lhi] : 0;
   if constexpr (NARROW) {       // the zero half FIRST: behind an LDS-DMA every LDS write waits for the copy to land (one HBM round trip each)
-    if (cx.l31 >= 16) {
+    if (zero_hi && cx.l31 >= 16) {
 #pragma unroll
       for (int j = 0; j < 16; ++j)
         if (j < n) *(u32x4_t*)(cx.smem + (c0 + j * stride) * 1024 + cx.lane * 16) = u32x4_t{0u, 0u, 0u, 0u};
@@ -1485,8 +1491,13 @@ __device__ __forceinline__ int fresh_lane() {
   return l;
 }
 
-template <typename E, int TAG, bool BIAS_INIT>
-__global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
+// XS: K steps of the chain's FIRST layer (swn_chain_desc.x_k / 16 where the launch sets it, KSTEPS otherwise).  XS < KSTEPS: the first
+// layer of a tile is run in FRONT of the layer loop, with a K loop of its own length (k_phase2<E, XS, KSTEPS>) - straight-line code, one
+// kernel per length, chosen by the launch.  (A branch between two K loops inside the layer loop, in any form - two loops side by side,
+// one loop entered at its half, one loop with eight steps jumped over - left 119 to 316 spilled registers: the two arms meet with the
+// 128 accumulator registers and both fragment rings live.)
+template <typename E, int TAG, bool BIAS_INIT, int XS>
+__device__ __forceinline__ void chainq_body(const ArgsQ& args) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef G256 G;
   constexpr int BM = G::BM, MI = 4;
@@ -1677,7 +1688,9 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
     const int lt = fg * 64 + fresh_lane();
     if (lt < 128) ((int*)(smem + idx_off))[128 * rg + lt] = src < 0 ? 0 : src;
   };
-  const bool narrow = d.x_features == 128;                  // 128-feature chain input (256-byte rows) under a K = 256 zero-padded first layer
+  const bool narrow = d.x_features == 128;                  // 128-feature chain input (256-byte rows) under a first layer whose weights are zero-padded to K = 256
+  constexpr bool k_short = XS != KSTEPS;                    // ... whose K loop runs the real K only (swn_chain_desc.x_k): no zero half needed
+  static_assert(!k_short || !TAIL, "a fused tail's chain input is 256 features wide");
   auto wrs = [&](int L, int wset) -> __amdgpu_buffer_rsrc_t {
     const int bytes = 8 * (d.layers[L].k >> 4) * 1024;      // 8 feature tiles x K / 16 steps of 1 KiB
     const char* p = (const char*)d.layers[L].w + (size_t)wset * bytes;
@@ -1871,7 +1884,7 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
             dsig_v = d.comb_dsig ? d.comb_dsig[tok] : 0.f;
           }
         }
-        stage_pieces_q<true>(cs, (const char*)d.x, 64 * rgs + fgs, 16, 4, idx_cur);
+        stage_pieces_q<true>(cs, (const char*)d.x, 64 * rgs + fgs, 16, 4, idx_cur, !k_short);
       } else if constexpr (TAIL) {
         if (cur.l0) {
           stage_dropped(cs, cur, idx_cur, keep[15]);     // (tail_out holds keep[0..7])
@@ -1879,7 +1892,7 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
           if (lts < 128) gate_v = d.tail_gate[((const int*)(smem + idx_cur))[128 * rgs + lts]];      // the rows' gate values -> T_GATE below
           stage_pieces_q<false>(cs, (const char*)d.x, 64 * rgs + fgs, 16, 4, idx_cur);
         }
-      } else if (narrow) stage_pieces_q<true>(cs, (const char*)d.x, 64 * rgs + fgs, 16, 4, idx_cur);
+      } else if (narrow) stage_pieces_q<true>(cs, (const char*)d.x, 64 * rgs + fgs, 16, 4, idx_cur, !k_short);
       else stage_pieces_q<false>(cs, (const char*)d.x, 64 * rgs + fgs, 16, 4, idx_cur);
       if (cs.w == 0) grab((it + 1) & 1, ticket);   // the tile after this one (both row groups read it during their last epilogue phase)
       SWN_TM(const long long si = TICK(); tSi += si - s0;)
@@ -1906,7 +1919,8 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
     SWN_TM(const long long s1 = TICK(); tS += s1 - s0;)
     Tile nxt = cur;
     const int l_end = HEAD ? cur.l1 : n_layers;
-    for (int L = cur.l0; L < l_end; ++L) {
+    auto run_layer = [&](const int L, auto first_c) {      // first_c: the tile's first layer under a K loop of XS steps
+      constexpr bool SHORT_K = decltype(first_c)::value;
       const swn_chain_layer& ly = d.layers[L];
       const bool last = L + 1 == l_end;
       // The phase boundary in front of every K phase (behind the S phase or the preceding E phase) sits HERE, with the bias values of
@@ -1947,7 +1961,8 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
         }
         {
           const Ctx ck = phase_ctx(true);
-          k_phase2<E>(acc, ck, rs_cur, wq);
+          if constexpr (SHORT_K) k_phase2<E, XS, KSTEPS>(acc, ck, rs_cur, wq);
+          else k_phase2<E>(acc, ck, rs_cur, wq);
         }
 #pragma unroll
         for (int q_ = 0; q_ < WQD; ++q_)
@@ -2083,7 +2098,9 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
         SWN_TM(const long long e2 = TICK(); tE += e1 - e0; tEb += e2 - e1;)
       }
       ++bc;
-    }
+    };
+    if constexpr (k_short) run_layer(cur.l0, std::true_type());      // (cur.l0 = 0: only a fused tail's tiles start further back)
+    for (int L = cur.l0 + (k_short ? 1 : 0); L < l_end; ++L) run_layer(L, std::false_type());
     prev = cur;
     cur = nxt;
     ++it;
@@ -2122,6 +2139,12 @@ __global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) {
   finish();
 }
 
+template <typename E, int TAG, bool BIAS_INIT>
+__global__ __launch_bounds__(512, 2) void chainq_kernel(const ArgsQ args) { chainq_body<E, TAG, BIAS_INIT, KSTEPS>(args); }
+// ... with the first layer at XS < KSTEPS K steps (geometry 7: the accumulators start at the bias)
+template <typename E, int TAG, int XS>
+__global__ __launch_bounds__(512, 2) void chainq_xk_kernel(const ArgsQ args) { chainq_body<E, TAG, true, XS>(args); }
+
 }  // namespace swn_big
 
 namespace swn {
@@ -2142,7 +2165,7 @@ bool chain_big_eligible(const swn_chain_desc& d) {
 }
 
 // geometries 6 / 7 (chainq_kernel) also take the dense front chains: a 128-feature chain input (x_features = 128 under a first layer
-// whose weights are zero-padded to k = 256) and a gathered y_add
+// whose weights are zero-padded to k = 256; x_k: its K loop stops at the real K - chain_persistent_launch) and a gathered y_add
 bool chain_persistent_eligible(const swn_chain_desc& d) {
   if (d.tail_first > 0) {      // the dense tail folded into the expert forward chain: chainq_kernel<., 7, true> only
     if (d.dtype != SWN_HALF || d.geometry != 7 || d.tag != 7 || d.x_save || d.x_scale || d.y_add || d.comb_y || !d.x_gather) return false;
@@ -2321,6 +2344,16 @@ static int chain_persistent_launch(const swn_chain_desc& d, void* stream) {
     default: fn = d.geometry == 7 ? (const void*)chainq_kernel<HalfT, 0, true> : (const void*)chainq_kernel<HalfT, 0, false>;
   }
 #undef SWN_PICKQ
+  if (d.x_k) {      // the first layer's real K (swn_chain_desc.x_k): one kernel per K-loop length - the ones the model's launches use
+    const int xs = d.x_k >> 4;
+    fn = nullptr;
+    if (d.geometry == 7 && d.tag == 3 && xs == 5) fn = (const void*)chainq_xk_kernel<HalfT, 3, 5>;
+    if (d.geometry == 7 && d.tag == 3 && xs == 8) fn = (const void*)chainq_xk_kernel<HalfT, 3, 8>;
+    if (d.geometry == 7 && d.tag == 5 && xs == 8) fn = (const void*)chainq_xk_kernel<HalfT, 5, 8>;
+    if (d.geometry == 7 && d.tag == 8 && xs == 8) fn = (const void*)chainq_xk_kernel<HalfT, 8, 8>;
+    SWN_CHECK(fn != nullptr, "swn_mlp_chain: x_k = %d on geometry %d, tag %d: built for geometry 7 with tag 3 (x_k = 80, 128), tag 5 and tag 8 (x_k = 128)",
+              d.x_k, d.geometry, d.tag);
+  }
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Q_LDS);
   SWN_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
   const long dws_rows = d.comb_dwsig_ws ? (long)a.n_vb_e * 8 : 0;      // (tiles without rows are never visited: their slots stay zero)

@@ -802,7 +802,7 @@ class SwitchNeRF:
                               o.Layer(self.wf["gate0"], self.p["gate0.b"].view(1, G), relu=1, mask=c["m_a1"] if sv else None,
                                       save=c["a1"] if sv else None),
                               o.Layer(self.wf["gate1"], self.p["gate1.b"].view(1, G))], c["g"], tag=3, geometry=c["front_geom"] if big else 0,
-                    x_features=self.KP if big else 0)
+                    x_features=self.KP if big else 0, x_k=self._xyz_k() if c["front_geom"] == 7 else 0)
         if not (sv and self.gate_noise > 0):       # (training only, like `self.training and self.gate_noise > 0`)
             return None
         if self.gate_noise_draw is None and self.noise.on:     # stream 4, element (ray_base * S + point) * E + expert
@@ -1185,7 +1185,8 @@ class SwitchNeRF:
             dgmax = self._cbuf(c, "dgmax", (P,), torch.float32)
             tg = self.sw["tail_geom"] if self._tail_big() else 0
             o.mlp_chain(dh2, [o.Layer(self.wb["l2h_pad" if tg >= 6 else "l2h"], None, save=dh1), o.Layer(self.wb["l1"], None)], dout, tag=5,
-                        combine=(c["y"], dsig, self.p["sigma.w"], c["gmax"], dgmax), geometry=tg, x_features=H2 if tg >= 6 else 0)
+                        combine=(c["y"], dsig, self.p["sigma.w"], c["gmax"], dgmax), geometry=tg, x_features=H2 if tg >= 6 else 0,
+                        x_k=H2 if tg == 7 else 0)
         else:
             o.mlp_chain(dh2, [o.Layer(self.wb["l2h"], None, save=dh1), o.Layer(self.wb["l1"], None)], dout, tag=5)
             dout, dgmax = o.combine_bwd(dout, c["y"], dsig, self.p["sigma.w"], c["gmax"])
@@ -1193,6 +1194,13 @@ class SwitchNeRF:
                                                    # per-GPU batch of an 8-GPU run (262144 points)
         b["dh1"], b["dout"], b["dgmax"] = dh1, dout, dgmax
         b["tail_jobs"] = [(c["h1"], dh2, g["l2h.w"].view(1, M, H2), None), (c["y"], dh1, g["l1.w"].view(1, M, M), g["l1.b"].view(1, M))]
+
+    def _xyz_k(self):
+        """The first front layer's real K for the persistent chain (swn_chain_desc.x_k): the encoding's width rounded up to the K step where
+        the library has a K loop of that length (80 = the default 75 columns), else the padded row's 128 columns; the rest of a c["pe"]
+        row is zeros."""
+        k = _ceil_to(self.in_xyz, 16)
+        return k if k == 80 else 128
 
     def _tail_wgrads_if_large(self, c, b):
         """The tail layers' weight gradients as their own launch, at the full batch only."""
@@ -1224,7 +1232,7 @@ class SwitchNeRF:
         grp = self._group_args(c)
 
         def run_expert_bwd():
-            o.mlp_chain(b["dh2"], lys, dx, y_add=y_add, tag=8, geometry=7, x_features=self.H2,
+            o.mlp_chain(b["dh2"], lys, dx, y_add=y_add, tag=8, geometry=7, x_features=self.H2, x_k=self.H2,
                         combine=(c["y"], b["dsig"], self.p["sigma.w"], c["gmax"], b["dgmax"], dws_dst[0]), head=(2, c["drop_begin"], c["dropped"]),
                         group_begin=c.get("group_begin"), packed_rows=c.get("packed_rows", 0), **grp)
         with self._timed("expert_bwd"):

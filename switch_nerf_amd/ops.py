@@ -1419,7 +1419,7 @@ def chain_mask_words_packed(dtype, rows: int, n_groups: int, max_width: int = 25
 def mlp_chain(x, layers: Sequence[Layer], y, n_groups=1, n_wsets=1, group_stride=None, group_rows=None,
               group_rows_clamp=None, x_gather=None, x_save=None, y_add=None, y_add_gather=None, tag=0, x_scale=None,
               x_relu=False, geometry=0, group_begin=None, combine=None, heads=None, sched=None, x_features=0, tail=None, head=None,
-              packed_rows=0):
+              packed_rows=0, x_k=0):
     """geometry: 0 / 1 the 64-row tile kernels, 2 - 5 the chain_big.hip geometries (include/swn.h).  group_begin: first row of every
     group (packed / no-batch layout) instead of g * group_stride.  combine = (y_fwd, dsig, wsig, gate, dgate_out): the combine backward
     (ops.combine_bwd) fused into the write-out of the last layer.  heads = (w_sigma, b_sigma, w_color, b_color, sigma_noise or None, raw):
@@ -1431,7 +1431,9 @@ def mlp_chain(x, layers: Sequence[Layer], y, n_groups=1, n_wsets=1, group_stride
     head = (head_layers, drop_begin, dropped): the mirror image for the backward pass (include/swn.h, head_layers: geometry 7, tag 8) -
     x = dh2 in token order, layers[:head_layers] shared, `combine` (token order) applied behind them, the expert backward layers after.
     packed_rows > 0: packed ReLU-mask slots (include/swn.h swn_chain_desc.packed_rows; group_begin required, geometry 0 / 1 / 7): the
-    masks of a row space of at most packed_rows rows, sized by chain_mask_words_packed - the forward and backward chains set it alike."""
+    masks of a row space of at most packed_rows rows, sized by chain_mask_words_packed - the forward and backward chains set it alike.
+    x_k > 0 (with x_features = 128): the first layer's real K - the zero half of its padded weights is not multiplied (include/swn.h
+    swn_chain_desc.x_k; same bits as x_k = 0 for finite x)."""
     d = ChainDesc()
     d.packed_rows = int(packed_rows)
     d.dtype = _dt(x)
@@ -1462,6 +1464,7 @@ def mlp_chain(x, layers: Sequence[Layer], y, n_groups=1, n_wsets=1, group_stride
     d.x_scale, d.x_relu = _p(x_scale), int(bool(x_relu))
     d.y_add, d.y_add_gather = _p(y_add), _p(y_add_gather)
     d.x_features = int(x_features)                 # (geometry 6 / 7: 128-feature rows under a zero-padded K = 256 first layer)
+    d.x_k = int(x_k)                               # (... whose K loop stops at the real K)
     if sched is None and d.geometry >= 6 and not CHAINQ_STATIC:
         sched = chain_sched(x.device, d.tag)       # (launches of one role on one stream are ordered: they can share the counters)
     if sched is not None:
