@@ -918,6 +918,21 @@ int swn_cells_gather(const float* x, int stride, int col0, const int32_t* rows, 
  *   position = centroids[r / capacity], direction (0, 0, 1), image index 0, sigma noise 0.                                           */
 int swn_cells_gather_padded(const float* x, int stride, int col0, const int32_t* rows, const float* centroids, int n_cells, int capacity,
                             int n_points, const float* sigma_noise, float* x_out, float* noise_out, void* stream);
+/* swn_cells_gather_rng / swn_cells_gather_padded_rng: the two gathers above with the sigma noise DRAWN at the packed row instead of read
+ *   from a [n_points] tensor (the seeded device noise of joint training; no such tensor is written or read).  Packed row r holds point
+ *   p = rows[r]; noise_out[r] = scale * the normal draw of global element e = ray_base * rows_per_ray + p of (seed, step_dev[0],
+ *   stream_id), domain 0 - bit for bit what swn_rng_fill(kind = 1, base = ray_base * rows_per_ray, scale) writes at index p; the
+ *   Box-Muller half follows the parity of the GLOBAL element e.  A point in several cells gets the same value in each; a row with
+ *   rows[r] < 0 (padding) or >= n_points gets exactly +0.  rows_per_ray: the rows per ray of the pass (p = ray * rows_per_ray + sample);
+ *   step_dev: the device int64[1] step counter, read by the kernel (a captured launch follows it).  x_out: the bytes of the plain
+ *   gathers.  Errors (nothing is launched): a null pointer, scale <= 0, a stream_id other than 1 (coarse sigma noise) or 3 (fine),
+ *   rows_per_ray <= 0, a negative ray_base or one whose element index overflows, and the plain gathers' own.                       */
+int swn_cells_gather_rng(const float* x, int stride, int col0, const int32_t* rows, long total, int n_points, uint64_t seed,
+                         const int64_t* step_dev, int stream_id, int rows_per_ray, int64_t ray_base, float scale, float* x_out,
+                         float* noise_out, void* stream);
+int swn_cells_gather_padded_rng(const float* x, int stride, int col0, const int32_t* rows, const float* centroids, int n_cells,
+                                int capacity, int n_points, uint64_t seed, const int64_t* step_dev, int stream_id, int rows_per_ray,
+                                int64_t ray_base, float scale, float* x_out, float* noise_out, void* stream);
 /* swn_cells_blend: out[p][:] = sum over the member cells i, ascending, of weights[p][i] * sub_out[begin[i] + slot[p][i]][:], channels 1
  *   or 4; hard != 0 (margin == 1): the plain copy of the one member's row (:47).  One thread per point: no atomics, no zero fill,
  *   the sum order is the reference's loop order.                                                                                   */

@@ -169,6 +169,8 @@ SIGNATURES = {
     "swn_cells_pack_padded": [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp],
     "swn_cells_gather": [vp, i32, i32, vp, i64, i32, vp, vp, vp, vp],
     "swn_cells_gather_padded": [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "swn_cells_gather_rng": [vp, i32, i32, vp, i64, i32, u64, vp, i32, i32, i64, f32, vp, vp, vp],
+    "swn_cells_gather_padded_rng": [vp, i32, i32, vp, vp, i32, i32, i32, u64, vp, i32, i32, i64, f32, vp, vp, vp],
     "swn_cells_blend": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp],
     "swn_cells_blend_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp],
     "swn_cells_blend_sh": [vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp, vp, vp],

@@ -7,6 +7,8 @@
 //   cells_gather_kernel    every cell's input rows (and sigma-noise rows) from rows[]
 //   cells_pad_kernel, cells_gather_padded_kernel      the PADDED row space (swn_cells_pack_padded, swn_cells_gather_padded): every
 //                          cell owns a fixed range of `capacity` rows, so nothing about a step's shapes depends on the batch
+//   cells_gather_rng_kernel, cells_gather_padded_rng_kernel   the two gathers with the sigma noise DRAWN at the packed row (philox.hpp)
+//                          instead of read from a [P] tensor: the seeded device noise of joint training (mega.py)
 //   cells_blend_kernel     out[p] = sum over the member cells, ascending, of weights * sub-model output (a per-point gather: no atomics)
 //   cells_blend_bwd_kernel d_sub[r] = weights * d_out[rows[r]]: the blend's adjoint, one packed row per thread (training, mega.py)
 // Plain C++, fp32, fma contraction off: the distance is the direct sqrt(sum (x_j - c_j)^2) in the order j = dim_start .. 2 and the
@@ -14,6 +16,7 @@
 // Everything that decides an ORDER is an integer (counts, prefixes, ranks from wave ballots): the packing is a pure function of the
 // input, rows ascend by point index inside a cell (the order x[cluster_mask] has in the reference).
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace swn {
 
@@ -240,6 +243,66 @@ __global__ __launch_bounds__(256) void cells_gather_padded_kernel(const float* _
   if (c == 0 && noise) noise_out[r] = real ? noise[p] : 0.f;
 }
 
+// The sigma noise of a packed row, drawn where it is consumed: the row holds point p = rows[r], global element e = elem_base + p of
+// (seed, step, stream_id), domain 0 - the bits swn_rng_fill (kind = normal) writes for element e.  The Box-Muller pair is the word
+// pair (0,1) or (2,3) of block e >> 2 and the half follows the parity of the GLOBAL element e (as in rng_fill_rows_kernel), so an odd
+// rows-per-ray or an odd ray base makes neighbouring points share a pair exactly as the fill does.  A point that sits in several cells
+// (soft margin) draws the same element in each: the reference's sigma_noise[cluster_mask].
+__device__ __forceinline__ float cells_row_normal(uint64_t seed, uint32_t step, int stream_id, long e, float scale) {
+  const PhiloxWords v = philox_block(seed, step, stream_id, e >> 2);
+  const bool hi = (e & 2) != 0;
+  float n_even, n_odd;
+  philox_normal_pair(hi ? v.w[2] : v.w[0], hi ? v.w[3] : v.w[1], scale, n_even, n_odd);
+  return (e & 1) ? n_odd : n_even;
+}
+
+// cells_gather_kernel with the noise drawn.  The copy keeps its layout (one thread per element of x_out, the same bytes); the draw has
+// its own: thread t < total draws row t, so the Philox rounds and the logf / sincosf run in full waves at the front of the grid and
+// not in the one lane in `width` that holds a row's first column.  No [P] noise tensor exists; a row with rows[r] outside [0, P) gets +0.
+__global__ __launch_bounds__(256) void cells_gather_rng_kernel(const float* __restrict__ x, int stride, int col0, const int32_t* __restrict__ rows,
+                                                              long total, int P, uint64_t seed, const int64_t* __restrict__ step_dev,
+                                                              int stream_id, long elem_base, float scale, float* __restrict__ x_out,
+                                                              float* __restrict__ noise_out) {
+  const int width = stride - col0;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total * width) return;
+  const long r = e / width;
+  const int c = (int)(e - r * width);
+  const int p = rows[r];
+  const bool ok = p >= 0 && p < P;
+  x_out[e] = ok ? x[(long)p * stride + col0 + c] : 0.f;
+  if (e < total) {
+    const int q = rows[e];
+    noise_out[e] = q >= 0 && q < P ? cells_row_normal(seed, (uint32_t)*step_dev, stream_id, elem_base + q, scale) : 0.f;
+  }
+}
+
+// cells_gather_padded_kernel with the noise drawn (cells_gather_rng_kernel's layout): a padding row gets exactly +0.
+__global__ __launch_bounds__(256) void cells_gather_padded_rng_kernel(const float* __restrict__ x, int stride, int col0,
+                                                                     const int32_t* __restrict__ rows, const float* __restrict__ centroids,
+                                                                     int K, int capacity, int P, uint64_t seed,
+                                                                     const int64_t* __restrict__ step_dev, int stream_id, long elem_base,
+                                                                     float scale, float* __restrict__ x_out, float* __restrict__ noise_out) {
+  constexpr int width = 7;
+  const long total = (long)K * capacity;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total * width) return;
+  const long r = e / width;
+  const int c = (int)(e - r * width);
+  const int p = rows[r];
+  const bool real = p >= 0 && p < P;
+  float v;
+  if (real)
+    v = x[(long)p * stride + col0 + c];
+  else
+    v = c < 3 ? centroids[(r / capacity) * 3 + c] : (c == 5 ? 1.f : 0.f);
+  x_out[e] = v;
+  if (e < total) {
+    const int q = rows[e];
+    noise_out[e] = q >= 0 && q < P ? cells_row_normal(seed, (uint32_t)*step_dev, stream_id, elem_base + q, scale) : 0.f;
+  }
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void cells_blend_kernel(const float* __restrict__ weights, const int32_t* __restrict__ slot,
                                                          const int32_t* __restrict__ begin, const float* __restrict__ sub_out, long total,
@@ -414,6 +477,55 @@ extern "C" int swn_cells_gather_padded(const float* x, int stride, int col0, con
             capacity);
   hipLaunchKernelGGL(cells_gather_padded_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, stride, col0, rows, centroids,
                      n_cells, capacity, n_points, sigma_noise, x_out, noise_out);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+// what both _rng gathers check of the draw before anything is launched; the element index ray_base * rows_per_ray + point must fit
+static int cells_rng_check(const char* name, const int64_t* step_dev, const float* noise_out, int stream_id, int rows_per_ray,
+                           int64_t ray_base, float scale, int n_points) {
+  SWN_CHECK(step_dev && noise_out, "%s: null pointer", name);
+  SWN_CHECK(scale > 0.f, "%s: scale %g is not > 0 (no sigma noise: that is the plain gather)", name, (double)scale);
+  SWN_CHECK(stream_id == RNG_STREAM_SIGMA || stream_id == RNG_STREAM_SIGMA_FINE,
+            "%s: stream id %d is neither %d (coarse sigma noise) nor %d (fine sigma noise)", name, stream_id, (int)RNG_STREAM_SIGMA,
+            (int)RNG_STREAM_SIGMA_FINE);
+  SWN_CHECK(rows_per_ray > 0, "%s: rows_per_ray %d is not > 0", name, rows_per_ray);
+  SWN_CHECK(ray_base >= 0 && ray_base <= (INT64_MAX - (int64_t)n_points) / rows_per_ray,
+            "%s: ray_base %lld is negative or overflows the element index (ray_base * rows_per_ray + point)", name, (long long)ray_base);
+  return 0;
+}
+
+extern "C" int swn_cells_gather_rng(const float* x, int stride, int col0, const int32_t* rows, long total, int n_points, uint64_t seed,
+                                    const int64_t* step_dev, int stream_id, int rows_per_ray, int64_t ray_base, float scale, float* x_out,
+                                    float* noise_out, void* stream) {
+  SWN_CHECK(x && rows && x_out, "swn_cells_gather_rng: null pointer");
+  SWN_CHECK(n_points >= 1 && total >= 0 && col0 >= 0 && col0 < stride, "swn_cells_gather_rng: bad sizes (n_points %d, total %ld, columns [%d, %d))",
+            n_points, total, col0, stride);
+  if (cells_rng_check("swn_cells_gather_rng", step_dev, noise_out, stream_id, rows_per_ray, ray_base, scale, n_points)) return -1;
+  if (total == 0) return 0;
+  const long n = total * (stride - col0);
+  SWN_CHECK(n <= 2147483647l * 256, "swn_cells_gather_rng: %ld elements exceed the grid", n);      // (cdiv returns an int)
+  hipLaunchKernelGGL(cells_gather_rng_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, stride, col0, rows, total, n_points,
+                     seed, step_dev, stream_id, (long)(ray_base * rows_per_ray), scale, x_out, noise_out);
+  SWN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int swn_cells_gather_padded_rng(const float* x, int stride, int col0, const int32_t* rows, const float* centroids, int n_cells,
+                                           int capacity, int n_points, uint64_t seed, const int64_t* step_dev, int stream_id,
+                                           int rows_per_ray, int64_t ray_base, float scale, float* x_out, float* noise_out, void* stream) {
+  SWN_CHECK(n_cells >= 1 && n_cells <= CELLS_MAX, "swn_cells_gather_padded_rng: n_cells %d outside [1, %d]", n_cells, CELLS_MAX);
+  SWN_CHECK(x && rows && centroids && x_out, "swn_cells_gather_padded_rng: null pointer");
+  SWN_CHECK(n_points >= 1 && capacity >= 1 && col0 >= 0, "swn_cells_gather_padded_rng: bad sizes (n_points %d, capacity %d, col0 %d)",
+            n_points, capacity, col0);
+  SWN_CHECK(stride - col0 == 7, "swn_cells_gather_padded_rng: columns [%d, %d) are not the 7 of (position, direction, image index)", col0,
+            stride);
+  if (cells_rng_check("swn_cells_gather_padded_rng", step_dev, noise_out, stream_id, rows_per_ray, ray_base, scale, n_points)) return -1;
+  const long n = (long)n_cells * capacity * 7;
+  SWN_CHECK((long)n_cells * capacity <= 2147483647l, "swn_cells_gather_padded_rng: %d cells of %d rows exceed the 32-bit row space", n_cells,
+            capacity);
+  hipLaunchKernelGGL(cells_gather_padded_rng_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, stride, col0, rows, centroids,
+                     n_cells, capacity, n_points, seed, step_dev, stream_id, (long)(ray_base * rows_per_ray), scale, x_out, noise_out);
   SWN_LAUNCH_CHECK();
   return 0;
 }

@@ -391,9 +391,12 @@ class GraphedMegaStep:
 
     One capture serves every batch of its shape, however its points fall over the cells - up to C per cell: a batch with more in a cell
     raises RuntimeError from the tail with no parameter touched, and the next replay is unaffected.  The jitter (perturb > 0) and the
-    sigma noise of both passes (noise_std > 0) are drawn inside the graph from the framework's device generator.
-    Not built: spherical-harmonics cells, seeded device noise for cells, data parallelism (no gradient all-reduce), the xyz_real
-    background half, a grouped launch over the cells."""
+    sigma noise of both passes (noise_std > 0) are drawn inside the graph from the framework's device generator - or, with the model's
+    seeded device noise on (MegaNeRF.set_device_noise before the capture), by the step itself: no noise tensor is passed, the captured
+    launches read the device step counter and the step's last captured launch advances it.  The counter is put back behind the warm-up
+    runs, so the first replay is the step it was set to and the replays equal the eager padded steps bit for bit.
+    Not built: spherical-harmonics cells, data parallelism (no gradient all-reduce), the xyz_real background half, a grouped launch
+    over the cells."""
 
     def __init__(self, model, rgbs, rays, image_indices, n_samples: int, cell_capacity, perturb: float = 1.0, noise_std: float = 1.0,
                  fine_samples: int = 0, warmup: int = 2):
@@ -407,15 +410,19 @@ class GraphedMegaStep:
         N, S, F = rays.shape[0], int(n_samples), int(fine_samples)
         self.rgbs, self.rays, self.idx = rgbs.clone().contiguous(), rays.clone().contiguous(), image_indices.clone().contiguous()
 
+        dn = model.device_noise          # seeded device noise: nothing is passed - the step draws, and its last launch advances the counter
+
         def run():
-            pr = torch.rand(N, S, device=dev) if perturb > 0 else None
-            noise = torch.randn(N * S, device=dev) * noise_std if noise_std > 0 else None
-            noise_f = torch.randn(N * F, device=dev) * noise_std if noise_std > 0 and F > 0 else None
-            return model.grad_step(self.rgbs, self.rays, self.idx, S, perturb, pr, noise, F, None, noise_f, self.cell_capacity)
+            pr = torch.rand(N, S, device=dev) if perturb > 0 and not dn else None
+            noise = torch.randn(N * S, device=dev) * noise_std if noise_std > 0 and not dn else None
+            noise_f = torch.randn(N * F, device=dev) * noise_std if noise_std > 0 and F > 0 and not dn else None
+            return model.grad_step(self.rgbs, self.rays, self.idx, S, perturb, pr, noise, F, None, noise_f, self.cell_capacity,
+                                   sigma_noise_std=noise_std if dn else 0.0)
 
         profiles = [m.profile for m in model.sub_modules]
         for m in model.sub_modules:
             m.profile = False
+        step0 = model.noise_state_dict()["step"]           # the warm-up steps advance the noise counter like real ones: put it back
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up on a side stream: allocates every cached buffer / workspace
@@ -423,6 +430,9 @@ class GraphedMegaStep:
                 run()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if dn:
+            model.noise.rewind(step0)
+            torch.cuda.synchronize()
         # a cell's cached buffers grow with the largest row count seen (a later eager compact step with more rows in a cell replaces
         # them): the capture keeps the ones it baked in alive
         self._held = [list(m._bufs.values()) + [getattr(m, "_ones", None)] for m in model.sub_modules]

@@ -64,12 +64,25 @@ backward_points or grad_step: ctx["counts"] is the device tensor of the true mem
 that did not fit, and apply_step(res=...) reads res["cell_overflow"] once behind the step's last launch - a batch with more than C
 members in a cell raises RuntimeError there, before any parameter, moment or step count is touched.  What padding costs: K C rows of
 network work against the batch's P (K times the largest cell's share at the tightest C).  What it buys: static shapes, so the step is
-captured into a hipGraph (graph.GraphedMegaStep).  Not built for the padded form: spherical-harmonics cells (sh_training), seeded
-device noise, data parallelism, the xyz_real background half, a grouped launch over the cells.
+captured into a hipGraph (graph.GraphedMegaStep).  Not built for the padded form: spherical-harmonics cells (sh_training), data
+parallelism, the xyz_real background half, a grouped launch over the cells.
 
-Not built for training (each raises NotImplementedError): the xyz_real background half, fp16 cells (one loss scale over K models), seeded
-device noise, graph capture of the COMPACT form (counts.tolist() sizes the ragged calls), expert / data parallelism, and
-rendering.render_rays on a model in training mode (the autograd bridge for a MegaNeRF is a later change).
+Seeded device noise (MegaNeRF.set_device_noise(seed, step, ray_base), opt-in, both forms): the model holds ONE noise.DeviceNoise; the
+cells' own stay off.  With it on grad_step draws what it is not handed as a pure function of (seed, step, stream, global element):
+
+    perturb_rand = rng_fill(stream 0, uniform, e = (ray_base + n) S + s)        fine_u = rng_fill(stream 2, e = (ray_base + n) F + f)
+    xin, noise = ops.cells_gather_rng / cells_gather_padded_rng(x, rows, .., seed, step, stream 1 | 3, R, ray_base, sigma_noise_std)
+    ops.rng_advance(step)                                                       the step's last launch (inside a captured step)
+
+The cells consume sigma noise per PACKED row - a point's value goes to every cell that holds it (sigma_noise[cluster_mask]) - so the
+gather draws it in place: packed row r of point p = rows[r] gets the normal draw of element ray_base R + p, the bits swn_rng_fill writes
+there, and the [N R] noise tensor is never written or read.  The eager step, a GraphedMegaStep replay and a resumed run
+(noise_state_dict) then compute the same step bit for bit.  Evaluation draws nothing: mega.render_rays refuses device_noise_seed, and
+a cell with its own seeded device noise switched on is refused.
+
+Not built for training (each raises NotImplementedError): the xyz_real background half, fp16 cells (one loss scale over K models),
+graph capture of the COMPACT form (counts.tolist() sizes the ragged calls), expert / data parallelism, gradient accumulation, the
+finite guard, and rendering.render_rays on a model in training mode (the autograd bridge for a MegaNeRF is a later change).
 """
 from __future__ import annotations
 
@@ -80,6 +93,7 @@ import torch
 
 from . import hier, ops, optim
 from .dense import DenseNeRF
+from .noise import DeviceNoise
 
 MAX_CELLS = 64      # swn_cells_*: the centroids live in LDS, a point's membership in one 64-bit mask
 
@@ -170,6 +184,7 @@ class MegaNeRF:
         self.sh_training = bool(sh_training)
         self.training = False
         self.moe_no_batch = False
+        self.noise = DeviceNoise()      # the seeded device noise's state (set_device_noise, joint training); the cells' own stay off
         if self.joint_training:
             self._check_trainable()
             self.lr = self.base_lr = float(sub_modules[0].base_lr)
@@ -194,8 +209,9 @@ class MegaNeRF:
             if m.dtype != self.dtype or m.dev != self.dev:
                 raise ValueError("joint_training: every cell must have the same compute dtype and device")
             if m.device_noise:
-                raise NotImplementedError("joint_training with seeded device noise (set_device_noise) on a cell is not built: supply "
-                                          "perturb_rand / sigma_noise, or let the step draw them with torch")
+                raise NotImplementedError("joint_training with seeded device noise (set_device_noise) switched on on a cell is refused: "
+                                          "the step's draws belong to the whole model - leave the cells' off and call "
+                                          "MegaNeRF.set_device_noise(seed)")
             if m.ep is not None:
                 raise NotImplementedError("joint_training with expert parallelism is not built (a cell has no experts to shard)")
 
@@ -269,9 +285,42 @@ class MegaNeRF:
     def set_expert_parallel(self, ep):
         raise NotImplementedError("MegaNeRF: expert parallelism is not built (the cells are dense models; nothing is sharded)")
 
+    # ------------------------------------------------------------------------------------------ seeded device noise
     def set_device_noise(self, seed, step: int = 0, ray_base: int = 0):
-        if seed is not None:
-            raise NotImplementedError("MegaNeRF has no seeded device noise: supply perturb_rand / sigma_noise, or let the step draw them")
+        """Seeded device-side noise for joint training (SwitchNeRF.set_device_noise's semantics; csrc/philox.hpp): seed = None turns it
+        off (the default - no launch differs from a model that never had it on).  On, grad_step / train_step draw what they are not
+        handed - the jitter (stream 0), the fine pass's u (stream 2) and, with sigma_noise_std > 0, the sigma noise of both passes
+        (streams 1 and 3, drawn at the cells' packed rows by swn_cells_gather_rng / _padded_rng) - from Philox4x32-10 keyed by (seed,
+        step, stream, global element): the same step eagerly and in a GraphedMegaStep replay, in the compact and the padded form, before
+        and after a resume (noise_state_dict).  The step lives on the device; grad_step's last launch advances it.  ray_base: the global
+        index of the batch's first ray.  An inference-only model draws nothing and refuses a seed; so does a host-resident model
+        (device "cpu": parameters only, no kernel can run on it - the counter is device memory the gather kernels read)."""
+        if seed is not None and not self.joint_training:
+            raise NotImplementedError("MegaNeRF.set_device_noise: seeded device noise belongs to joint training (evaluation draws "
+                                      "nothing) - construct the model with joint_training=True")
+        if seed is not None and self.dev.type != "cuda":
+            raise NotImplementedError("MegaNeRF.set_device_noise: seeded device noise needs the model on a GPU - this one is "
+                                      f"host-resident (device {self.dev}) and trains nothing; its step counter is device memory")
+        self.noise.set(seed, step, ray_base, self.dev)
+
+    @property
+    def device_noise(self) -> bool:
+        return self.noise.on
+
+    def set_ray_base(self, ray_base: int):
+        """The global index of the next batch's first ray (SwitchNeRF.set_ray_base)."""
+        self._need_joint("set_ray_base")
+        self.noise.set_base(ray_base)
+
+    def noise_state_dict(self) -> dict:
+        """{"seed", "step", "ray_base"} - what a resume needs besides the cells' parameters and Adam state (seed None: off).  Reads the
+        step back from the device."""
+        self._need_joint("noise_state_dict")
+        return self.noise.state_dict()
+
+    def load_noise_state_dict(self, sd: dict):
+        self._need_joint("load_noise_state_dict")
+        self.set_device_noise(sd.get("seed"), int(sd.get("step", 0)), int(sd.get("ray_base", 0)))
 
     def _need_joint(self, what):
         if not self.joint_training:
@@ -336,9 +385,10 @@ class MegaNeRF:
             sub_out[:, :3] = torch.sigmoid(sub_out[:, :3])
         return r["weights"], r["slot"], r["begin"], sub_out, r["hard"]
 
-    def _gather_cells(self, x, sigma_noise, col0=0):
+    def _gather_cells(self, x, sigma_noise, col0=0, sigma_rng=None):
         """The prologue of every forward over the points x: route, the ONE device-to-host read, cells_gather from column col0 on ->
-        (routing, xin [total, ..], noise [total] or None); routing = {weights, rows, begin, slot, counts (a host list), total, hard, P}."""
+        (routing, xin [total, ..], noise [total] or None); routing = {weights, rows, begin, slot, counts (a host list), total, hard, P}.
+        sigma_rng = (stream id, rows per ray, std): the noise is drawn at the packed rows from the model's seeded generator instead."""
         x = x.to(torch.float32).contiguous()
         noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
         weights, counts, begin, rows, slot = self.route(x)
@@ -346,7 +396,10 @@ class MegaNeRF:
         total = sum(n)
         if total == 0:      # only non-finite positions under a soft margin get here: their weights are NaN, so no cell counts as a member
             raise ValueError("MegaNeRF: no point belongs to a cell - the positions are not finite")
-        xin, nin = ops.cells_gather(x, rows, total, col0, noise)
+        if sigma_rng is None:
+            xin, nin = ops.cells_gather(x, rows, total, col0, noise)
+        else:
+            xin, nin = ops.cells_gather_rng(x, rows, total, col0, *self._sigma_rng(sigma_rng))
         return dict(weights=weights, rows=rows, begin=begin, slot=slot, counts=n, total=total, hard=self.boundary_margin == 1,
                     P=x.shape[0]), xin, nin
 
@@ -376,18 +429,26 @@ class MegaNeRF:
             b += n
 
     # ------------------------------------------------------------------------------------------ training through the cells
-    def _gather_cells_padded(self, x, sigma_noise, C):
+    def _sigma_rng(self, sigma_rng):
+        """(stream id, rows per ray, std) -> the draw arguments of ops.cells_gather_rng / cells_gather_padded_rng."""
+        stream_id, R, std = sigma_rng
+        return self.noise.seed, self.noise.step, stream_id, R, self.noise.base, std
+
+    def _gather_cells_padded(self, x, sigma_noise, C, sigma_rng=None):
         """_gather_cells in the padded form (module doc): no host read, every cell on C rows.  routing["counts"] is the device tensor of
         the true members, routing["overflow"] [1] the device count of memberships that did not fit, routing["C"] the capacity."""
         x = x.to(torch.float32).contiguous()
         noise = None if sigma_noise is None else sigma_noise.reshape(-1).to(torch.float32).contiguous()
         weights, counts = ops.cells_assign(x, self.centroids, self.cluster_dim_start, self.boundary_margin)
         begin, rows, slot, overflow = ops.cells_pack_padded(weights, counts, C)
-        xin, nin = ops.cells_gather_padded(x, rows, self.centroids, C, 0, noise)
+        if sigma_rng is None:
+            xin, nin = ops.cells_gather_padded(x, rows, self.centroids, C, 0, noise)
+        else:
+            xin, nin = ops.cells_gather_padded_rng(x, rows, self.centroids, C, 0, *self._sigma_rng(sigma_rng))
         return dict(weights=weights, rows=rows, begin=begin, slot=slot, counts=counts, total=len(self.sub_modules) * C,
                     hard=self.boundary_margin == 1, P=x.shape[0], C=C, overflow=overflow), xin, nin
 
-    def forward_points(self, x, sigma_noise=None, tag: str = "c", dirs=None, rows_per_group: int = 1, cell_capacity=None):
+    def forward_points(self, x, sigma_noise=None, tag: str = "c", dirs=None, rows_per_group: int = 1, cell_capacity=None, sigma_rng=None):
         """The training form of __call__: x [P, 3 + 3 + 1] -> ctx with ctx["out"] [P, 4] and what backward_points needs.  Every non-empty
         cell runs a SAVING forward on its packed rows (DenseNeRF.forward_rays on one-sample rays, as DenseNeRF.__call__ does), so a cell
         holds ONE live context per tag: a second forward_points under the same tag overwrites the first one's saved activations (the
@@ -398,9 +459,17 @@ class MegaNeRF:
         cell_capacity = C, or (C_coarse, C_fine) of which tag "f" takes the second: the padded form (module doc) - every cell, one
         without a member included, runs on exactly C rows; nothing is read on the host, so the pass can be captured into a hipGraph.
         ctx["counts"] is then the device int32 [K] of true members and ctx["overflow"] the device count of memberships dropped because
-        a cell had more than C (apply_step(res=...) refuses such a step).  Not built for cells with sh_deg."""
+        a cell had more than C (apply_step(res=...) refuses such a step).  Not built for cells with sh_deg.
+        sigma_rng = (stream id, R, std), with the model's device noise on (set_device_noise) and instead of sigma_noise: the sigma noise
+        is drawn at the cells' packed rows - point p = n * R + s of the batch is element ray_base * R + p of stream ops.RNG_SIGMA or
+        RNG_SIGMA_FINE, times std - so no [P] noise tensor exists (swn_cells_gather_rng / _padded_rng)."""
         self._need_joint("forward_points")
         cap = self._capacity(cell_capacity)
+        if sigma_rng is not None:
+            if sigma_noise is not None:
+                raise ValueError("forward_points: sigma_noise (a tensor) and sigma_rng (a draw request) exclude each other")
+            if not self.noise.on:
+                raise ValueError("forward_points: sigma_rng draws from the model's seeded device noise, which is off (set_device_noise)")
         if cap is None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError("MegaNeRF: graph capture is not built - counts.tolist() sizes the ragged per-cell calls on the host")
         sh = self.sh_deg is not None
@@ -419,7 +488,8 @@ class MegaNeRF:
         elif dirs is not None:
             raise ValueError("forward_points: dirs belong to cells with sh_deg; these points carry their direction columns")
         C = None if cap is None else cap[1 if tag == "f" else 0]
-        r, xin, nin = self._gather_cells(x, sigma_noise) if C is None else self._gather_cells_padded(x, sigma_noise, C)
+        r, xin, nin = (self._gather_cells(x, sigma_noise, 0, sigma_rng) if C is None else
+                       self._gather_cells_padded(x, sigma_noise, C, sigma_rng))
         total, cells = r["total"], [None] * len(self.sub_modules)
         if sh:
             # each cell's heads write its slice of the packed rows (degree 0: the reference NeRF's own sigmoid on its three outputs, as
@@ -458,15 +528,21 @@ class MegaNeRF:
             child.backward_net(c, d_sub[sl], None)
 
     def grad_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, fine_samples=0, fine_u=None,
-                  sigma_noise_fine=None, cell_capacity=None):
+                  sigma_noise_fine=None, cell_capacity=None, sigma_noise_std=0.0):
         """Forward + loss + backward of one training step (SwitchNeRF.grad_step's contract): zeroes every cell's gradient, fills it, and
         returns the metrics.  The whole batch goes through the cells in one call: a MegaNeRF's output for a point does not depend on the
         other points of its chunk, so there is no model_chunk_size loop.  fine_samples > 0: the sequence of SwitchNeRF.forward_hier
         (coarse pass with weights, sample_pdf from the detached weights, fine pass under tag "f", sort-merge, compositing of the union).
         cell_capacity: the padded form (forward_points) - no host read in the whole step; the result then holds "cell_overflow", the
-        device int32 [2] of memberships dropped in the coarse and the fine pass (0 for a pass that did not run), for apply_step(res=...)."""
+        device int32 [2] of memberships dropped in the coarse and the fine pass (0 for a pass that did not run), for apply_step(res=...).
+        Device noise on (set_device_noise): what is not supplied is drawn from the seeded generator - the jitter (perturb != 0; stream 0,
+        element (ray_base + n) * S + s), the fine pass's u (stream 2, (ray_base + n) * F + f) and, with sigma_noise_std > 0, the sigma
+        noise of both passes at the cells' packed rows (forward_points sigma_rng) - and the step's LAST launch advances the counter,
+        whatever optimizer_step the caller applies it with.  A supplied tensor wins, each for its own draw."""
         self._need_joint("grad_step")
         cap = self._capacity(cell_capacity)
+        dn = self.noise if self.noise.on else None
+        std = float(sigma_noise_std)
         o = ops
         N, S, F = rays.shape[0], int(n_samples), int(fine_samples)
         rays = rays.to(torch.float32).contiguous()
@@ -474,11 +550,13 @@ class MegaNeRF:
             m.grad.zero_()
         lin = self.sub_modules[0]._linspace
         if perturb != 0 and perturb_rand is None:
-            perturb_rand = torch.rand(N, S, device=self.dev)
+            perturb_rand = torch.rand(N, S, device=self.dev) if dn is None else dn.draw(o.RNG_JITTER, N * S, dn.base * S,
+                                                                                       o.RNG_UNIFORM).view(N, S)
         z = o.sample_z(rays, lin(S), perturb_rand if perturb != 0 else None, perturb, S)
         sh = self.sh_deg is not None          # (sh_deg: no direction columns, one direction per ray: rendering.py:316-330)
         dirs = rays[:, 3:6].contiguous() if sh else None
-        c = self.forward_points(_points(rays, z, image_indices, not sh), sigma_noise, "c", dirs, S, cap)
+        draw = lambda given, stream_id, R: (stream_id, R, std) if dn is not None and given is None and std > 0 else None
+        c = self.forward_points(_points(rays, z, image_indices, not sh), sigma_noise, "c", dirs, S, cap, draw(sigma_noise, o.RNG_SIGMA, S))
         raw = c["out"]
         if F == 0:
             cf = None
@@ -486,10 +564,13 @@ class MegaNeRF:
             out["rgb"], out["depth"], out["depth_variance"], _ = o.composite_fwd(raw, z)
         else:
             _, _, _, w = o.composite_fwd(raw, z, want_weights=True)
+            if fine_u is None and perturb != 0 and dn is not None:
+                fine_u = dn.draw(o.RNG_FINE_U, N * F, dn.base * F, o.RNG_UNIFORM).view(N, F)
             if fine_u is None:
                 fine_u = hier.default_fine_u(lin, N, F, perturb, self.dev)
             z_fine = o.sample_pdf(z, w, fine_u, F)
-            cf = self.forward_points(_points(rays, z_fine, image_indices, not sh), sigma_noise_fine, "f", dirs, F, cap)
+            cf = self.forward_points(_points(rays, z_fine, image_indices, not sh), sigma_noise_fine, "f", dirs, F, cap,
+                                     draw(sigma_noise_fine, o.RNG_SIGMA_FINE, F))
             zm, order, raw_m = o.merge_samples(z_fine, z, cf["out"], raw)
             out = dict(raw=raw_m, z=zm, order=order, z_fine=z_fine)
             out["rgb"], out["depth"], out["depth_variance"], _ = o.composite_fwd(raw_m, zm)
@@ -508,6 +589,7 @@ class MegaNeRF:
             res["ctx_fine"] = cf
         if cap is not None:
             res["cell_overflow"] = torch.cat([c["overflow"], cf["overflow"] if cf is not None else torch.zeros_like(c["overflow"])])
+        self.noise.advance()               # device noise: the next step draws at step + 1 (the last launch, inside a captured step)
         return res
 
     def set_accumulation(self, steps: int):
@@ -556,11 +638,12 @@ class MegaNeRF:
         optim.apply_tail(self.sub_modules, refresh=refresh)
 
     def train_step(self, rgbs, rays, image_indices, n_samples, perturb=1.0, perturb_rand=None, sigma_noise=None, optimizer_step=True,
-                   fine_samples=0, fine_u=None, sigma_noise_fine=None, cell_capacity=None):
+                   fine_samples=0, fine_u=None, sigma_noise_fine=None, cell_capacity=None, sigma_noise_std=0.0):
         """grad_step + apply_step; result keys as SwitchNeRF.train_step (loss, photo_loss, psnr, rgb, depth, depth_variance; gate_loss 0).
-        cell_capacity: the padded form (module doc); a batch that overflows a cell raises RuntimeError with no parameter touched."""
+        cell_capacity: the padded form (module doc); a batch that overflows a cell raises RuntimeError with no parameter touched.
+        sigma_noise_std: with device noise on (set_device_noise) the std of the sigma noise the step draws where none is supplied."""
         res = self.grad_step(rgbs, rays, image_indices, n_samples, perturb, perturb_rand, sigma_noise, fine_samples, fine_u, sigma_noise_fine,
-                             cell_capacity)
+                             cell_capacity, sigma_noise_std)
         self.apply_step(None, optimizer_step, res)
         return res
 
@@ -669,7 +752,8 @@ def render_rays(nerf: MegaNeRF, bg_nerf, rays, image_indices, hparams, sphere_ce
             raise NotImplementedError(f"hparams.sh_deg = {want} but {who} was built with sh_deg = {m.sh_deg}: build the container's "
                                       "models and the hparams with the same sh_deg")
     if getattr(hparams, "device_noise_seed", None) is not None:
-        raise NotImplementedError("device_noise_seed: MegaNeRF has no seeded device noise")
+        raise NotImplementedError("device_noise_seed: mega.render_rays is evaluation and draws nothing - the seeded device noise of a "
+                                  "MegaNeRF belongs to joint training (MegaNeRF.set_device_noise, then train_step)")
     if nerf.training or getattr(nerf, "graph_eval", False) or getattr(nerf, "graph_train", False):
         raise NotImplementedError("MegaNeRF renders in evaluation mode without graph capture (a joint_training model trains through "
                                   "MegaNeRF.train_step; call eval() before rendering)")

@@ -1118,6 +1118,38 @@ def cells_gather_padded(x, rows, centroids, capacity: int, col0: int = 0, sigma_
     return x_out, noise_out
 
 
+def _sigma_rng_args(seed: int, step_dev, stream_id: int, rows_per_ray: int, ray_base: int, scale: float):
+    assert step_dev.dtype == torch.int64 and step_dev.numel() == 1
+    return (int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev), int(stream_id), int(rows_per_ray), int(ray_base), float(scale))
+
+
+def cells_gather_rng(x, rows, total: int, col0: int, seed: int, step_dev, stream_id: int, rows_per_ray: int, ray_base: int, scale: float):
+    """cells_gather with the sigma noise drawn at the packed row (swn_cells_gather_rng): noise_out [total] = scale * the normal draw of
+    element ray_base * rows_per_ray + rows[r] of (seed, step_dev[0], stream_id) - rng_fill(P, ray_base * rows_per_ray, RNG_NORMAL, ...,
+    scale)[rows[r]] bit for bit, with no [P] tensor.  stream_id: RNG_SIGMA or RNG_SIGMA_FINE."""
+    P, stride = x.shape
+    assert x.dtype == torch.float32 and rows.dtype == torch.int32 and rows.numel() >= total
+    x_out = torch.empty(total, stride - col0, dtype=torch.float32, device=x.device)
+    noise_out = torch.empty(total, dtype=torch.float32, device=x.device)
+    call("swn_cells_gather_rng", _p(x), stride, int(col0), _p(rows), int(total), P,
+         *_sigma_rng_args(seed, step_dev, stream_id, rows_per_ray, ray_base, scale), _p(x_out), _p(noise_out), _stream())
+    return x_out, noise_out
+
+
+def cells_gather_padded_rng(x, rows, centroids, capacity: int, col0: int, seed: int, step_dev, stream_id: int, rows_per_ray: int,
+                            ray_base: int, scale: float):
+    """cells_gather_padded with the sigma noise drawn at the packed row (swn_cells_gather_padded_rng), addressed like cells_gather_rng;
+    a padding row gets exactly +0."""
+    P, stride = x.shape
+    K, Cc = centroids.shape[0], int(capacity)
+    assert x.dtype == centroids.dtype == torch.float32 and rows.dtype == torch.int32 and rows.numel() == K * Cc
+    x_out = torch.empty(K * Cc, stride - col0, dtype=torch.float32, device=x.device)
+    noise_out = torch.empty(K * Cc, dtype=torch.float32, device=x.device)
+    call("swn_cells_gather_padded_rng", _p(x), stride, int(col0), _p(rows), _p(centroids), K, Cc, P,
+         *_sigma_rng_args(seed, step_dev, stream_id, rows_per_ray, ray_base, scale), _p(x_out), _p(noise_out), _stream())
+    return x_out, noise_out
+
+
 def cells_blend(weights, slot, begin, sub_out, hard: bool):
     """out [P, C] = sum over the member cells (ascending) of weights * sub_out[begin[i] + slot] (swn_cells_blend), C = sub_out.shape[1]
     in {1, 4}; hard: the plain copy of the one member's row."""
