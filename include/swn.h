@@ -1045,6 +1045,60 @@ int swn_rays_from_directions(const float* directions, const float* c2w, int n_ca
 int swn_rays_from_pixels(const float* camera_table, int n_cameras, const void* cam_idx, const void* pix_idx, int idx_is_i64, long n, int W,
                          int H, int center_pixels, float near, float far, const float* altitude_range, float* rays, void* stream);
 
+/* ---- rays the NeRF-dataset way (nerf_rays.py; raygen_nerf.hip) ------------------------------------------------------------------------
+ * The reference's datasets/nerf_data in fp32, one thread per pixel: ray_utils.get_rays (:14-24), ndc_rays (:27-46), the loader's
+ * normalisation and scalar near / far (nerf_loader.py:155-177), load_bungee.get_bungee_nearfar_radii (:44-90).  For the pixel
+ * (col, row) - its corner, no + 0.5 - of a camera with K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] and pose c2w [3][4] (row-major):
+ *     c = ((col - cx) / fx, -(row - cy) / fy, -1);  d = c2w[:, :3] c (each dot product (c0 r0 + c1 r1) + c2 r2);  o = c2w[:, 3]
+ *     SWN_NERF_RAW         o, d as they are
+ *     SWN_NERF_NORMALIZED  d / sqrt(fma(dz, dz, fma(dy, dy, dx dx))) (torch.norm's CPU accumulation, one fused multiply-add per element)
+ *     SWN_NERF_NDC         ndc_rays(H, W, focal, near_ndc, o, d), not normalised; -1 / (W / (2 focal)), -1 / (H / (2 focal)) and
+ *                          2 near_ndc are formed in double on the host and rounded to fp32 once
+ *   columns 6, 7 of these three: the caller's scalar near / far.
+ *     SWN_NERF_BUNGEE_SPHERE / _FLAT   d normalised; near / far per ray:
+ *       sphere: dist = the nearer intersection of the ray with the sphere about scene_origin * scale (rounded to fp32) of radius
+ *               (6371011 + 250) * scale (near) and 6371011 * scale (far), formed in fp64 from the fp32 o, d, centre and rounded once;
+ *               near = |o - (o + dist d)| * 0.9, far likewise * 1.1
+ *       flat:   near = max((250 s - o_z s) / (d_z s), 1e-6), far = (0 - o_z s) / (d_z s), s = fp32(scale)
+ *       radii [n] = dx * 2 / fp32(sqrt(12)), dx(row) = |d(col, row) - d(col, row + 1)| (normalised directions, the neighbour's
+ *               recomputed in the thread); the last row takes dx(H - 3) - the reference's cat([dx, dx[:, -2:-1]]) over dx's H - 1 rows -
+ *               and dx(0) when H == 2.  H < 2 is refused.
+ * IEEE division and square root, no contraction but the one written above: the same pixel of the same camera gives the same bits
+ * through every entry.  No LDS, no atomics, no host read; the output is a pure function of the arguments.
+ * swn_nerf_rays_from_camera: ONE camera by value (`camera` points to HOST memory), mode RAW / NORMALIZED / NDC -> rays [n, 8] of the
+ *   row-major pixels [pixel_begin, pixel_begin + n).  focal and near_ndc are read in NDC only.  No [H, W, 3] tensor is written.
+ * swn_nerf_rays_bungee: the same for the bungee scenes: ray_nearfar SWN_NERF_SPHERE / SWN_NERF_FLAT, scene_origin three doubles in HOST
+ *   memory (sphere only) -> rays [n, 8] and radii [n].
+ * swn_nerf_rays_from_pixels: the gather form.  camera_table [n_cameras, 16] (device): c2w then fx, fy, cx, cy per camera; cam_idx /
+ *   pix_idx [n] int64 (idx_is_i64 != 0) or int32, pix_idx row-major in [0, W * H); any of the five modes; radii is written in the
+ *   bungee modes only (and may be NULL otherwise).  Index values are not checked.
+ * swn_nerf_rays_dirs: get_rays as the reference's own first step: camera_row (device, 16 floats as a table row, 16-byte aligned) ->
+ *   rays_o, rays_d [H, W, 3].   swn_nerf_ndc: ndc_rays over rays_o, rays_d [n, 3] -> out_o, out_d [n, 3].
+ * Errors return -1 and launch nothing: a null pointer, n <= 0, a pixel range outside W * H, an unknown mode or ray_nearfar, near > far,
+ * H < 2 in a bungee mode, a focal or scale that is not positive and finite, a misaligned pointer (rays and tables 16 bytes).          */
+#define SWN_NERF_RAW 0
+#define SWN_NERF_NORMALIZED 1
+#define SWN_NERF_NDC 2
+#define SWN_NERF_BUNGEE_SPHERE 3
+#define SWN_NERF_BUNGEE_FLAT 4
+#define SWN_NERF_SPHERE 0
+#define SWN_NERF_FLAT 1
+typedef struct swn_nerf_camera {
+  float c2w[12];
+  float fx, fy, cx, cy;
+  int32_t W, H;
+} swn_nerf_camera;
+int swn_nerf_rays_from_camera(const swn_nerf_camera* camera, int mode, float near, float far, double focal, double near_ndc,
+                              long pixel_begin, long n, float* rays, void* stream);
+int swn_nerf_rays_bungee(const swn_nerf_camera* camera, double scene_scaling_factor, const double* scene_origin, int ray_nearfar,
+                         long pixel_begin, long n, float* rays, float* radii, void* stream);
+int swn_nerf_rays_from_pixels(const float* camera_table, int n_cameras, const void* cam_idx, const void* pix_idx, int idx_is_i64, long n,
+                              int W, int H, int mode, float near, float far, double focal, double near_ndc, double scene_scaling_factor,
+                              const double* scene_origin, float* rays, float* radii, void* stream);
+int swn_nerf_rays_dirs(const float* camera_row, int W, int H, float* rays_o, float* rays_d, void* stream);
+int swn_nerf_ndc(const float* rays_o, const float* rays_d, long n, int W, int H, double focal, double near, float* out_o, float* out_d,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ def source_hash() -> str:
             h.update(open(f, "rb").read())
     return h.hexdigest()
 
-vp, i32, i64, f32, sz, u64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_uint64
+vp, i32, i64, f32, f64, sz, u64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t, C.c_uint64
 
 
 class ChainLayer(C.Structure):
@@ -55,6 +55,15 @@ class Camera(C.Structure):
     """swn_camera (include/swn.h): one camera by value - c2w [3][4] row-major, fx, fy, cx, cy, W, H, center_pixels, image_index."""
     _fields_ = [("c2w", f32 * 12), ("fx", f32), ("fy", f32), ("cx", f32), ("cy", f32), ("W", C.c_int32), ("H", C.c_int32),
                 ("center_pixels", C.c_int32), ("reserved", C.c_int32), ("image_index", C.c_int64)]
+
+
+class NerfCamera(C.Structure):
+    """swn_nerf_camera (include/swn.h): one NeRF-dataset camera by value - c2w [3][4] row-major, fx, fy, cx, cy (K's used entries), W, H."""
+    _fields_ = [("c2w", f32 * 12), ("fx", f32), ("fy", f32), ("cx", f32), ("cy", f32), ("W", C.c_int32), ("H", C.c_int32)]
+
+
+NERF_RAW, NERF_NORMALIZED, NERF_NDC, NERF_BUNGEE_SPHERE, NERF_BUNGEE_FLAT = range(5)       # SWN_NERF_* modes (include/swn.h)
+NERF_SPHERE, NERF_FLAT = 0, 1                                                             # SWN_NERF_SPHERE / SWN_NERF_FLAT
 
 
 class ChainDesc(C.Structure):
@@ -192,6 +201,11 @@ SIGNATURES = {
     "swn_ray_directions": [i32, i32, f32, f32, f32, f32, i32, vp, vp],
     "swn_rays_from_directions": [vp, vp, i32, i64, f32, f32, vp, vp, vp],
     "swn_rays_from_pixels": [vp, i32, vp, vp, i32, i64, i32, i32, i32, f32, f32, vp, vp, vp],
+    "swn_nerf_rays_from_camera": [C.POINTER(NerfCamera), i32, f32, f32, f64, f64, i64, i64, vp, vp],
+    "swn_nerf_rays_bungee": [C.POINTER(NerfCamera), f64, vp, i32, i64, i64, vp, vp, vp],
+    "swn_nerf_rays_from_pixels": [vp, i32, vp, vp, i32, i64, i32, i32, i32, f32, f32, f64, f64, f64, vp, vp, vp, vp],
+    "swn_nerf_rays_dirs": [vp, i32, i32, vp, vp, vp],
+    "swn_nerf_ndc": [vp, vp, i64, i32, i32, f64, f64, vp, vp, vp],
     "swn_cast": [vp, vp, i32, i64, vp],
     "swn_cast_transpose": [vp, vp, i32, i32, i32, i32, vp],
 }

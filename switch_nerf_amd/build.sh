@@ -11,7 +11,7 @@ build_one() {   # $1 = object directory, $2 = extra flags, $3 = output library
   mkdir -p "$OBJ"
   local pids=()
   newer() { [ ! -f "$2" ] || [ "$1" -nt "$2" ] || [ common.hpp -nt "$2" ] || [ pe_store.hpp -nt "$2" ] || [ philox.hpp -nt "$2" ] || [ row16.hpp -nt "$2" ] || [ adam.hpp -nt "$2" ] || [ ../../include/swn.h -nt "$2" ]; }
-  for f in elementwise gate_mfma route chain chain_big wgrad sampling mip bounds hashgrid rayops points residual rng affine bg_compact cells sh accum finite_guard ssim raygen; do
+  for f in elementwise gate_mfma route chain chain_big wgrad sampling mip bounds hashgrid rayops points residual rng affine bg_compact cells sh accum finite_guard ssim raygen raygen_nerf; do
     if newer $f.hip "$OBJ/$f.o"; then $HIPCC $FLAGS -c $f.hip -o "$OBJ/$f.o" & pids+=($!); fi
   done
   # chain.hip a second time: the 512-feature geometry; a third time: the concat-skip layer mode of the dense NeRF trunk (kept out of
@@ -20,7 +20,7 @@ build_one() {   # $1 = object directory, $2 = extra flags, $3 = output library
   if newer chain.hip "$OBJ/chain_wide2.o"; then $HIPCC $FLAGS -DSWN_WIDE=2 -c chain.hip -o "$OBJ/chain_wide2.o" & pids+=($!); fi
   if newer chain.hip "$OBJ/chain_cat.o"; then $HIPCC $FLAGS -DSWN_CONCAT=1 -c chain.hip -o "$OBJ/chain_cat.o" & pids+=($!); fi
   for p in "${pids[@]}"; do wait $p; done
-  $HIPCC --offload-arch=gfx950 -shared -fPIC "$OBJ"/{elementwise,gate_mfma,route,chain,chain_big,chain_wide,chain_wide2,chain_cat,wgrad,sampling,mip,bounds,hashgrid,rayops,points,residual,rng,affine,bg_compact,cells,sh,accum,finite_guard,ssim,raygen}.o -o "$OUT"
+  $HIPCC --offload-arch=gfx950 -shared -fPIC "$OBJ"/{elementwise,gate_mfma,route,chain,chain_big,chain_wide,chain_wide2,chain_cat,wgrad,sampling,mip,bounds,hashgrid,rayops,points,residual,rng,affine,bg_compact,cells,sh,accum,finite_guard,ssim,raygen,raygen_nerf}.o -o "$OUT"
   echo "built $OUT"
 }
 # SWN_VARIANT=name (experiments): the bf16 library built with SWN_DEFS into libswn_hip_<name>.so / build_<name>/ - select it at run time

@@ -1836,6 +1836,90 @@ def rays_from_pixels(table, cam_idx, pix_idx, W: int, H: int, center_pixels: boo
     return out
 
 
+# ---- rays the NeRF-dataset way (csrc/raygen_nerf.hip; the user-facing layer: nerf_rays.py)
+def _radii_out(out, n: int, dev):
+    if out is None:
+        return torch.empty(n, 1, dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, 1) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"radii_out must be a contiguous fp32 tensor ({n}, 1) on {dev}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def _origin_arg(scene_origin):
+    """-> a host double[3] for the globe's centre, or None."""
+    if scene_origin is None:
+        return None
+    o = [float(v) for v in scene_origin]
+    if len(o) != 3:
+        raise ValueError(f"scene_origin must have three values, got {len(o)}")
+    return (C.c_double * 3)(*o)
+
+
+def nerf_rays_from_camera(camera: "_lib.NerfCamera", mode: int, near: float, far: float, focal: float, near_ndc: float, pixel_begin: int,
+                          n: int, out=None, device=None):
+    """swn_nerf_rays_from_camera: the rays [n, 8] of the row-major pixels [pixel_begin, pixel_begin + n) of one camera (a
+    _lib.NerfCamera, passed by value) in mode _lib.NERF_RAW / NERF_NORMALIZED / NERF_NDC, written into `out` when given.  One launch."""
+    dev = out.device if out is not None else torch.device("cuda" if device is None else device)
+    out = _rays_out(out, n, dev)
+    with torch.cuda.device(out.device):
+        call("swn_nerf_rays_from_camera", C.byref(camera), int(mode), float(near), float(far), float(focal), float(near_ndc),
+             int(pixel_begin), int(n), _p(out), _stream())
+    return out
+
+
+def nerf_rays_bungee(camera: "_lib.NerfCamera", scene_scaling_factor: float, scene_origin, ray_nearfar: int, pixel_begin: int, n: int,
+                     out=None, radii_out=None, device=None):
+    """swn_nerf_rays_bungee: rays [n, 8] with per-ray near / far (_lib.NERF_SPHERE / NERF_FLAT) and the mip radii [n, 1].  One launch."""
+    given = out if out is not None else radii_out
+    dev = given.device if given is not None else torch.device("cuda" if device is None else device)
+    out = _rays_out(out, n, dev)
+    radii = _radii_out(radii_out, n, out.device)
+    with torch.cuda.device(out.device):
+        call("swn_nerf_rays_bungee", C.byref(camera), float(scene_scaling_factor), _origin_arg(scene_origin), int(ray_nearfar),
+             int(pixel_begin), int(n), _p(out), _p(radii), _stream())
+    return out, radii
+
+
+def nerf_rays_from_pixels(table, cam_idx, pix_idx, W: int, H: int, mode: int, near: float, far: float, focal: float, near_ndc: float,
+                          scene_scaling_factor: float, scene_origin, out=None, radii_out=None):
+    """swn_nerf_rays_from_pixels: table [M, 16] fp32 (c2w, fx, fy, cx, cy per camera), cam_idx / pix_idx [n] both int32 or both int64,
+    any _lib.NERF_* mode -> rays [n, 8], and radii [n, 1] in the bungee modes (None otherwise).  Index values are not checked."""
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] == 16
+    assert cam_idx.dtype == pix_idx.dtype and cam_idx.shape == pix_idx.shape and cam_idx.dim() == 1
+    assert cam_idx.device == pix_idx.device == table.device
+    n = cam_idx.shape[0]
+    out = _rays_out(out, n, table.device)
+    radii = _radii_out(radii_out, n, table.device) if mode in (_lib.NERF_BUNGEE_SPHERE, _lib.NERF_BUNGEE_FLAT) else None
+    cp, i64 = _idx_arg(cam_idx)
+    pp, _ = _idx_arg(pix_idx)
+    with torch.cuda.device(out.device):
+        call("swn_nerf_rays_from_pixels", _p(table), table.shape[0], cp, pp, i64, n, int(W), int(H), int(mode), float(near), float(far),
+             float(focal), float(near_ndc), float(scene_scaling_factor), _origin_arg(scene_origin), _p(out), _p(radii), _stream())
+    return out, radii
+
+
+def nerf_rays_dirs(camera_row, W: int, H: int):
+    """swn_nerf_rays_dirs: camera_row [16] fp32 on the device (c2w, fx, fy, cx, cy) -> raw rays_o, rays_d, each [H, W, 3]."""
+    assert camera_row.dtype == torch.float32 and camera_row.numel() == 16 and camera_row.is_contiguous() and camera_row.is_cuda
+    if camera_row.data_ptr() % 16:
+        camera_row = camera_row.clone()
+    o = torch.empty(int(H), int(W), 3, dtype=torch.float32, device=camera_row.device)
+    d = torch.empty_like(o)
+    with torch.cuda.device(o.device):
+        call("swn_nerf_rays_dirs", _p(camera_row), int(W), int(H), _p(o), _p(d), _stream())
+    return o, d
+
+
+def nerf_ndc(rays_o, rays_d, W: int, H: int, focal: float, near: float):
+    """swn_nerf_ndc: ndc_rays over contiguous fp32 device tensors rays_o, rays_d [n, 3] -> (o, d), each [n, 3]."""
+    assert rays_o.dtype == rays_d.dtype == torch.float32 and rays_o.shape == rays_d.shape and rays_o.dim() == 2 and rays_o.shape[1] == 3
+    assert rays_o.is_contiguous() and rays_d.is_contiguous() and rays_o.device == rays_d.device and rays_o.is_cuda
+    o, d = torch.empty_like(rays_o), torch.empty_like(rays_d)
+    with torch.cuda.device(o.device):
+        call("swn_nerf_ndc", _p(rays_o), _p(rays_d), rays_o.shape[0], int(W), int(H), float(focal), float(near), _p(o), _p(d), _stream())
+    return o, d
+
+
 def cast(src, dst):
     call("swn_cast", _p(src), _p(dst), _dt(dst), src.numel(), _stream())
     return dst

@@ -490,3 +490,53 @@ def validate_image(nerf, bg_nerf, camera, target, hparams, near: float, far: flo
     typ = "fine" if "rgb_fine" in results else "coarse"
     image = results[f"rgb_{typ}"].view(camera.H, camera.W, 3)
     return metrics.image_metrics(image, target, valid_mask=valid_mask), image
+
+
+def _render_image_nerf_loop(who, nerf, camera, hparams, gen, render):
+    """The walk Runner.render_image_nerf / render_image_nerf_mip share: batches of hparams.image_pixel_batch_size pixels (a ragged last
+    batch), gen(begin, n) makes the batch's rays on the device, render(...) is the batch's render_rays / render_rays_mip call; the
+    results are assembled on the device as render_image assembles them."""
+    from . import nerf_rays
+    if getattr(nerf, "training", False):
+        raise RuntimeError(f"{who}: nerf is in training mode; validation images are rendered in evaluation (call .eval())")
+    P = camera.W * camera.H
+    results: Dict[str, torch.Tensor] = {}
+    loose: Dict[str, list] = {}
+    with torch.no_grad():
+        for begin, n in nerf_rays.batches(P, hparams.image_pixel_batch_size):
+            batch, _ = render(*gen(begin, n))
+            for k, v in batch.items():
+                if v.dim() >= 1 and v.shape[0] == n and not k.startswith("gate_loss"):
+                    if k not in results:
+                        results[k] = torch.empty(P, *v.shape[1:], dtype=v.dtype, device=v.device)
+                    results[k][begin:begin + n] = v
+                else:
+                    loose.setdefault(k, []).append(v)
+    for k, v in loose.items():
+        results[k] = torch.stack(v) if v[0].dim() == 0 else torch.cat(v)
+    return results
+
+
+def render_image_nerf(nerf, camera, hparams, near: float, far: float, mode: str = "normalized", focal: Optional[float] = None,
+                      near_ndc: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Runner.render_image_nerf (runner.py:2943-2974) from a nerf_rays.PinholeCamera: the image is walked in
+    batches of hparams.image_pixel_batch_size pixels, each batch's rays come from ONE launch (nerf_rays.camera_rays in `mode`:
+    "normalized" for Blender / LLFF no_ndc, "ndc" for forward-facing LLFF, "raw") and go through render_rays(nerf, None, rays,
+    image_indices=None, ..., get_depth=True, get_depth_variance=False, get_bg_fg_rgb=False).  -> the reference's result keys as device
+    tensors: a per-ray value in its slice of a [H * W, ...] tensor, the gate losses concatenated in batch order."""
+    from . import nerf_rays
+    dev = _model_device(nerf) if not getattr(nerf, "training", False) else None
+    gen = lambda begin, n: (nerf_rays.camera_rays(camera, mode, near, far, focal, near_ndc, begin, n, device=dev),)
+    render = lambda r: render_rays(nerf, None, r, None, hparams, None, None, True, False, False)
+    return _render_image_nerf_loop("render_image_nerf", nerf, camera, hparams, gen, render)
+
+
+def render_image_nerf_mip(nerf, camera, hparams, scene_scaling_factor: float, scene_origin, ray_nearfar: str) -> Dict[str, torch.Tensor]:
+    """Runner.render_image_nerf_mip (runner.py:2977-3008) from a nerf_rays.PinholeCamera: each batch's rays
+    and mip radii come from ONE launch (nerf_rays.bungee_rays: per-ray near / far of the "sphere" or "flat" form) and go through
+    render_rays_mip(nerf, rays, radii, image_indices=None, hparams, get_depth=True, get_depth_variance=False)."""
+    from . import nerf_rays
+    dev = _model_device(nerf) if not getattr(nerf, "training", False) else None
+    gen = lambda begin, n: nerf_rays.bungee_rays(camera, scene_scaling_factor, scene_origin, ray_nearfar, begin, n, device=dev)
+    render = lambda r, radii: render_rays_mip(nerf, r, radii, None, hparams, True, False)
+    return _render_image_nerf_loop("render_image_nerf_mip", nerf, camera, hparams, gen, render)
